@@ -1,30 +1,35 @@
 #!/usr/bin/env python3
-"""bench.py — headline benchmark of the hot path: restarted GCR iterations/sec and SpMV HBM GB/s
-on the 3-D 7-point Poisson system of BASELINE.json configs[1] (128^3, unpreconditioned GCR
-restart 5, complex fp64, x0 = 0, deterministic RHS), one process per GPU.
+"""bench.py — headline benchmark of the hot path: restarted GCR iterations/sec on the 3-D 7-point Poisson system of
+BASELINE.json configs[1] (128^3, unpreconditioned GCR restart 5, complex fp64, x0 = 0, deterministic RHS), one process
+per GPU.
 
-  python bench.py --gpus 1 --steps 200 --warmup 20
+  python bench.py --gpus 1 --steps 200 --warmup 20                  the headline line alone
+  python bench.py --gpus 1 --steps 200 --warmup 20 --full           ... and everything else this script measures
+  python bench.py --gpus 1 --steps 200 --dump-outputs DIR           ... and what the timed solve computed, as DIR/<name>.npy
   python bench.py --gpus N ...                      (WORLD_SIZE unset: starts its N ranks itself)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-A "step" is one GCR iteration (1 SpMV + the fused orthogonalisation kernels).  The timed region is
-one mgcr_gcr_solve call limited to exactly K iterations (tol = 0 so it cannot stop early), inputs
-resident in HBM, bracketed by barrier + device synchronisation, max over ranks; it is repeated until
->= 0.25 s have been timed and the MEDIAN is reported (`timing` holds repetitions, min and max).
+A "step" is one GCR iteration (1 SpMV + the fused orthogonalisation kernels).  The warm-up is a solve of W (at least 1)
+iterations, then more solves until WARMUP_MIN_S of solving have passed; the timed region is ONE mgcr_gcr_solve call limited
+to exactly K iterations (tol = 0 so it cannot stop early), inputs resident in HBM, bracketed by barrier + device
+synchronisation, max over ranks: value = K / its seconds, ms_per_step = its milliseconds / K.  --dump-outputs DIR then
+writes that solve's x (float64 [re, im] pairs; a fixed, seeded sample of its rows when it is larger than 64 MB) and
+residual history (dump_outputs).
 N > 1: the grid grows along i to (128 N) x 128 x 128 and is slab-partitioned, 128 planes (= the N=1
 problem) per GPU — weak scaling; value = N * iterations/s (shard-iterations/s).
 
-One JSON line on stdout (rank 0) with `roofline` (the phase of the iteration that takes longest,
-hipEvent-timed on the library's own stream inside a solve), `cpu_baseline` (the real reference,
-oracle/_ref/ref_harness, on this box's host cores; the oracle port when that binary is absent — `kind` and
-`binary` say which), `cpu_baseline_optimised` (OpenMP fused-pass CPU port) and, at N = 1,
-`workloads`: the other BASELINE.json configs, each measured by a child process of this script
-(`python bench.py --workload NAME` runs one alone).
+One JSON line on stdout (rank 0).  With --full it also carries `timing_repeated` (the same solve repeated until >= 0.25 s
+have been timed: median, min, max), `phases` and `roofline` (the phase of the iteration that takes longest, hipEvent-timed
+on the library's own stream inside a solve), `spmv` (stand-alone applies, cold and back to back), `cpu_baseline` (the real
+reference, oracle/_ref/ref_harness, on the host's cores; the oracle port when that binary is absent — `kind` and
+`binary` say which), `cpu_baseline_optimised` (OpenMP fused-pass CPU port) and `workloads`: the other
+BASELINE.json configs, each measured by a child process of this script (`python bench.py --workload NAME` runs one alone;
+--no-cpu-baseline / --no-extras leave those parts out of a --full line).
 
-Process structure.  N = 1: the headline runs in this process, every other workload in a child process
-(bounded time; a failure is recorded, never fatal).  N > 1: each rank is a SUPERVISOR that never touches
-the GPU; it starts the measuring WORKER as a child process and, should the worker fail or hang on any
+Process structure.  N = 1: the headline runs in this process (the library alone: torch is not imported), every other
+workload in a child process (bounded time; a failure is recorded, never fatal).  N > 1: each rank is a SUPERVISOR that
+never touches the GPU; it starts the measuring WORKER as a child process and, should the worker fail or hang on any
 rank, all supervisors agree (gloo) to try again with a more conservative transport: peer-write kernels
 -> plain RCCL -> host-staged.  `launch` in the JSON says what ran.  With WORLD_SIZE unset the N
 supervisors are started by this script (the launcher), which exits non-zero if any of them does.
@@ -52,6 +57,7 @@ LADDER = [("default: peer-write kernels where their self-test passes, RCCL other
           ("RCCL only", {"MGCR_PEER_ALLREDUCE": "0", "MGCR_PEER_HALO": "0"}),
           ("host-staged transport (slow; a flagged line instead of none)", {"MGCR_BENCH_TRANSPORT": "host"})]
 ATTEMPT_TIMEOUT_S = [420, 240, 240]
+WARMUP_MIN_S = 0.2      # seconds of solving before the timed steps, the --warmup steps included
 
 
 # ------------------------------------------------------------------------------------------------
@@ -232,10 +238,10 @@ def run_supervisor(args, argv):
         if good:
             ok, result, used = True, parsed, (label, mode_env)
             break
-    # configs[3] and configs[4] in their multi-GPU form, with the transport that carried the headline; bounded in time and
+    # --full: configs[3] and configs[4] in their multi-GPU form, with the transport that carried the headline; bounded in time and
     # never fatal (skipped when the headline needed long: the one JSON line must not be lost to a time limit)
     extras = {}
-    if ok and args is not None and not args.no_extras:
+    if ok and args is not None and args.full and not args.no_extras:
         for name in DIST_WORKLOADS:
             go = torch.tensor([1 if time.time() - t_start < 360 else 0], dtype=torch.int32)
             dist.broadcast(go, src=0)
@@ -555,12 +561,16 @@ def run_headline(args, with_cpu=True):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     import ctypes
-    import torch
     import mgpreconditionedgcr_amd as mg
     from mgpreconditionedgcr_amd import Field, GCR, GCR_Param, Sparse, problems
 
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a GPU (there is no CPU fallback for the product path)")
+    # one GPU: the library is the whole path (its own HIP stream; mg.init raises without a GPU, there is no CPU fallback).
+    # torch only carries the control plane of a multi-GPU run.
+    torch = None
+    if world > 1:
+        import torch
+        if not torch.cuda.is_available():
+            raise SystemExit("bench.py needs a GPU (there is no CPU fallback for the product path)")
     # bring-up switches: MGCR_BENCH_ONE_GPU=1 puts every rank on GPU 0 so that the N > 1 code path can be rehearsed on a
     # one-GPU box (RCCL refuses two ranks on one device: the run then uses the host-staged transport); numbers obtained
     # that way are not benchmark results.  MGCR_BENCH_TRANSPORT=host: host-staged (gloo) transport on purpose.
@@ -568,7 +578,8 @@ def run_headline(args, with_cpu=True):
     host_transport = os.environ.get("MGCR_BENCH_TRANSPORT", "rccl") == "host" or (one_gpu and world > 1)
     if one_gpu:
         local_rank = 0
-    torch.cuda.set_device(local_rank)
+    if torch is not None:
+        torch.cuda.set_device(local_rank)
     mg.init(local_rank)
     dist = None
     n = args.n
@@ -609,6 +620,11 @@ def run_headline(args, with_cpu=True):
         if dist is not None:
             dist.barrier()
 
+    def synchronize():
+        mg.lib().mgcr_synchronize()
+        if torch is not None:
+            torch.cuda.synchronize()
+
     # one solver object for all runs: its work vectors are allocated by the warm-up solve and re-used
     # (GCR_Param is re-read at every solve, like the reference's GCR does with its GCR_Param*)
     gparam = GCR_Param(0, args.restart, 1, 0.0, False)
@@ -617,13 +633,11 @@ def run_headline(args, with_cpu=True):
     def run(iters, profile=False):
         x.set_zero()
         gparam.max_iter, gparam.check_every, gparam.profile_spmv = iters, max(iters, 1), profile
-        torch.cuda.synchronize()
-        mg.lib().mgcr_synchronize()
+        synchronize()
         barrier()
         t0 = time.perf_counter()
         gcr.solve(rhs, x)
-        mg.lib().mgcr_synchronize()
-        torch.cuda.synchronize()
+        synchronize()
         dt = time.perf_counter() - t0
         barrier()
         if dist is not None:  # max over ranks
@@ -633,87 +647,31 @@ def run_headline(args, with_cpu=True):
         assert gcr.last_iterations == iters, (gcr.last_iterations, iters)
         return dt
 
-    run(max(args.warmup, 1))  # at least one untimed solve: it allocates the solver's work vectors
-    # the number of repetitions must be the same on every rank: rank 0 decides after the first timed solve
-    first = run(args.steps)
-    reps = int(min(400, max(5, 0.25 / max(first, 1e-6))))
-    if dist is not None:
-        t = torch.tensor([reps], dtype=torch.int64)
-        dist.broadcast(t, src=0)
-        reps = int(t[0])
-    samples = [first] + [run(args.steps) for _ in range(reps - 1)]
-    st = stats(samples)
-    dt = st["median"]
+    dt_w = run(max(args.warmup, 1))  # the warm-up steps: at least one untimed solve, it allocates the solver's work vectors
+    # The first solves after start-up run 1-3 % slower than the ones after them (clocks, caches): keep warming up with solves of
+    # about 20 ms (at most the timed length) until WARMUP_MIN_S of solving have passed.  The solve times are maxima over the ranks,
+    # so every rank runs the same number of them.
+    it_w, warm_s = max(args.warmup, 1), dt_w
+    while warm_s < WARMUP_MIN_S:
+        it_w = int(min(args.steps, max(args.restart, it_w * 0.02 / max(dt_w, 1e-6))))
+        dt_w = run(it_w)
+        warm_s += dt_w
+    # The solver keeps a residual-history buffer of max_iter + 1 entries (and fewer direction slots for a solve shorter
+    # than a restart cycle): size it for the timed solve now, with a solve that stops after its first iteration
+    # (|r|/|b| <= 2 always holds), so that no allocation falls into the timed region.
+    gparam.max_iter, gparam.check_every, gparam.tol = args.steps, 1, 2.0
+    x.set_zero()
+    gcr.solve(rhs, x)
+    gparam.tol = 0.0
+    # THE timed steps: one solve of exactly --steps iterations (tol = 0, it cannot stop early)
+    dt = run(args.steps)
     hist = gcr.last_history
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x.to_numpy(), hist)
     ms_per_step = dt * 1e3 / args.steps
     it_per_s = args.steps / dt
-
-    # Per-phase timing IN SITU: one more solve of the same length with hipEvents (library stream) between
-    # the phases of every iteration — back-to-back replays of one kernel would be served from the
-    # 256 MiB Infinity Cache once its operands fit, which at this size they do.
-    run(args.steps, profile=True)
-    ph_ms = (ctypes.c_double * 3)()
-    n_it, fused = ctypes.c_int32(), ctypes.c_int32()
-    mg.lib().mgcr_gcr_last_profile(ph_ms, ctypes.byref(n_it), ctypes.byref(fused))
-    ph_us = [1e3 * v / max(n_it.value, 1) for v in ph_ms]           # average microseconds per iteration
-    y = Field(dims)
-    spmv_ms_replay = A.bench_apply(rhs, y, reps=args.spmv_reps)
-    cold, cold_copy = (None, None)
-    if world == 1:
-        cold, cold_copy = cold_apply_ms(mg, A, rhs, y, args.spmv_reps, Field)
     stored = A.stored_bytes()
-    cold_read = cold_apply_read_sweep(mg, A, rhs, y, args.spmv_reps, Field, stored["matrix_bytes"] + 16 * ncol + 16 * N) if world == 1 else None
     fmt, npat = A.storage_format()
-    V = 16 * N
-    R = args.restart
-    b_phase, mean_lim = gcr_phase_model(n_it.value, R, V, stored["matrix_bytes"], ncol, N, fused.value)
-    names = ["xr_update_kernel (alpha, residual ring, |r|^2)" if fused.value != 5 else "(no launch but the solve's last update: the residual update runs inside the apply kernel)",
-             "step_apply_kernel (SpMV + beta dot products, one kernel)" if fused.value == 1 else
-             "step_apply_xr*_kernel (residual update + SpMV + beta dot products, one kernel)" if fused.value == 5 else "SpMV + multidot_kernel",
-             "build_lean_kernel<1..%d> / build_close_kernel<%d> (direction build + x update)" % (R - 1, R)]
-    if fused.value >= 2:
-        names[0] = "xr_update_kernel (alpha, residual ring, |r|^2)" + (
-            ": only the updates that open or end the solve%s — the others run at the end of step_build_kernel" % ("" if fused.value == 4 else " or follow a cycle's closing step") if fused.value >= 3 else "")
-        names[1] = ("step_build_kernel<1..%d> (SpMV + beta dot products + direction build%s in ONE launch, A r stays in LDS)%s"
-                    % (R if fused.value == 4 else R - 1, " + the next step's residual update" if fused.value >= 3 else "",
-                       "" if fused.value == 4 else "; the step that closes a cycle: step_apply_kernel<%d>" % R))
-        names[2] = ("(no launch: every step builds inside step_build_kernel; what is timed here are the event records of an empty slot)" if fused.value == 4 else
-                    "build_close_kernel<%d> (the step that closes a cycle; the other steps build inside step_build_kernel)" % R)
-    keys = ["xr", "apply_dots", "build"]
-    dom = max(range(3), key=lambda k: ph_us[k])
-    achieved = b_phase[dom] / (ph_us[dom] * 1e-6) / 1e9
-    lims_timed = [((k - 1) % R) + 1 for k in range(1, max(n_it.value, 1) + 1)]
-    traffic, traffic_note = pmc_traffic(keys[dom], n, lims_timed, R) if world == 1 else (None, "N > 1")
-    b_spmv_survey = spmv_algorithmic_bytes(nnz, N, ncol)
-    iter_bytes_survey = b_spmv_survey + (13 + 3 * mean_lim) * V   # SURVEY.md §8(d) accounting
-    iter_bytes_ours = sum(b_phase)                                # what this implementation moves
-    spmv_bytes = stored["matrix_bytes"] + 16 * ncol + 16 * N
-    cold_ms = cold["median"] if cold else None
-
-    # N > 1: what ONE GPU does on its own shard with the kernel path the distributed solve runs — the three kernels per
-    # iteration; the one-launch steps (gcr_stepbuild.hip) stop at the process boundary, their in-launch sums do not cross GPUs —
-    # so that per_shard_it_per_s / scaling_baseline_it_per_s is the price of the communication alone, and the N = 1 headline
-    # (one-launch steps) is not what an N-GPU line gets divided by.  Every rank measures its own shard; the slowest counts.
-    scaling_baseline = None
-    if world > 1:
-        Nl, ncl, rp, ci, va = problems.poisson3d_csr(n)
-        Aloc = Sparse(Nl, ncl, rp, ci, va)
-        del rp, ci, va
-        prev_sb, prev_res = mg.set_option("step_build", 0), mg.set_option("resident_solver", 0)
-        try:
-            gl = GCR(Aloc, GCR_Param(0, args.restart, args.steps, 0.0, False, check_every=args.steps))
-            xl, rl = Field(dims), Field(dims).fill_rhs(0)
-            timed_solve(mg, gl, rl, xl)
-            sb = stats(repeat_timed(lambda: timed_solve(mg, gl, rl, xl), min_total=0.15, min_reps=5))
-        finally:
-            mg.set_option("step_build", prev_sb)
-            mg.set_option("resident_solver", prev_res)
-        t = torch.tensor([sb["median"]], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        scaling_baseline = {"it_per_s": args.steps / float(t[0]), "this_rank_seconds": sb,
-                            "what": "single-GPU solve of one %d^3 shard, same %d iterations, three kernels per iteration (step_build and the resident "
-                                    "solver off: the path a distributed shard runs); max over ranks" % (n, args.steps)}
-        del Aloc, gl, xl, rl
 
     out = {
         "metric": "gcr_iterations_per_sec", "value": it_per_s * world, "unit": "it/s", "n_gpus": world,
@@ -722,12 +680,10 @@ def run_headline(args, with_cpu=True):
         "value_definition": "iterations/s of ONE solve on one GPU" if world == 1 else
                             "iterations/s of the ONE distributed solve (%.1f) x n_gpus: every iteration sweeps n_gpus shards of "
                             "%d^3 rows, the weak-scaling aggregate (shard-iterations per second)" % (it_per_s, n),
-        "timing": {"what": "wall seconds of one solve of exactly %d iterations (barrier + synchronise on both sides, max over ranks), "
-                           "repeated; value and ms_per_step come from the median" % args.steps,
-                   "seconds": st, "it_per_s_min": args.steps / st["max"] * world, "it_per_s_max": args.steps / st["min"] * world},
+        "timing": {"what": "wall seconds of one solve of exactly %d iterations (barrier + synchronise on both sides, max over ranks); "
+                           "value and ms_per_step come from it" % args.steps,
+                   "seconds": dt},
         "per_shard_it_per_s": it_per_s,
-        "scaling_baseline_it_per_s": None if scaling_baseline is None else scaling_baseline["it_per_s"],
-        "scaling_baseline": scaling_baseline,
         "one_launch_fallbacks": mg.stat("one_launch_fallbacks"),
         "config": {"workload": "3D 7-point Poisson %d^3 per GPU, unpreconditioned GCR restart %d, complex fp64, x0=0, "
                                "RHS splitmix64 seed 0" % (n, args.restart),
@@ -737,62 +693,147 @@ def run_headline(args, with_cpu=True):
                    "partition": "1 GPU" if world == 1 else "slab x%d (grid %dx%dx%d), %s" % (
                        world, world * n, n, n, ("host-staged transport%s (not a result)" % (", all ranks on GPU 0" if one_gpu else ""))
                        if host_transport else "RCCL communicator; halo: %s, all-reduce: %s" % (A.halo_kind, comm.allreduce_kind))},
-        "phases": {keys[k]: {"kernel": names[k], "us_per_iteration": ph_us[k], "bytes_per_launch": b_phase[k],
-                             "GBps": b_phase[k] / (ph_us[k] * 1e-6) / 1e9 if ph_us[k] > 0 else None} for k in range(3)},
-        "phases_timed": "in situ: hipEvents between the phases of each of the %d iterations of a GCR solve" % n_it.value,
-        "spmv": {"kernel": "stand-alone operator apply (inside the solver loop it runs fused with the beta dot products: phases.apply_dots)",
-                 "ms_cold_caches": cold_ms, "ms_cold_caches_stats": cold, "ms_back_to_back_replay": spmv_ms_replay,
-                 "includes_halo_exchange": world > 1,
-                 "bytes_moved_stored_layout": spmv_bytes,
-                 "GBps": None if not cold_ms else spmv_bytes / cold_ms / 1e6,
-                 "frac_hbm_peak": None if not cold_ms else spmv_bytes / cold_ms / 1e6 / HBM_PEAK_GBS,
-                 "GBps_back_to_back": spmv_bytes / spmv_ms_replay / 1e6,
-                 "copy_of_one_vector_same_conditions": None if not cold_copy else {
-                     "ms_cold_caches": cold_copy["median"], "bytes": 2 * V, "GBps": 2 * V / cold_copy["median"] / 1e6,
-                     "frac_hbm_peak": 2 * V / cold_copy["median"] / 1e6 / HBM_PEAK_GBS,
-                     "note": "a plain y = x between the same cache sweep and the same stream events: the ceiling a cold "
-                             "%d-row kernel has under this measurement" % N},
-                 "cold_caches_read_only_sweep": cold_read,
-                 "algorithmic_bytes_survey_formula": b_spmv_survey,
-                 "GBps_survey_formula": None if not cold_ms else b_spmv_survey / cold_ms / 1e6},
-        "iteration": {"bytes_moved_model": iter_bytes_ours, "GBps": iter_bytes_ours / (ms_per_step * 1e-3) / 1e9,
-                      "frac_hbm_peak": iter_bytes_ours / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                      "algorithmic_bytes_survey": iter_bytes_survey,
-                      "GBps_survey": iter_bytes_survey / (ms_per_step * 1e-3) / 1e9},
-        "roofline": {"kernel": names[dom], "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note, "bytes_per_launch": b_phase[dom],
-                     "us_per_launch": ph_us[dom],
-                     "note": "dominant phase of the iteration by time; achieved = bytes of the stored layout the phase's "
-                             "kernel has to move per launch (average over a restart cycle) / its hipEvent-timed duration"
-                             + ("" if world == 1 else "; N > 1: the phase times include the halo exchange (apply_dots) and both "
-                                                      "all-reduces of the iteration (build)")},
         "final_rel_residual": float(hist[-1]),
         "kernel_sources_sha16": source_sha16(),
     }
-    if world > 1:
-        # what the iteration's two all-reduces (4 doubles; 1 + 2 lim doubles) and its halo exchange cost on their own
-        us = ctypes.c_double()
-        comm_us = {}
-        for cnt in (4, 1 + 2 * args.restart):
-            mg.lib().mgcr_comm_bench_allreduce(comm.h, cnt, 50, ctypes.byref(us))
-            comm_us["allreduce_%d_doubles_us" % cnt] = us.value
-        out["comm"] = comm_us
-        out["comm"]["allreduce_kind"] = comm.allreduce_kind
-        out["comm"]["halo_kind"] = A.halo_kind
-        out["comm"]["ranks"] = comm.size
-        out["comm"]["transport"] = "host-staged" if host_transport else "RCCL"
-        out["comm"]["spmv_with_halo_exchange_ms_replay"] = spmv_ms_replay
-    if rank == 0 and world == 1 and with_cpu:
-        try:
-            out["cpu_baseline"] = cpu_baseline(n)
-        except Exception as e:  # the baseline leg must never take the GPU numbers down with it
-            out["cpu_baseline"] = {"value": None, "unit": "it/s", "cores": 1, "kind": "reference", "sample": "failed: %r" % (e,)}
-        try:
-            out["cpu_baseline_optimised"] = cpu_baseline_optimised(n, args.restart)
-        except Exception as e:
-            out["cpu_baseline_optimised"] = {"value": None, "unit": "it/s", "cores": None, "kind": "port", "sample": "failed: %r" % (e,)}
+    if args.full:
+        # everything the line carries besides the timed steps: the same solve repeated (median), per-phase in-situ timings,
+        # stand-alone SpMV figures, the roofline of the dominant phase, the N > 1 scaling baseline and collective costs, the
+        # CPU baselines.  The repetitions run until >= 0.25 s have been timed; their number must be the same on every rank:
+        # rank 0 decides from the timed solve
+        reps = int(min(400, max(5, 0.25 / max(dt, 1e-6))))
+        if dist is not None:
+            t = torch.tensor([reps], dtype=torch.int64)
+            dist.broadcast(t, src=0)
+            reps = int(t[0])
+        st = stats([dt] + [run(args.steps) for _ in range(reps - 1)])
+
+        # Per-phase timing IN SITU: one more solve of the same length with hipEvents (library stream) between
+        # the phases of every iteration — back-to-back replays of one kernel would be served from the
+        # 256 MiB Infinity Cache once its operands fit, which at this size they do.
+        run(args.steps, profile=True)
+        ph_ms = (ctypes.c_double * 3)()
+        n_it, fused = ctypes.c_int32(), ctypes.c_int32()
+        mg.lib().mgcr_gcr_last_profile(ph_ms, ctypes.byref(n_it), ctypes.byref(fused))
+        ph_us = [1e3 * v / max(n_it.value, 1) for v in ph_ms]           # average microseconds per iteration
+        y = Field(dims)
+        spmv_ms_replay = A.bench_apply(rhs, y, reps=args.spmv_reps)
+        cold, cold_copy = (None, None)
+        if world == 1:
+            cold, cold_copy = cold_apply_ms(mg, A, rhs, y, args.spmv_reps, Field)
+        cold_read = cold_apply_read_sweep(mg, A, rhs, y, args.spmv_reps, Field, stored["matrix_bytes"] + 16 * ncol + 16 * N) if world == 1 else None
+        V = 16 * N
+        R = args.restart
+        b_phase, mean_lim = gcr_phase_model(n_it.value, R, V, stored["matrix_bytes"], ncol, N, fused.value)
+        names = ["xr_update_kernel (alpha, residual ring, |r|^2)" if fused.value != 5 else "(no launch but the solve's last update: the residual update runs inside the apply kernel)",
+                 "step_apply_kernel (SpMV + beta dot products, one kernel)" if fused.value == 1 else
+                 "step_apply_xr*_kernel (residual update + SpMV + beta dot products, one kernel)" if fused.value == 5 else "SpMV + multidot_kernel",
+                 "build_lean_kernel<1..%d> / build_close_kernel<%d> (direction build + x update)" % (R - 1, R)]
+        if fused.value >= 2:
+            names[0] = "xr_update_kernel (alpha, residual ring, |r|^2)" + (
+                ": only the updates that open or end the solve%s — the others run at the end of step_build_kernel" % ("" if fused.value == 4 else " or follow a cycle's closing step") if fused.value >= 3 else "")
+            names[1] = ("step_build_kernel<1..%d> (SpMV + beta dot products + direction build%s in ONE launch, A r stays in LDS)%s"
+                        % (R if fused.value == 4 else R - 1, " + the next step's residual update" if fused.value >= 3 else "",
+                           "" if fused.value == 4 else "; the step that closes a cycle: step_apply_kernel<%d>" % R))
+            names[2] = ("(no launch: every step builds inside step_build_kernel; what is timed here are the event records of an empty slot)" if fused.value == 4 else
+                        "build_close_kernel<%d> (the step that closes a cycle; the other steps build inside step_build_kernel)" % R)
+        keys = ["xr", "apply_dots", "build"]
+        dom = max(range(3), key=lambda k: ph_us[k])
+        achieved = b_phase[dom] / (ph_us[dom] * 1e-6) / 1e9
+        lims_timed = [((k - 1) % R) + 1 for k in range(1, max(n_it.value, 1) + 1)]
+        traffic, traffic_note = pmc_traffic(keys[dom], n, lims_timed, R) if world == 1 else (None, "N > 1")
+        b_spmv_survey = spmv_algorithmic_bytes(nnz, N, ncol)
+        iter_bytes_survey = b_spmv_survey + (13 + 3 * mean_lim) * V   # SURVEY.md §8(d) accounting
+        iter_bytes_ours = sum(b_phase)                                # what this implementation moves
+        spmv_bytes = stored["matrix_bytes"] + 16 * ncol + 16 * N
+        cold_ms = cold["median"] if cold else None
+
+        # N > 1: what ONE GPU does on its own shard with the kernel path the distributed solve runs — the three kernels per
+        # iteration; the one-launch steps (gcr_stepbuild.hip) stop at the process boundary, their in-launch sums do not cross GPUs —
+        # so that per_shard_it_per_s / scaling_baseline_it_per_s is the price of the communication alone, and the N = 1 headline
+        # (one-launch steps) is not what an N-GPU line gets divided by.  Every rank measures its own shard; the slowest counts.
+        scaling_baseline = None
+        if world > 1:
+            Nl, ncl, rp, ci, va = problems.poisson3d_csr(n)
+            Aloc = Sparse(Nl, ncl, rp, ci, va)
+            del rp, ci, va
+            prev_sb, prev_res = mg.set_option("step_build", 0), mg.set_option("resident_solver", 0)
+            try:
+                gl = GCR(Aloc, GCR_Param(0, args.restart, args.steps, 0.0, False, check_every=args.steps))
+                xl, rl = Field(dims), Field(dims).fill_rhs(0)
+                timed_solve(mg, gl, rl, xl)
+                sb = stats(repeat_timed(lambda: timed_solve(mg, gl, rl, xl), min_total=0.15, min_reps=5))
+            finally:
+                mg.set_option("step_build", prev_sb)
+                mg.set_option("resident_solver", prev_res)
+            t = torch.tensor([sb["median"]], dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            scaling_baseline = {"it_per_s": args.steps / float(t[0]), "this_rank_seconds": sb,
+                                "what": "single-GPU solve of one %d^3 shard, same %d iterations, three kernels per iteration (step_build and the resident "
+                                        "solver off: the path a distributed shard runs); max over ranks" % (n, args.steps)}
+            del Aloc, gl, xl, rl
+
+        out.update({
+            "timing_repeated": {"what": "the timed solve repeated until >= 0.25 s have been timed (the first repetition is the timed solve itself)",
+                                "seconds": st, "it_per_s_median": args.steps / st["median"] * world,
+                                "it_per_s_min": args.steps / st["max"] * world, "it_per_s_max": args.steps / st["min"] * world},
+            "scaling_baseline_it_per_s": None if scaling_baseline is None else scaling_baseline["it_per_s"],
+            "scaling_baseline": scaling_baseline,
+            "phases": {keys[k]: {"kernel": names[k], "us_per_iteration": ph_us[k], "bytes_per_launch": b_phase[k],
+                                 "GBps": b_phase[k] / (ph_us[k] * 1e-6) / 1e9 if ph_us[k] > 0 else None} for k in range(3)},
+            "phases_timed": "in situ: hipEvents between the phases of each of the %d iterations of a GCR solve" % n_it.value,
+            "spmv": {"kernel": "stand-alone operator apply (inside the solver loop it runs fused with the beta dot products: phases.apply_dots)",
+                     "ms_cold_caches": cold_ms, "ms_cold_caches_stats": cold, "ms_back_to_back_replay": spmv_ms_replay,
+                     "includes_halo_exchange": world > 1,
+                     "bytes_moved_stored_layout": spmv_bytes,
+                     "GBps": None if not cold_ms else spmv_bytes / cold_ms / 1e6,
+                     "frac_hbm_peak": None if not cold_ms else spmv_bytes / cold_ms / 1e6 / HBM_PEAK_GBS,
+                     "GBps_back_to_back": spmv_bytes / spmv_ms_replay / 1e6,
+                     "copy_of_one_vector_same_conditions": None if not cold_copy else {
+                         "ms_cold_caches": cold_copy["median"], "bytes": 2 * V, "GBps": 2 * V / cold_copy["median"] / 1e6,
+                         "frac_hbm_peak": 2 * V / cold_copy["median"] / 1e6 / HBM_PEAK_GBS,
+                         "note": "a plain y = x between the same cache sweep and the same stream events: the ceiling a cold "
+                                 "%d-row kernel has under this measurement" % N},
+                     "cold_caches_read_only_sweep": cold_read,
+                     "algorithmic_bytes_survey_formula": b_spmv_survey,
+                     "GBps_survey_formula": None if not cold_ms else b_spmv_survey / cold_ms / 1e6},
+            "iteration": {"bytes_moved_model": iter_bytes_ours, "GBps": iter_bytes_ours / (ms_per_step * 1e-3) / 1e9,
+                          "frac_hbm_peak": iter_bytes_ours / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                          "algorithmic_bytes_survey": iter_bytes_survey,
+                          "GBps_survey": iter_bytes_survey / (ms_per_step * 1e-3) / 1e9},
+            "roofline": {"kernel": names[dom], "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note, "bytes_per_launch": b_phase[dom],
+                         "us_per_launch": ph_us[dom],
+                         "note": "dominant phase of the iteration by time; achieved = bytes of the stored layout the phase's "
+                                 "kernel has to move per launch (average over a restart cycle) / its hipEvent-timed duration"
+                                 + ("" if world == 1 else "; N > 1: the phase times include the halo exchange (apply_dots) and both "
+                                                          "all-reduces of the iteration (build)")},
+        })
+        if world > 1:
+            # what the iteration's two all-reduces (4 doubles; 1 + 2 lim doubles) and its halo exchange cost on their own
+            us = ctypes.c_double()
+            comm_us = {}
+            for cnt in (4, 1 + 2 * args.restart):
+                mg.lib().mgcr_comm_bench_allreduce(comm.h, cnt, 50, ctypes.byref(us))
+                comm_us["allreduce_%d_doubles_us" % cnt] = us.value
+            out["comm"] = comm_us
+            out["comm"]["allreduce_kind"] = comm.allreduce_kind
+            out["comm"]["halo_kind"] = A.halo_kind
+            out["comm"]["ranks"] = comm.size
+            out["comm"]["transport"] = "host-staged" if host_transport else "RCCL"
+            out["comm"]["spmv_with_halo_exchange_ms_replay"] = spmv_ms_replay
+        if rank == 0 and world == 1 and with_cpu:
+            try:
+                out["cpu_baseline"] = cpu_baseline(n)
+            except Exception as e:  # the baseline leg must never take the GPU numbers down with it
+                out["cpu_baseline"] = {"value": None, "unit": "it/s", "cores": 1, "kind": "reference", "sample": "failed: %r" % (e,)}
+            try:
+                out["cpu_baseline_optimised"] = cpu_baseline_optimised(n, args.restart)
+            except Exception as e:
+                out["cpu_baseline_optimised"] = {"value": None, "unit": "it/s", "cores": None, "kind": "port", "sample": "failed: %r" % (e,)}
+        del y
     # orderly teardown: solver state and operator first, then the communicator, then the process group
-    del gcr, x, rhs, y
+    del gcr, x, rhs
     del A
     if dist is not None:
         dist.barrier()
@@ -803,6 +844,26 @@ def run_headline(args, with_cpu=True):
         dist.destroy_process_group()
     mg.finalize()
     return out
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, x, hist):
+    """--dump-outputs DIR: what the timed solve returned to its caller — the solution x (complex, stored as float64 pairs
+    [re, im]) and the residual history |r_k| / |b| — as DIR/<name>.npy.  An x larger than the room the history leaves under
+    DUMP_LIMIT_BYTES is written as a fixed, seeded sample of its rows (x_sample.npy, rows in ascending order)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    hist = np.ascontiguousarray(hist, dtype=np.float64)
+    xr = np.ascontiguousarray(x).view(np.float64).reshape(-1, 2)
+    room = (DUMP_LIMIT_BYTES - hist.nbytes - 4096) // 16
+    name = "x"
+    if xr.shape[0] > room:
+        idx = np.sort(np.random.default_rng(0).choice(xr.shape[0], size=room, replace=False))
+        xr, name = xr[idx], "x_sample"
+    np.save(os.path.join(dirname, name + ".npy"), xr)
+    np.save(os.path.join(dirname, "residual_history.npy"), hist)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1504,10 +1565,18 @@ def parse_args(argv):
     ap.add_argument("--grid", dest="n", type=int, default=128, help="Poisson grid edge per GPU shard (128 = BASELINE configs[1])")
     ap.add_argument("--restart", type=int, default=5)
     ap.add_argument("--spmv-reps", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the other configs' workloads (N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: repeated solves, per-phase timings, SpMV and roofline figures, CPU baselines and the "
+                         "other configs' workloads")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other configs' workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed solve computed (x, residual history; N > 1: rank 0's shard of x) as DIR/<name>.npy")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), help="run ONE of the other workloads in this process and print its JSON")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main(argv=None):
@@ -1547,7 +1616,7 @@ def main(argv=None):
         os.environ["MGCR_RESIDENT"] = "0"
         out = run_headline(args, with_cpu=not args.no_cpu_baseline)
         out["fallback"] = "one-launch paths switched off after: %s" % (str(e)[:300],)
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         out["workloads"] = run_extras(argv)
     print(json.dumps(out), flush=True)
     return 0

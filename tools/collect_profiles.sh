@@ -7,7 +7,7 @@ tag=${1:-r03}
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-B="bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras"
+B="bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace -d $out/kt -o kt -- python3 $B > $out/kt.log 2>&1 && python tools/rocpd_stats.py $out/kt/kt_results.db > $out/${tag}_bench_kernel_stats.csv \
  && python tools/roofline_table.py $out/${tag}_bench_kernel_stats.csv > $out/${tag}_kernel_roofline_table.md && echo "kernel trace done" \
  && rocprofv3 --pmc FETCH_SIZE -d $out/pmc_fetch --output-format csv -- python3 $B > $out/pf.log 2>&1 && echo "fetch pass done" \
@@ -20,7 +20,7 @@ rocprofv3 --kernel-trace -d $out/kt -o kt -- python3 $B > $out/kt.log 2>&1 && py
  && rocprofv3 --kernel-trace -d $out/p512 -o p -- python3 bench.py --workload poisson512_gcr > $out/p512.log 2>&1 && python tools/rocpd_stats.py $out/p512/p_results.db > $out/${tag}_poisson512_kernel_stats.csv \
  && python tools/roofline_table.py $out/${tag}_poisson512_kernel_stats.csv 512 > $out/${tag}_poisson512_roofline_table.md && echo "poisson512 done" \
  && rocprofv3 --kernel-trace -d $out/ell -o e -- python3 bench.py --workload ell_slab_spmv128 > $out/ell.log 2>&1 && python tools/rocpd_stats.py $out/ell/e_results.db > $out/${tag}_ell_slab_kernel_stats.csv && echo "ell done" \
- && python bench.py --steps 20 --warmup 5 > $out/${tag}_bench.json 2> $out/bench.err && echo "bench done" \
+ && python bench.py --steps 20 --warmup 5 --full > $out/${tag}_bench.json 2> $out/bench.err && echo "bench done" \
  && rocprofv3 --kernel-trace -d $out/gen -o g -- python3 bench.py --workload poisson128_gcr_general > $out/gen.log 2>&1 && python tools/rocpd_stats.py $out/gen/g_results.db > $out/${tag}_poisson128_general_kernel_stats.csv && echo "general storage done" \
  && rocprofv3 --kernel-trace -d $out/bmg -o b -- python3 bench.py --workload bcsr_mg > $out/bmg.log 2>&1 && python tools/rocpd_stats.py $out/bmg/b_results.db > $out/${tag}_bcsr_mg_kernel_stats.csv && echo "bcsr_mg done" \
  && timeout -k 10 120 tools/build/barrier_lab > $out/${tag}_barrier_lab.txt 2>&1 && timeout -k 10 120 tools/build/coherent_lab > $out/${tag}_coherent_lab.txt 2>&1 && echo "labs done" \

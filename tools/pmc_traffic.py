@@ -3,9 +3,9 @@
 (MI355X_MICROARCH.md, HBM / rocprofv3 section: separate --pmc FETCH_SIZE and --pmc WRITE_SIZE runs;
 units KiB per dispatch; gfx950 correction: bytes read = 2 x FETCH_SIZE).
 
-    rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras
-    rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras
-    python tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write profiles/r02_pmc_hbm_traffic.csv profiles/pmc_traffic.json
+    rocprofv3 --pmc FETCH_SIZE -d OUT/pmc_fetch --output-format csv -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras
+    rocprofv3 --pmc WRITE_SIZE -d OUT/pmc_write --output-format csv -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras
+    python tools/pmc_traffic.py OUT/pmc_fetch OUT/pmc_write profiles/r02_pmc_hbm_traffic.csv profiles/pmc_traffic.json
 
 The JSON is stamped with the fingerprint of the kernel sources it was measured on (bench.source_sha16): bench.py prints
 roofline.traffic only while that fingerprint matches the sources it runs.
@@ -68,7 +68,7 @@ def main():
             phases[ph][0] += calls
             phases[ph][1] += b * calls
     with open(out_csv, "w") as f:
-        f.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes) -- python3 bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 5\n")
+        f.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes) -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 20 --warmup 5\n")
         f.write("# MI355X, Poisson %d^3.  Units: KiB per dispatch as reported; gfx950 correction (MI355X_MICROARCH.md HBM section): reads = 2 x FETCH_SIZE\n" % n)
         f.write("kernel,dispatches,FETCH_SIZE_KiB_avg,WRITE_SIZE_KiB_avg,hbm_bytes_per_launch_corrected\n")
         for name, calls, favg, wavg, b in rows:
