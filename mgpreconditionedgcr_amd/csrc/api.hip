@@ -193,6 +193,8 @@ int mgcr_set_option(const char *name, int value, int *previous) {
     else if (!strcmp(name, "graph_replay")) prev = set_graph_enabled(value != 0);
     else if (!strcmp(name, "resident_solver")) prev = set_resident_enabled(value != 0);
     else if (!strcmp(name, "step_build")) prev = set_stepbuild_enabled(value != 0);
+    else if (!strcmp(name, "start_build")) prev = set_start_build_enabled(value != 0);
+    else if (!strcmp(name, "step_build_keep_r")) prev = set_stepbuild_keepr_enabled(value != 0);
     else if (!strcmp(name, "halo_split")) prev = set_halo_split(value != 0);
     else if (!strcmp(name, "pw_tail")) prev = set_pw_tail_enabled(value != 0);
     else { set_error("mgcr_set_option: unknown option '%s'", name); return MGCR_ERR_INVALID; }
@@ -204,6 +206,7 @@ int mgcr_stat(const char *name, int64_t *value) {
     MGCR_CHECK(name && value, MGCR_ERR_INVALID, "mgcr_stat: null argument");
     if (!strcmp(name, "resident_solves")) *value = resident_solve_count();
     else if (!strcmp(name, "step_build_launches")) *value = stepbuild_launch_count();
+    else if (!strcmp(name, "start_build_launches")) *value = start_build_launch_count();
     else if (!strcmp(name, "small_solves")) *value = gcr_small_solve_count();
     else if (!strcmp(name, "one_launch_fallbacks")) *value = gcr_fallback_count();
     else if (!strcmp(name, "halo_split_exchanges")) *value = dist_halo_split_count();

@@ -161,6 +161,7 @@ __global__ void reset_kernel(DevState *st, const int *inherit, int inherit_it, d
     st->bnorm2 = 0.;
     st->rr = 0.;
     st->tol2 = tol2;
+    st->closed = 0;
 }
 
 
@@ -282,35 +283,39 @@ __global__ void __launch_bounds__(RED_THREADS) xr_update_kernel(DevState *__rest
 // applies the x updates still pending when the solve ends (never skipped).  The usual counts (a smoother's 2-3 sweeps, up to a
 // restart-5 cycle) get their loads issued together; same sums, same order.
 template <int NP>
-__device__ __forceinline__ void flush_x_rows(const cplx *__restrict__ alphas, const DirPtrs &d0, cplx *__restrict__ x, int64_t n, int assign) {
+__device__ __forceinline__ void flush_x_rows(const cplx *__restrict__ alphas, const cplx *p0, const DirPtrs &d0, cplx *__restrict__ x, int64_t n,
+                                             int assign) {
     cplx al[NP];
 #pragma unroll
     for (int j = 0; j < NP; j++) al[j] = to_sgpr(alphas[j]);
     GRID_STRIDE(i, n) {
         cplx pv[NP];
 #pragma unroll
-        for (int j = 0; j < NP; j++) pv[j] = d0.ps[j][i];
+        for (int j = 0; j < NP; j++) pv[j] = (j == 0 ? p0 : d0.ps[j])[i];
         cplx xv = assign ? make_double2(0., 0.) : x[i];   // assign: x0 = 0 was never materialised (gcr_run: assign_x)
 #pragma unroll
         for (int j = 0; j < NP; j++) xv = cadd(xv, cmul(al[j], pv[j]));
         x[i] = xv;
     }
 }
+// p0_first: where P0 lives until the solve's first cycle is closed (gcr_run_once start1: b itself), d0.ps[0] after that
 __global__ void __launch_bounds__(RED_THREADS) flush_x_kernel(DevState *__restrict__ st, const cplx *__restrict__ alphas, DirPtrs d0,
-                                                              cplx *__restrict__ x, int64_t n, int assign) {
+                                                              cplx *__restrict__ x, int64_t n, int assign, const cplx *p0_first) {
     const int np = st->npend;
     if (np <= 0) return;   // (also when an outer solver's stop predicate turned this whole solve into a no-op)
+    // (a pointer of its own: a kernel argument that is written to moves to scratch, and every d0.ps[j] with it)
+    const cplx *p0 = (p0_first && !st->closed) ? p0_first : d0.ps[0];
     switch (np) {
-        case 1: flush_x_rows<1>(alphas, d0, x, n, assign); return;
-        case 2: flush_x_rows<2>(alphas, d0, x, n, assign); return;
-        case 3: flush_x_rows<3>(alphas, d0, x, n, assign); return;
-        case 4: flush_x_rows<4>(alphas, d0, x, n, assign); return;
-        case 5: flush_x_rows<5>(alphas, d0, x, n, assign); return;
+        case 1: flush_x_rows<1>(alphas, p0, d0, x, n, assign); return;
+        case 2: flush_x_rows<2>(alphas, p0, d0, x, n, assign); return;
+        case 3: flush_x_rows<3>(alphas, p0, d0, x, n, assign); return;
+        case 4: flush_x_rows<4>(alphas, p0, d0, x, n, assign); return;
+        case 5: flush_x_rows<5>(alphas, p0, d0, x, n, assign); return;
         default: break;
     }
     GRID_STRIDE(i, n) {
         cplx xv = assign ? make_double2(0., 0.) : x[i];
-        for (int j = 0; j < np && j < LND; j++) xv = cadd(xv, cmul(alphas[j], d0.ps[j][i]));
+        for (int j = 0; j < np && j < LND; j++) xv = cadd(xv, cmul(alphas[j], (j == 0 ? p0 : d0.ps[j])[i]));
         x[i] = xv;
     }
 }
@@ -1227,9 +1232,22 @@ static int gcr_run_once(GcrState *s, const cplx *rhs, cplx *x, bool nested, doub
     // per solve; same sums in the same order as the separate kernels (test_fused_apply_and_dots_same_bits).  Worth
     // ~45 us per solve, i.e. 2-3 % of a 20-iteration solve at 128^3.
     const bool fuse_start = fuse_ok && !alias_p0 && !flex && !p.use_x0 && !p.left_precond && !p.right_precond && fuse_init_enabled();
+    // ... and where the steps are one launch each (gcr_stepbuild.hip), that start is ONE launch too (start_build_kernel): Ap0 = A b, the
+    // sums, |b|^2 / hist[0], alpha and step 1's residual update r1 = b - alpha Ap0.  r and P0 are not copied: cycle 1 reads b where it
+    // read them, the closing step reads P0 from b and writes P0' to its slot, flush_x_kernel picks P0 by DevState::closed.  Every
+    // closing step of the solve has to be a one-launch step then (that sets `closed`): restart <= 5 directions, all of them stored.
+    bool start1 = false;
+    if (fuse_start && lean && s->restart > 1 && s->restart <= 5 && s->storage >= s->restart && rmap.band == 0 && !graphs_enabled() &&
+        stepbuild_close_enabled() && !(nested && p.max_iter <= 1 && (s->defer_residual || s->discard_residual))) {
+        const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
+        start1 = !csr_xr_fusable(b0->csr, b0->dist) && csr_start_build_eligible(b0->csr, b0->dist) &&
+                 csr_step_build_eligible(b0->csr, b0->dist, s->restart);
+    }
     // r = rhs (src/GCR.h:189); the reference ignores x0 here unless use_x0 is requested
     if (p.use_x0) {
         MGCR_TRY(op_residual_raw(s->A, x, rhs, s->r, n));
+    } else if (start1) {
+        // (r0 = P0 = rhs, read in place)
     } else if (fuse_start) {
         hipLaunchKernelGGL(copy2_kernel, dim3(g), dim3(RED_THREADS), 0, c.stream, s->r, s->ps[0], rhs, n, (const DevState *)s->st);
         MGCR_HIP(hipGetLastError());
@@ -1263,7 +1281,15 @@ static int gcr_run_once(GcrState *s, const cplx *rhs, cplx *x, bool nested, doub
                "on a distributed operator only flexible right preconditioning is available (set flexible = 1)");
     const DevState *cst = s->st;
     const double *normN = s->partsN;
-    if (fuse_start) {
+    bool xr_prefetched = false;   // the next iteration's residual update already ran at the end of this one's launch
+    if (start1) {
+        const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
+        const int nxt1 = 1 % s->storage;   // where step 1 leaves its residual (one_iteration: dslot)
+        MGCR_TRY(ensure_slot(s, nxt1));
+        MGCR_TRY(csr_start_build(b0->csr, rhs, s->A->kind == OP_DIRAC, s->A->k, s->aps[0], s->st, s->hist, s->lc, s->den,
+                                 nxt1 >= 1 ? s->ps[nxt1] : s->r, s->partsR, rmap));
+        xr_prefetched = true;
+    } else if (fuse_start) {
         const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
         MGCR_TRY(csr_init_apply(b0->csr, rhs, s->aps[0], s->A->kind == OP_DIRAC, s->A->k, (const cplx *)nullptr, s->partsA, s->partsR,
                                 s->partsN, b0->dist, rmap));
@@ -1294,7 +1320,7 @@ static int gcr_run_once(GcrState *s, const cplx *rhs, cplx *x, bool nested, doub
         KLAUNCH(init_kernel, 1, s->st, (const double *)s->dN, 1, 1, (const double *)(s->dN + 1), 1, 1, s->hist);
         refA = {s->dA, 1, 1};
         refR = {s->dRB, 1, 1};
-    } else {
+    } else if (!start1) {
         KLAUNCH(init_kernel, 1, s->st, normN, g, RED_MAX_BLOCKS, (const double *)s->partsR, g, RED_MAX_BLOCKS, s->hist);
     }
 
@@ -1305,12 +1331,12 @@ static int gcr_run_once(GcrState *s, const cplx *rhs, cplx *x, bool nested, doub
     s->r_after.clear();
     if (!p.left_precond && (!p.right_precond || flex) && max_it <= LND) s->r_after.assign((size_t)max_it + 1, nullptr);
     int check_every = p.check_every > 0 ? p.check_every : 10;
-    const cplx *rcur = alias0 ? rhs : s->r;  // lean: where the current residual lives (s->r at the start of every cycle)
+    const cplx *rcur = (alias0 || start1) ? rhs : s->r;  // lean: where the current residual lives (s->r at the start of every cycle)
+    const cplx *p0_live = start1 ? rhs : (const cplx *)s->ps[0];   // where the closing step reads P0 (start1: b until cycle 1 closes)
     int iter_count = 0, cur = 0, global = 0;
     bool done = false;
     std::vector<hipEvent_t> prof_events;
     bool prof_step_build = false, prof_step_build_xr = false, prof_step_build_close = false;
-    bool xr_prefetched = false;   // the next iteration's residual update already ran at the end of this one's launch
     // one iteration, enqueued on the library stream; `it` = iteration number relative to DevState::base
     auto one_iteration = [&](int it, bool last = false) -> int {
         iter_count++;
@@ -1431,13 +1457,14 @@ static int gcr_run_once(GcrState *s, const cplx *rhs, cplx *x, bool nested, doub
                 xr_out = nxt2 >= 1 ? s->ps[nxt2] : s->r;
             }
             const cplx *cps[FND];
-            for (int j = 0; j < FND; j++) cps[j] = s->ps[j < lim ? j : 0];
+            for (int j = 0; j < FND; j++) cps[j] = j < lim && j > 0 ? s->ps[j] : p0_live;
             MGCR_TRY(csr_step_build(b0->csr, dir, s->A->kind == OP_DIRAC, s->A->k, vecs, lim, s->st, it, refR.p, refR.nblk, refR.stride, s->hist,
                                     s->hist_cap, s->den, s->aps[nxt], s->partsA, s->lc, rmap, xr_out, s->den + nxt, nxt, s->partsR,
                                     closes ? cps : nullptr, closes ? s->ps[0] : nullptr, closes ? x : nullptr));
             xr_prefetched = xr_out != nullptr;
             prof_step_build_xr = prof_step_build_xr || xr_prefetched;
             prof_step_build_close = prof_step_build_close || closes;
+            if (closes) p0_live = s->ps[0];
             MGCR_TRY(mark());
             MGCR_TRY(mark());
             iter_count = ic_next;
@@ -1491,6 +1518,8 @@ static int gcr_run_once(GcrState *s, const cplx *rhs, cplx *x, bool nested, doub
             if (!tail_rb) MGCR_TRY(comm_fold_allreduce(comm, s->partsR, 1, s->partsB, 2 * lim, s->dRB, g));
             refB = {s->dRB + 1, 1, 1};
         }
+        // (start1 makes every closing step a one-launch step: P0 is read from b only there)
+        MGCR_CHECK(!(start1 && ic_next == 0 && p0_live != s->ps[0]), MGCR_ERR_INVALID, "gcr: a cycle closed off the one-launch path after a one-launch start");
         if (lean) {
             LeanArgs a;
             a.g = g; a.nd = lim; a.rdir = flex; a.st = s->st; a.it = it; a.B = refB; a.R = refR; a.hist = s->hist;
@@ -1602,7 +1631,8 @@ static int gcr_run_once(GcrState *s, const cplx *rhs, cplx *x, bool nested, doub
             s->has_pending = true;
         } else {
         // (npend is not cleared afterwards: nothing reads it again before the next solve's reset_kernel zeroes it)
-        KLAUNCH(flush_x_kernel, g, s->st, lean ? (const cplx *)s->lc->cx : (const cplx *)s->alphas, d0, x, n, assign_x ? 1 : 0);
+        KLAUNCH(flush_x_kernel, g, s->st, lean ? (const cplx *)s->lc->cx : (const cplx *)s->alphas, d0, x, n, assign_x ? 1 : 0,
+                start1 ? rhs : (const cplx *)nullptr);
         }
     }
     if (nested) return MGCR_OK;
@@ -1673,7 +1703,8 @@ void gcr_set_keep_pending(GcrState *s, bool on) { s->keep_pending = on; }
 int gcr_flush_pending(const PendingX &pd, cplx *x, int64_t n) {
     DirPtrs d0;
     for (int j = 0; j < LND; j++) { d0.ps[j] = pd.v[j]; d0.aps[j] = pd.v[j]; d0.slot[j] = j; }
-    hipLaunchKernelGGL(flush_x_kernel, dim3(red_grid(n)), dim3(RED_THREADS), 0, ctx().stream, const_cast<DevState *>(pd.st), pd.coef, d0, x, n, 1);
+    hipLaunchKernelGGL(flush_x_kernel, dim3(red_grid(n)), dim3(RED_THREADS), 0, ctx().stream, const_cast<DevState *>(pd.st), pd.coef, d0, x, n, 1,
+                       (const cplx *)nullptr);
     MGCR_HIP(hipGetLastError());
     return MGCR_OK;
 }

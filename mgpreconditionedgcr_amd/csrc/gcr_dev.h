@@ -29,6 +29,8 @@ struct DevState {
     double bnorm2; // |b|^2
     double rr;     // |r|^2 of the last finished step
     double tol2;
+    int closed;    // a restart cycle of this solve has been closed (set by gcr_stepbuild.hip's closing step, cleared by reset_kernel):
+                   // until then P0 may still be read from b itself (gcr.hip start1)
 };
 
 // Where a finished solve left its recurrence residual, by the number of steps it actually ran (a solve that
@@ -202,6 +204,10 @@ int gcr_resident_run(Op *A, const mgcr_gcr_param &p, int storage, int restart, c
 
 // gcr_stepbuild.hip: apply + dot products + direction build of a lean step in one launch
 bool csr_step_build_eligible(const CsrDev &A, const DistCsr *dist, int lim);
+// the start of a solve from x0 = 0 (Ap0 = A b, |b|^2, hist[0], alpha, r1 = b - alpha Ap0) as one launch
+bool csr_start_build_eligible(const CsrDev &A, const DistCsr *dist);
+int csr_start_build(const CsrDev &A, const cplx *b, bool shift, cplx k, cplx *ap0, DevState *st, double *hist, LeanCoef *lc, cplx *den0,
+                    cplx *r_out, double *partsR_out, const RowMap &rm);
 int csr_step_build(const CsrDev &A, const cplx *x, bool shift, cplx k, const cplx *const *aps, int nd, DevState *st, int it, const double *partsR,
                    int nblkR, int strideR, double *hist, int hist_cap, const cplx *den, cplx *ap_out, double *partsA, LeanCoef *lc,
                    const RowMap &rm, cplx *xr_out = nullptr, cplx *xr_den_slot = nullptr, int xr_slot = 0, double *partsR_out = nullptr,

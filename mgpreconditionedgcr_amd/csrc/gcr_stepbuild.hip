@@ -81,8 +81,11 @@ __device__ __forceinline__ void sb_close_step(DevState *st, int it, double rr, d
 
 // REALC: the instantiation for real stencil coefficients (no per-slot real / complex decision, 14 scalar registers less — the
 // kernels' scalar registers spill into vector-register lanes, which a wave then reads back one v_readlane at a time)
-template <int MODE, int WT, int NDT, bool XR, bool CLOSE, bool REALC = false>
+// KEEPR (in-cycle steps with XR): the thread's residual rows, read once by the build, stay in registers (SB_MAX_TRIPS x 16 B)
+// until the update after the second exchange: one read of r per step less, and nothing but LDS left to wait for after that poll
+template <int MODE, int WT, int NDT, bool XR, bool CLOSE, bool REALC = false, bool KEEPR = false>
 __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArgs a) {
+    static_assert(!KEEPR || (XR && !CLOSE), "KEEPR: the in-cycle step that ends with the next residual update");
     __shared__ double lds[(2 * NDT > 4 ? 2 * NDT : 4) * 17];
     __shared__ double lds_pw[2 * SB_MAX_ND * 17], lds_ws[2 * SB_MAX_ND * RES_GRP];
     __shared__ int gave_up;
@@ -163,7 +166,10 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
     if (XR || lb == 0) {
         double rr[1];
         fold_partials<1>(a.partsR, a.nblkR, a.strideR, rr, lds);
-        if (lb == 0 && threadIdx.x == 0) sb_close_step(a.st, a.it, rr[0], a.hist, a.hist_cap, CLOSE);
+        if (lb == 0 && threadIdx.x == 0) {
+            sb_close_step(a.st, a.it, rr[0], a.hist, a.hist_cap, CLOSE);
+            if (CLOSE) a.st->closed = 1;   // (P0' is written below, by every workgroup that reaches the close pass)
+        }
         ends_here = !((rr[0] / a.st->bnorm2) > a.st->tol2);
     }
     if ((int)threadIdx.x < NDT) sbeta[threadIdx.x] = cdiv(make_double2(res_total(sy, 2 * threadIdx.x), res_total(sy, 2 * threadIdx.x + 1)), a.den[threadIdx.x]);
@@ -227,7 +233,8 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    for (int64_t i = i0; i < end; i += stride, trip++) {
+    cplx rk[KEEPR ? SB_MAX_TRIPS : 1];   // KEEPR: r of the thread's rows, for the update after the second exchange
+    auto build_row = [&](int64_t i, int trip) -> cplx {
         cplx aj[NDT];
 #pragma unroll
         for (int j = 0; j < NDT; j++) aj[j] = (PRE && !CLOSE && i == i0) ? pre[j] : ld_stream<NTS>(a.aps[j] + i);
@@ -242,6 +249,17 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
         v[0] += t.x; v[1] += t.y;
         cplx u = cconj_mul(an, an);
         v[2] += u.x; v[3] += u.y;
+        return rv;
+    };
+    if constexpr (KEEPR) {   // the same rows in the same order, with trip numbers known at compile time (register indices)
+#pragma unroll
+        for (int t = 0; t < SB_MAX_TRIPS; t++) {
+            const int64_t i = i0 + (int64_t)t * stride;
+            if (i < end) rk[t] = build_row(i, t);
+            __builtin_amdgcn_sched_barrier(0);   // (one trip's streams in registers at a time, as in the loop below)
+        }
+    } else {
+        for (int64_t i = i0; i < end; i += stride, trip++) (void)build_row(i, trip);
     }
     const double mine = block_sum_owner<4>(v, lds);
     if (threadIdx.x < 4) a.partsA[threadIdx.x * RED_MAX_BLOCKS + lb] = mine;
@@ -252,7 +270,7 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
             const v4i w4 = {__double2loint(mine), __double2hiint(mine), (int)sy.gen, 0};
             __builtin_amdgcn_raw_buffer_store_b128(w4, sy.slots, ((2 * RES_NV + (int)threadIdx.x) * RES_BLK + lb) * 16, 0, RES_SC1);
         }
-        const cplx xr0 = i0 < end ? a.x[i0] : make_double2(0., 0.);   // (requested before the polls, like `pre` above)
+        const cplx xr0 = (!KEEPR && i0 < end) ? a.x[i0] : make_double2(0., 0.);   // (requested before the polls, like `pre` above)
         if (!res_collect<4>(sy, 2)) {
             if (threadIdx.x == 0) {
                 __hip_atomic_store(a.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -271,15 +289,145 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
         }
         if (lb == 0 && (int)threadIdx.x < LND) lean_pending_update(a.lc, a.xr_slot, alpha, (int)threadIdx.x);
         double vr[1] = {0.};
-        trip = 0;
-        for (int64_t i = i0; i < end; i += stride, trip++) {
-            const cplx rn = csub(i == i0 ? xr0 : a.x[i], cmul(alpha, arL[trip * RED_THREADS + (int)threadIdx.x]));
-            a.xr_out[i] = rn;
-            vr[0] += rn.x * rn.x + rn.y * rn.y;
+        if constexpr (KEEPR) {
+#pragma unroll
+            for (int t = 0; t < SB_MAX_TRIPS; t++) {
+                const int64_t i = i0 + (int64_t)t * stride;
+                if (i < end) {
+                    const cplx rn = csub(rk[t], cmul(alpha, arL[t * RED_THREADS + (int)threadIdx.x]));
+                    a.xr_out[i] = rn;
+                    vr[0] += rn.x * rn.x + rn.y * rn.y;
+                }
+            }
+        } else {
+            trip = 0;
+            for (int64_t i = i0; i < end; i += stride, trip++) {
+                const cplx rn = csub(i == i0 ? xr0 : a.x[i], cmul(alpha, arL[trip * RED_THREADS + (int)threadIdx.x]));
+                a.xr_out[i] = rn;
+                vr[0] += rn.x * rn.x + rn.y * rn.y;
+            }
         }
         const double tot = block_sum_owner<1>(vr, lds);
         if (threadIdx.x == 0) a.partsR_out[lb] = tot;
     }
+}
+
+// The start of a solve from x0 = 0 as ONE launch (r0 = P0 = b, no preconditioner): what gcr.hip ran as copy2_kernel (r = P0 = b),
+// gcr_fused.hip init_apply_kernel (Ap0 = A b and the partials of <b,Ap0>, <Ap0,Ap0>, |b|^2), init_kernel (|b|^2, hist[0]) and
+// step 1's xr_update_kernel<true, true> (alpha, r1 = b - alpha Ap0 into the residual ring, its |r1|^2 partials):
+//   apply + sums | exchange | bookkeeping (logical workgroup 0) | alpha, r1.
+// Ap0 stays in LDS for the update (and is written once, as aps[0]); b is read again by the update, its first row requested before
+// the poll (kept in registers instead, the kernel needs scratch); r and P0 are never copied — cycle 1 reads b where it read them.  The same rows per thread (RowMap), the same per-thread accumulation order,
+// the same fold tree as those kernels: the same bits.  |b|^2 and |r0|^2 are one sum here, as they were two folds of the same
+// partials there.  Needs what step_build_kernel needs (co-residency, bounded polls, give-up with NaN results).
+struct StartArgs {
+    RowMat m;
+    const cplx *b;
+    cplx *ap0;
+    int64_t n;
+    int nlogical;
+    RowMap rm;
+    DevState *st;
+    double *hist;
+    LeanCoef *lc;
+    cplx *den0;
+    cplx *r_out;             // r1 (the ring slot of step 1)
+    double *partsR_out;
+    v4i *slots;
+    unsigned gen0;
+    unsigned *abort_dev;
+    int *abort_host;
+    int spin_limit;
+    int test_stall;
+};
+
+template <bool REALC>
+__global__ void __launch_bounds__(RED_THREADS, 8) start_build_kernel(StartArgs a) {
+    __shared__ double lds[6 * 17];
+    __shared__ double lds_pw[2 * SB_MAX_ND * 17], lds_ws[2 * SB_MAX_ND * RES_GRP];
+    __shared__ int gave_up;
+    extern __shared__ __attribute__((aligned(16))) unsigned char sb_smem[];   // Ap0 of this workgroup's rows: [trip][thread]
+    if (a.st->stop_at < 0) return;   // (an outer solve that is over: reset_kernel)
+    const int lb = logical_workgroup(a.rm, (int)blockIdx.x, (int)gridDim.x);
+    if (lb >= a.nlogical) return;
+    cplx *apL = reinterpret_cast<cplx *>(sb_smem);
+    ResSync sy;
+    sy.slots = res_rsrc(a.slots, (unsigned)RES_SLOT_BYTES);
+    sy.gen = a.gen0;
+    sy.nblk = a.nlogical;
+    sy.lb = lb;
+    sy.abort_dev = a.abort_dev;
+    sy.spin_limit = a.spin_limit;
+    sy.pw = lds_pw;
+    sy.ws = lds_ws;
+    sy.gave_up = &gave_up;
+    if (threadIdx.x == 0) gave_up = 0;
+    if (a.test_stall && lb == a.test_stall - 1) return;
+    int64_t i0, end, stride;
+    row_range(a.rm, lb, a.nlogical, a.n, &i0, &end, &stride);
+    // ---- Ap0 = A b and the sums (init_apply_kernel: v[4] = |r0|^2, v[5] = |b|^2 stays 0 as there, b IS r0) ----
+    {
+        double v[6] = {0., 0., 0., 0., 0., 0.};
+#pragma unroll
+        for (int t = 0; t < SB_MAX_TRIPS; t++) {
+            const int64_t i = i0 + (int64_t)t * stride;
+            if (i < end) {
+                const PatLds pl{nullptr, nullptr, nullptr};
+                cplx sum;
+                if constexpr (REALC) sum = sten_row_product_t<7, false, 1>(a.m, i, [&](int32_t j) -> cplx { return a.b[j]; });
+                else sum = fused_row_product<3, 7>(a.m, i, 0, pl, [&](int32_t j) -> cplx { return a.b[j]; });
+                const cplx rv = a.b[i];
+                const cplx yi = a.m.shift ? csub(rv, cmul(a.m.k, sum)) : sum;
+                a.ap0[i] = yi;
+                apL[t * RED_THREADS + (int)threadIdx.x] = yi;
+                v[4] += rv.x * rv.x + rv.y * rv.y;
+                const cplx tt = cconj_mul(rv, yi);
+                v[0] += tt.x; v[1] += tt.y;
+                const cplx u = cconj_mul(yi, yi);
+                v[2] += u.x; v[3] += u.y;
+            }
+            __builtin_amdgcn_sched_barrier(0);   // (one trip's gathers in registers at a time)
+        }
+        const double mine = block_sum_owner<6>(v, lds);
+        if ((int)threadIdx.x < 5) {
+            const v4i w4 = {__double2loint(mine), __double2hiint(mine), (int)sy.gen, 0};
+            __builtin_amdgcn_raw_buffer_store_b128(w4, sy.slots, ((1 * RES_NV + (int)threadIdx.x) * RES_BLK + lb) * 16, 0, RES_SC1);
+        }
+    }
+    const cplx b0 = i0 < end ? a.b[i0] : make_double2(0., 0.);   // (requested before the polls)
+    if (!res_collect<5>(sy, 1)) {
+        if (threadIdx.x == 0) {
+            __hip_atomic_store(a.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.abort_host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        for (int64_t i = i0; i < end; i += stride) a.r_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
+        if (threadIdx.x == 0) a.partsR_out[lb] = __builtin_nan("");
+        return;
+    }
+    // ---- init_kernel's bookkeeping, then xr_update_kernel<true, true> of step 1 (slot 0) ----
+    const cplx num = make_double2(res_total(sy, 0), res_total(sy, 1)), den = make_double2(res_total(sy, 2), res_total(sy, 3));
+    const cplx alpha = to_sgpr(cdiv(num, den));
+    if (lb == 0 && threadIdx.x == 0) {
+        const double nb = res_total(sy, 4);
+        a.st->bnorm2 = nb;
+        a.st->rr = nb;
+        a.hist[0] = sqrt(nb) / sqrt(nb);
+        *a.den0 = den;
+        a.st->npend = 1;
+    }
+    if (lb == 0 && (int)threadIdx.x < LND) lean_pending_update(a.lc, 0, alpha, (int)threadIdx.x);
+    double vr[1] = {0.};
+#pragma unroll
+    for (int t = 0; t < SB_MAX_TRIPS; t++) {
+        const int64_t i = i0 + (int64_t)t * stride;
+        if (i < end) {
+            const cplx rn = csub(t == 0 ? b0 : a.b[i], cmul(alpha, apL[t * RED_THREADS + (int)threadIdx.x]));
+            a.r_out[i] = rn;
+            vr[0] += rn.x * rn.x + rn.y * rn.y;
+        }
+    }
+    const double tot = block_sum_owner<1>(vr, lds);
+    if (threadIdx.x == 0) a.partsR_out[lb] = tot;
 }
 
 static int g_stepbuild = -1;
@@ -301,9 +449,25 @@ static bool sb_real_enabled() {
     static const bool on = !(getenv("MGCR_SB_REAL") && atoi(getenv("MGCR_SB_REAL")) == 0);
     return on;
 }
+// (KEEPR only where the instantiation keeps 0 scratch and 8 waves per SIMD — up to 2 stored directions; with 3..5 the kept rows
+// spill: tests/test_stepbuild_regs.py)
+template <int NDT> constexpr bool sb_keepr_fits() { return NDT <= 2; }
+static int g_sb_keepr = -1;
+static bool sb_keepr_enabled() {
+    if (g_sb_keepr < 0) g_sb_keepr = !(getenv("MGCR_SB_KEEPR") && atoi(getenv("MGCR_SB_KEEPR")) == 0);
+    return g_sb_keepr != 0;
+}
+bool set_stepbuild_keepr_enabled(bool on) {
+    const bool prev = sb_keepr_enabled();
+    g_sb_keepr = on ? 1 : 0;
+    return prev;
+}
 static const void *sb_kernel(int nd, bool xr, bool close, bool realc) {
+    const bool keepr = xr && !close && sb_keepr_enabled();
+#define SBX(NDT, R) ((keepr && sb_keepr_fits<NDT>()) ? (const void *)step_build_kernel<3, 7, NDT, true, false, R, sb_keepr_fits<NDT>()> \
+                                                     : (const void *)step_build_kernel<3, 7, NDT, true, false, R>)
 #define SBR(NDT, R) (close ? (xr ? (const void *)step_build_kernel<3, 7, NDT, true, true, R> : (const void *)step_build_kernel<3, 7, NDT, false, true, R>) \
-                           : (xr ? (const void *)step_build_kernel<3, 7, NDT, true, false, R> : (const void *)step_build_kernel<3, 7, NDT, false, false, R>))
+                           : (xr ? SBX(NDT, R) : (const void *)step_build_kernel<3, 7, NDT, false, false, R>))
 #define SBK(NDT) (realc ? SBR(NDT, true) : SBR(NDT, false))
     switch (nd) {
         case 1: return SBK(1);
@@ -314,6 +478,7 @@ static const void *sb_kernel(int nd, bool xr, bool close, bool realc) {
     }
 #undef SBK
 #undef SBR
+#undef SBX
 }
 // Do `grid` workgroups of this instantiation, with this much dynamic LDS, fit the chip AT ONCE?  The workgroups wait for each
 // other inside the launch, so the answer has to come from the runtime (registers and LDS of the code object that was actually
@@ -393,6 +558,56 @@ int csr_step_build(const CsrDev &A, const cplx *x, bool shift, cplx k, const cpl
     MGCR_HIP(hipLaunchKernel(kernel, dim3(grid), dim3(RED_THREADS), kargs, lds_bytes, ctx().stream));
     MGCR_HIP(hipGetLastError());
     g_stepbuild_launches++;
+    return MGCR_OK;
+}
+
+static int g_start_build = -1;
+static bool start_build_enabled() {
+    if (g_start_build < 0) g_start_build = !(getenv("MGCR_START_BUILD") && atoi(getenv("MGCR_START_BUILD")) == 0);
+    return g_start_build != 0;
+}
+bool set_start_build_enabled(bool on) {
+    const bool prev = start_build_enabled();
+    g_start_build = on ? 1 : 0;
+    return prev;
+}
+static int64_t g_start_build_launches = 0;
+int64_t start_build_launch_count() { return g_start_build_launches; }
+static const void *start_kernel(bool realc) {
+    return realc ? (const void *)start_build_kernel<true> : (const void *)start_build_kernel<false>;
+}
+
+// can the start of a solve on A run as one launch?  (the conditions of a one-launch step, and its own kernel co-resident)
+bool csr_start_build_eligible(const CsrDev &A, const DistCsr *dist) {
+    if (!start_build_enabled() || !csr_step_build_eligible(A, dist, 1)) return false;
+    const bool realc = sb_real_enabled() && row_mat(A, false, cplx{0., 0.}).realv;
+    return launch_is_coresident(start_kernel(realc), RED_THREADS, sb_lds_bytes(A, red_grid(A.nrow)), red_grid(A.nrow));
+}
+
+int csr_start_build(const CsrDev &A, const cplx *b, bool shift, cplx k, cplx *ap0, DevState *st, double *hist, LeanCoef *lc, cplx *den0,
+                    cplx *r_out, double *partsR_out, const RowMap &rm) {
+    MGCR_TRY(exchange_shared_init());
+    ExchangeShared &sh = exchange_shared();
+    StartArgs a;
+    a.m = row_mat(A, shift, k);
+    a.b = b;
+    a.ap0 = ap0;
+    a.n = A.nrow;
+    const int g = red_grid(A.nrow);
+    a.nlogical = g;
+    a.rm = rm;
+    a.st = st; a.hist = hist; a.lc = lc; a.den0 = den0; a.r_out = r_out; a.partsR_out = partsR_out;
+    a.slots = sh.slots; a.abort_dev = sh.abort_dev; a.abort_host = sh.abort_host;
+    a.gen0 = exchange_take_generations(1);
+    a.test_stall = getenv("MGCR_TEST_STEPBUILD_STALL") ? atoi(getenv("MGCR_TEST_STEPBUILD_STALL")) : 0;
+    a.spin_limit = getenv("MGCR_TEST_RESIDENT_SPIN_LIMIT") ? atoi(getenv("MGCR_TEST_RESIDENT_SPIN_LIMIT")) : RES_SPIN_LIMIT;
+    const size_t lds_bytes = sb_lds_bytes(A, g);
+    const void *kernel = start_kernel(sb_real_enabled() && a.m.realv);
+    MGCR_CHECK(launch_is_coresident(kernel, RED_THREADS, lds_bytes, g), MGCR_ERR_INVALID, "csr_start_build: launch would not be co-resident");
+    void *kargs[1] = {(void *)&a};
+    MGCR_HIP(hipLaunchKernel(kernel, dim3((unsigned)g), dim3(RED_THREADS), kargs, lds_bytes, ctx().stream));
+    MGCR_HIP(hipGetLastError());
+    g_start_build_launches++;
     return MGCR_OK;
 }
 

@@ -197,6 +197,9 @@ void resident_shutdown();
 int64_t resident_solve_count();
 bool set_stepbuild_enabled(bool on);   // gcr_stepbuild.hip: apply + dots + build of a lean step as one launch
 int64_t stepbuild_launch_count();
+bool set_start_build_enabled(bool on);         // ... and the start of a solve as one launch
+int64_t start_build_launch_count();
+bool set_stepbuild_keepr_enabled(bool on);     // ... an in-cycle step keeps r in registers for the next update
 int coherence_selftest(int steps, int coherent, int64_t *rows_wrong);   // gcr_resident.hip
 bool stepbuild_is_enabled();
 bool launch_is_coresident(const void *kernel, int threads, size_t dyn_lds, int grid);   // gcr_stepbuild.hip: asks the runtime
