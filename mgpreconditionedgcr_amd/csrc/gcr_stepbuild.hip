@@ -23,6 +23,7 @@
 // on the device turns the whole launch, or its update part, into a no-op like any other kernel of the solve.
 #include <climits>
 #include <cstdlib>
+#include <type_traits>
 
 #include "internal.h"
 #include "reduce.h"
@@ -34,6 +35,7 @@ namespace mgcr {
 
 constexpr int SB_MAX_TRIPS = 4;     // rows per thread whose Ar stays in LDS (4 x 1024 x 16 B = 64 KB per workgroup)
 constexpr int SB_MAX_ND = 5;
+constexpr int SB_KEEP_TB = 2;      // step_keep_kernel: trips whose streams are in registers at a time
 
 struct StepBuildArgs {
     RowMat m;
@@ -312,6 +314,289 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
     }
 }
 
+// p + off bytes, with p a wave-uniform (scalar) address and off a 32-bit byte offset: the load or store takes the saddr form
+template <class T>
+__device__ __forceinline__ T *sb_elem(T *p, uint32_t off) {
+    using C = std::conditional_t<std::is_const_v<T>, const char, char>;
+    return reinterpret_cast<T *>(reinterpret_cast<C *>(p) + off);
+}
+
+// block_sum_owner<NV> (reduce.h) in two halves, for per-thread sums that become final a pair at a time: each pair goes through
+// the wave trees as soon as it is final — wave_multi_sum sums every scalar by the same tree whatever NV is (same operands,
+// same order: reduce.h), so lds[k * 17 + wave] holds the bits block_sum_owner<NV> puts there — and the waves' sums are
+// added in wave order once all pairs are in.  `lds` must not be reused before another barrier.
+__device__ __forceinline__ void sb_wave_pair_to_lds(double (&v)[2], double *lds, int k0) {
+    double s;
+    const int k = wave_multi_sum<2>(v, s);
+    if (((int)threadIdx.x & 31) == 0) lds[(k0 + k) * 17 + ((int)threadIdx.x >> 6)] = s;
+}
+template <int NV>
+__device__ __forceinline__ double sb_block_owner_from_lds(double *lds) {
+    const int nwave = (blockDim.x + 63) >> 6;
+    __syncthreads();
+    double t = 0.;
+    if (threadIdx.x < NV)
+        for (int w = 0; w < nwave; w++) t += lds[threadIdx.x * 17 + w];
+    return t;
+}
+
+// KEEP-ALL: step_build_kernel's step (in-cycle / closing, with / without XR) with r read ONCE per launch: the thread's residual
+// rows are loaded by the apply, next to the stencil gather (the same lines: a cache hit), and stay in registers (SB_MAX_TRIPS x
+// 16 B) for the shift epilogue, the build's <r,Ap'>, the close pass's P0' and XR; no later pass loads a.x.
+// Register use: the pass-1 dots walk one direction (all trips) at a time and hand its two sums to the wave trees as soon as they
+// are final (sb_wave_pair_to_lds: the bits of block_sum_owner<2 NDT>); the build and the close pass walk SB_KEEP_TB trips at a
+// time, one direction after the other; every stream is addressed as scalar base + one 32-bit offset per trip.  Every element sees
+// the same operations in the same order as in step_build_kernel (ac -= beta_j Ap_j in j order, each per-thread accumulator adds
+// the rows in trip order): the same bits.  Only the forms that fit 64 VGPRs without scratch are launched (sb_keep_fits).
+// CLOSE runs build | publish exchange 2 | close pass | poll 2 | XR: the build's Ap_j re-reads follow pass 1 closely, and the close
+// pass (x update and P0', which need only beta and cp) runs while the exchange-2 partials travel.  xr_out = ps[1] (read by the
+// close pass) and p_out = ps[0]: a thread reads an element of them before it writes it, and no other thread touches it; lc->cx,
+// which workgroup 0 updates behind poll 2, is read before this workgroup publishes.
+template <int NDT, bool XR, bool CLOSE, bool REALC>
+__global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs a) {
+    __shared__ double lds[(2 * NDT > 4 ? 2 * NDT : 4) * 17];
+    __shared__ double lds_pw[2 * SB_MAX_ND * 17], lds_ws[2 * SB_MAX_ND * RES_GRP];
+    __shared__ int gave_up;
+    __shared__ cplx sbeta[NDT], scp[NDT], scx[NDT];
+    extern __shared__ __attribute__((aligned(16))) unsigned char sb_smem[];   // Ar of this workgroup's rows: [trip][thread]
+    if (a.st->stop_at < a.st->base + a.it) return;
+    const int lb = logical_workgroup(a.rm, (int)blockIdx.x, (int)gridDim.x);
+    if (lb >= a.nlogical) return;
+    cplx *arL = reinterpret_cast<cplx *>(sb_smem);
+    const int tid = (int)threadIdx.x;
+    ResSync sy;
+    sy.slots = res_rsrc(a.slots, (unsigned)RES_SLOT_BYTES);
+    sy.gen = a.gen0;
+    sy.nblk = a.nlogical;
+    sy.lb = lb;
+    sy.abort_dev = a.abort_dev;
+    sy.spin_limit = a.spin_limit;
+    sy.pw = lds_pw;
+    sy.ws = lds_ws;
+    sy.gave_up = &gave_up;
+    if (threadIdx.x == 0) gave_up = 0;
+    if (a.test_stall && lb == a.test_stall - 1) return;
+    int64_t i0, end, stride;
+    row_range(a.rm, lb, a.nlogical, a.n, &i0, &end, &stride);
+    auto row = [&](int t) -> int64_t { return i0 + (int64_t)t * stride; };
+    // the rows' byte offsets (n < 2^28 rows here), one VGPR per trip for every stream: the loads and stores take a scalar base
+    // and this offset (64-bit addresses per stream and trip would be kept from pass 1 to the build, and spill)
+    uint32_t off[SB_MAX_TRIPS];
+#pragma unroll
+    for (int t = 0; t < SB_MAX_TRIPS; t++) off[t] = (uint32_t)row(t) * (uint32_t)sizeof(cplx);
+    auto at = [&](auto *p, int t) { return sb_elem(p, off[t]); };
+    cplx rk[SB_MAX_TRIPS];   // r of the thread's rows, from the apply to the last pass
+    // ---- apply (gcr_fused.hip step_apply_kernel): Ar to LDS, r kept ----
+#pragma unroll
+    for (int t = 0; t < SB_MAX_TRIPS; t++) {
+        const int64_t i = row(t);
+        rk[t] = make_double2(0., 0.);
+        if (i < end) {
+            const PatLds pl{nullptr, nullptr, nullptr};
+            cplx sum;
+            // (the stencil's columns are clamped to 0..n-1: 32-bit byte offsets from the scalar base, as below)
+            const auto xj = [&](int32_t j) -> cplx { return *sb_elem(a.x, (uint32_t)j * (uint32_t)sizeof(cplx)); };
+            if constexpr (REALC) sum = sten_row_product_t<7, false, 1>(a.m, i, xj);
+            else sum = fused_row_product<3, 7>(a.m, i, 0, pl, xj);
+            rk[t] = *at(a.x, t);
+            arL[t * RED_THREADS + tid] = a.m.shift ? csub(rk[t], cmul(a.m.k, sum)) : sum;
+        }
+        __builtin_amdgcn_sched_barrier(0);   // (one trip's gathers in registers at a time)
+    }
+    // ---- <Ar, Ap_j>, one direction (all trips) at a time: its two sums go through the wave trees as soon as they are final ----
+    {
+#pragma unroll
+        for (int j = 0; j < NDT; j++) {
+            cplx b[SB_MAX_TRIPS];
+#pragma unroll
+            for (int t = 0; t < SB_MAX_TRIPS; t++) b[t] = row(t) < end ? ld_stream<true>(at(a.aps[j], t)) : make_double2(0., 0.);
+            double v[2] = {0., 0.};
+#pragma unroll
+            for (int t = 0; t < SB_MAX_TRIPS; t++) {
+                if (row(t) < end) {
+                    const cplx tt = cconj_mul(arL[t * RED_THREADS + tid], b[t]);
+                    v[0] += tt.x;
+                    v[1] += tt.y;
+                }
+            }
+            sb_wave_pair_to_lds(v, lds, 2 * j);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const double mine = sb_block_owner_from_lds<2 * NDT>(lds);
+        if (tid < 2 * NDT) {
+            const v4i w4 = {__double2loint(mine), __double2hiint(mine), (int)sy.gen, 0};
+            __builtin_amdgcn_raw_buffer_store_b128(w4, sy.slots, ((1 * RES_NV + tid) * RES_BLK + lb) * 16, 0, RES_SC1);
+        }
+    }
+    // the build's first streams are requested before the exchange is polled (they do not depend on beta)
+    cplx pre[SB_KEEP_TB];
+#pragma unroll
+    for (int u = 0; u < SB_KEEP_TB; u++) pre[u] = row(u) < end ? ld_stream<NTS>(at(a.aps[0], u)) : make_double2(0., 0.);
+    if (!res_collect<2 * NDT>(sy, 1)) {
+        if (threadIdx.x == 0) {
+            __hip_atomic_store(a.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.abort_host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        for (int64_t i = i0; i < end; i += stride) a.ap_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
+        if (tid < 4) a.partsA[tid * RED_MAX_BLOCKS + lb] = __builtin_nan("");
+        return;
+    }
+    // ---- direction build (as in step_build_kernel) ----
+    bool ends_here = false;
+    if (XR || lb == 0) {
+        double rr[1];
+        fold_partials<1>(a.partsR, a.nblkR, a.strideR, rr, lds);
+        if (lb == 0 && threadIdx.x == 0) {
+            sb_close_step(a.st, a.it, rr[0], a.hist, a.hist_cap, CLOSE);
+            if (CLOSE) a.st->closed = 1;
+        }
+        ends_here = __builtin_amdgcn_readfirstlane(!((rr[0] / a.st->bnorm2) > a.st->tol2)) != 0;   // (decided here: not sunk to XR)
+    }
+    if (tid < NDT) sbeta[tid] = cdiv(make_double2(res_total(sy, 2 * tid), res_total(sy, 2 * tid + 1)), a.den[tid]);
+    __syncthreads();
+    if constexpr (CLOSE) {
+        if (tid < NDT) {
+            const int m = tid;
+            const LeanCoef *lc = a.lc;
+            cplx c = make_double2(0., 0.);
+            if (m == 0) {
+                for (int j = 0; j < NDT; j++) c = cadd(c, cmul(sbeta[j], j == 0 ? make_double2(1., 0.) : lc->t[j]));
+            } else {
+                for (int j = m; j < NDT; j++) c = cadd(c, cmul(sbeta[j], j == m ? make_double2(1., 0.) : lc->T[j * LND + m]));
+            }
+            scp[m] = c;
+            scx[m] = lc->cx[m];
+        }
+        __syncthreads();
+    }
+    if (!CLOSE && lb == 0 && tid <= NDT) {
+        constexpr int k = NDT;
+        const int m = tid;
+        LeanCoef *lc = a.lc;
+        cplx c = make_double2(0., 0.);
+        if (m == 0) {
+            for (int j = 0; j < k; j++) c = csub(c, cmul(sbeta[j], j == 0 ? make_double2(1., 0.) : lc->t[j]));
+            lc->t[k] = c;
+        } else if (m < k) {
+            for (int j = m; j < k; j++) c = csub(c, cmul(sbeta[j], j == m ? make_double2(1., 0.) : lc->T[j * LND + m]));
+            lc->T[k * LND + m] = c;
+        } else {
+            lc->T[k * LND + k] = make_double2(1., 0.);
+        }
+    }
+    {
+        cplx beta[NDT];   // (in scalar registers once: read from LDS per batch, the compiler keeps them in vector registers)
+#pragma unroll
+        for (int j = 0; j < NDT; j++) beta[j] = to_sgpr(sbeta[j]);
+        double v[4] = {0., 0., 0., 0.};
+#pragma unroll
+        for (int t0 = 0; t0 < SB_MAX_TRIPS; t0 += SB_KEEP_TB) {
+            cplx ac[SB_KEEP_TB];
+#pragma unroll
+            for (int u = 0; u < SB_KEEP_TB; u++) ac[u] = make_double2(0., 0.);
+#pragma unroll
+            for (int j = 0; j < NDT; j++) {
+                cplx aj[SB_KEEP_TB];
+#pragma unroll
+                for (int u = 0; u < SB_KEEP_TB; u++)
+                    aj[u] = (t0 == 0 && j == 0) ? pre[u] : row(t0 + u) < end ? ld_stream<NTS>(at(a.aps[j], t0 + u)) : make_double2(0., 0.);
+#pragma unroll
+                for (int u = 0; u < SB_KEEP_TB; u++) ac[u] = csub(ac[u], cmul(beta[j], aj[u]));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int u = 0; u < SB_KEEP_TB; u++) {
+                const int t = t0 + u;
+                const int64_t i = row(t);
+                if (i < end) {
+                    const cplx an = cadd(arL[t * RED_THREADS + tid], ac[u]);
+                    *at(a.ap_out, t) = an;
+                    if (XR) arL[t * RED_THREADS + tid] = an;   // (A r is not needed any more; the update below wants Ap')
+                    const cplx tt = cconj_mul(rk[t], an);
+                    v[0] += tt.x; v[1] += tt.y;
+                    const cplx w = cconj_mul(an, an);
+                    v[2] += w.x; v[3] += w.y;
+                }
+            }
+        }
+        const double mine = block_sum_owner<4>(v, lds);
+        if (tid < 4) a.partsA[tid * RED_MAX_BLOCKS + lb] = mine;
+        if (XR && tid < 4) {
+            const v4i w4 = {__double2loint(mine), __double2hiint(mine), (int)sy.gen, 0};
+            __builtin_amdgcn_raw_buffer_store_b128(w4, sy.slots, ((2 * RES_NV + tid) * RES_BLK + lb) * 16, 0, RES_SC1);
+        }
+    }
+    if constexpr (CLOSE) {
+        // x += sum_j cx_j p_j;  P0' = r - sum_j cp_j p_j  (p_0 = P0, p_m = D_m), while the exchange-2 partials travel
+        cplx cx[NDT], cp[NDT];
+#pragma unroll
+        for (int j = 0; j < NDT; j++) {
+            cx[j] = to_sgpr(scx[j]);
+            cp[j] = to_sgpr(scp[j]);
+        }
+#pragma unroll
+        for (int t0 = 0; t0 < SB_MAX_TRIPS; t0 += SB_KEEP_TB) {
+            cplx xv[SB_KEEP_TB], pc[SB_KEEP_TB];
+#pragma unroll
+            for (int u = 0; u < SB_KEEP_TB; u++) {
+                xv[u] = row(t0 + u) < end ? *at(a.xvec, t0 + u) : make_double2(0., 0.);
+                pc[u] = make_double2(0., 0.);
+            }
+#pragma unroll
+            for (int j = 0; j < NDT; j++) {
+                cplx pj[SB_KEEP_TB];
+#pragma unroll
+                for (int u = 0; u < SB_KEEP_TB; u++) pj[u] = row(t0 + u) < end ? ld_stream<NTS>(at(a.ps[j], t0 + u)) : make_double2(0., 0.);
+#pragma unroll
+                for (int u = 0; u < SB_KEEP_TB; u++) {
+                    xv[u] = cadd(xv[u], cmul(cx[j], pj[u]));
+                    pc[u] = csub(pc[u], cmul(cp[j], pj[u]));
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < SB_KEEP_TB; u++) {
+                const int64_t i = row(t0 + u);
+                if (i < end) {
+                    *at(a.xvec, t0 + u) = xv[u];
+                    st_stream<NTS>(at(a.p_out, t0 + u), cadd(rk[t0 + u], pc[u]));
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if constexpr (XR) {
+        if (!res_collect<4>(sy, 2)) {
+            if (threadIdx.x == 0) {
+                __hip_atomic_store(a.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(a.abort_host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+            for (int64_t i = i0; i < end; i += stride) a.xr_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
+            if (threadIdx.x == 0) a.partsR_out[lb] = __builtin_nan("");
+            return;
+        }
+        if (ends_here) return;
+        const cplx num = make_double2(res_total(sy, 0), res_total(sy, 1)), den = make_double2(res_total(sy, 2), res_total(sy, 3));
+        const cplx alpha = to_sgpr(cdiv(num, den));
+        if (lb == 0 && threadIdx.x == 0) {
+            *a.xr_den_slot = den;
+            a.st->npend = a.xr_slot + 1;
+        }
+        if (lb == 0 && tid < LND) lean_pending_update(a.lc, a.xr_slot, alpha, tid);
+        double vr[1] = {0.};
+#pragma unroll
+        for (int t = 0; t < SB_MAX_TRIPS; t++) {
+            const int64_t i = row(t);
+            if (i < end) {
+                const cplx rn = csub(rk[t], cmul(alpha, arL[t * RED_THREADS + tid]));
+                *at(a.xr_out, t) = rn;
+                vr[0] += rn.x * rn.x + rn.y * rn.y;
+            }
+        }
+        const double tot = block_sum_owner<1>(vr, lds);
+        if (threadIdx.x == 0) a.partsR_out[lb] = tot;
+    }
+}
+
 // The start of a solve from x0 = 0 as ONE launch (r0 = P0 = b, no preconditioner): what gcr.hip ran as copy2_kernel (r = P0 = b),
 // gcr_fused.hip init_apply_kernel (Ap0 = A b and the partials of <b,Ap0>, <Ap0,Ap0>, |b|^2), init_kernel (|b|^2, hist[0]) and
 // step 1's xr_update_kernel<true, true> (alpha, r1 = b - alpha Ap0 into the residual ring, its |r1|^2 partials):
@@ -462,7 +747,38 @@ bool set_stepbuild_keepr_enabled(bool on) {
     g_sb_keepr = on ? 1 : 0;
     return prev;
 }
+// KEEP-ALL (step_keep_kernel) where an instantiation keeps 0 scratch and 8 waves per SIMD: up to 2 stored directions in every
+// form, 3 except the closing step with XR (tests/test_stepbuild_keep_all.py).  With more directions the kept rows spill (the
+// build's two trips of NDT streams, beta and the kept rows exceed 64 VGPRs): step_build_kernel takes those steps.
+template <int NDT, bool XR, bool CLOSE> constexpr bool sb_keep_fits() { return NDT <= 2 || (NDT == 3 && !(XR && CLOSE)); }
+template <int NDT, bool XR, bool CLOSE, bool R> const void *sb_keep() {
+    if constexpr (sb_keep_fits<NDT, XR, CLOSE>()) return (const void *)step_keep_kernel<NDT, XR, CLOSE, R>;
+    else return nullptr;
+}
+// off: the step_build_kernel dispatch below
+static int g_sb_keep_all = -1;
+static bool sb_keep_all_enabled() {
+    if (g_sb_keep_all < 0) g_sb_keep_all = !(getenv("MGCR_SB_KEEP_ALL") && atoi(getenv("MGCR_SB_KEEP_ALL")) == 0);
+    return g_sb_keep_all != 0;
+}
+bool set_stepbuild_keep_all_enabled(bool on) {
+    const bool prev = sb_keep_all_enabled();
+    g_sb_keep_all = on ? 1 : 0;
+    return prev;
+}
 static const void *sb_kernel(int nd, bool xr, bool close, bool realc) {
+    if (sb_keep_all_enabled() && (nd <= 2 || (nd == 3 && !(xr && close)))) {   // (sb_keep_fits)
+#define SKR(NDT, R) (close ? (xr ? sb_keep<NDT, true, true, R>() : sb_keep<NDT, false, true, R>()) \
+                           : (xr ? sb_keep<NDT, true, false, R>() : sb_keep<NDT, false, false, R>()))
+#define SKK(NDT) (realc ? SKR(NDT, true) : SKR(NDT, false))
+        switch (nd) {
+            case 1: return SKK(1);
+            case 2: return SKK(2);
+            default: return SKK(3);
+        }
+#undef SKK
+#undef SKR
+    }
     const bool keepr = xr && !close && sb_keepr_enabled();
 #define SBX(NDT, R) ((keepr && sb_keepr_fits<NDT>()) ? (const void *)step_build_kernel<3, 7, NDT, true, false, R, sb_keepr_fits<NDT>()> \
                                                      : (const void *)step_build_kernel<3, 7, NDT, true, false, R>)
