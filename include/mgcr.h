@@ -39,6 +39,7 @@ extern "C" {
 
 typedef struct mgcr_vec_s *mgcr_vec_t; /* device-resident Field   (src/Fields.h:29-71)   */
 typedef struct mgcr_op_s *mgcr_op_t;   /* device-resident Operator (src/Operator.h:16-29) */
+typedef struct mgcr_mvec_s *mgcr_mvec_t; /* device-resident block of k Fields (multi-RHS; no reference counterpart) */
 
 /* ---- context ------------------------------------------------------------------------------ */
 int mgcr_init(int device);
@@ -72,6 +73,27 @@ int mgcr_normalise(mgcr_vec_t v);                                  /* normalise 
  * (4-entry) spinor dimension */
 int mgcr_vec_gamma5(mgcr_vec_t in, mgcr_vec_t out, int64_t inner);
 
+/* ---- multi-vector: a block of k Fields, 1 <= k <= 16 (new: the reference works on one right-hand side at a time) ----
+ * Device layout: row-major with the columns INTERLEAVED, element (row i, column j) at data[i * k + j] — the k values an
+ * operator gathers for one column index are contiguous (k = 8: one 128-byte line), and a matrix is streamed once for all
+ * k products (mgcr_op_apply_multi).  Host arrays hold k contiguous columns, [k][n] interleaved (re, im); the transposition
+ * runs on the device. */
+int mgcr_mvec_create(int64_t n, int32_t k, mgcr_mvec_t *out);      /* k outside 1 .. 16: MGCR_ERR_INVALID */
+int mgcr_mvec_destroy(mgcr_mvec_t v);
+int64_t mgcr_mvec_size(mgcr_mvec_t v);                             /* n: rows = entries per column */
+int32_t mgcr_mvec_ncols(mgcr_mvec_t v);                            /* k */
+int mgcr_mvec_zero(mgcr_mvec_t v);
+int mgcr_mvec_upload(mgcr_mvec_t v, const double *host_ri);        /* host: [k][n][2] */
+int mgcr_mvec_download(mgcr_mvec_t v, double *host_ri);
+int mgcr_mvec_set_column(mgcr_mvec_t v, int32_t j, mgcr_vec_t src);  /* column j = src (device-side pack) */
+int mgcr_mvec_get_column(mgcr_mvec_t v, int32_t j, mgcr_vec_t dst);  /* dst = column j (device-side unpack) */
+/* k dot products (conj on a) / squared norms in ONE pass over a and b: out_ri[2 j], out_ri[2 j + 1] = <a_j, b_j>, out[j] = |a_j|^2.
+ * Same rows per thread, same summation tree and fold as mgcr_dot / mgcr_norm2: the value of column j has the bits of
+ * mgcr_dot / mgcr_norm2 on that column held in a Field. */
+int mgcr_mvec_dot(mgcr_mvec_t a, mgcr_mvec_t b, double *out_ri);
+int mgcr_mvec_norm2(mgcr_mvec_t a, double *out);
+int mgcr_mvec_axpy(const double *alpha_ri, mgcr_mvec_t x, mgcr_mvec_t y);  /* y_j += alpha_j x_j, alpha_ri: [k][2] */
+
 /* ---- Operators: src/Operator.h, src/HierarchicalSparse.h ---------------------------------- */
 /* Sparse<long> (CSR, int64 indices as the reference stores them, src/Operator.h:56-101).  The
  * device copy is an ELL slab (column-major, int32 columns) plus a CSR tail for long rows. */
@@ -98,6 +120,16 @@ int64_t mgcr_op_nnz(mgcr_op_t op);
 /* y = op(x)        Operator::operator() src/Operator.h:19; Sparse :330-346; DiracOp :569-575;
  *                  HierarchicalSparse.h:101-161; GCR.h:62-68; MG.h:124-129 */
 int mgcr_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y);
+/* Y = op(X) for a block of k Fields: the matrix is read once for all k columns.  Column j of Y is BIT-IDENTICAL to
+ * mgcr_op_apply on column j: per column the kernels add a row's products in the order mgcr_op_ell_layout documents (block-CSR:
+ * per block in column order, blocks in storage order), whichever storage form carries the matrix.  Supported: single-GPU
+ * Sparse in every storage form (ELL slab + CSR tail with 1 .. 16 lanes per row, the LDS-window variant, both row-pattern
+ * dictionary forms, the stencil view), DiracOp on top of any of them, HierarchicalSparse / Dense.  Distributed operators
+ * and GCR / MG objects: MGCR_ERR_UNSUPPORTED.  X == Y, mismatched n or k: MGCR_ERR_INVALID.
+ * Block-CSR stages min(k, 64 / bs) (at least 1) columns of products and k columns of accumulators in LDS,
+ * 16 (kg bs (bs + 1) + bs k) bytes: block sizes for which that exceeds 160 KiB (bs from about 95, depending on k) are
+ * MGCR_ERR_UNSUPPORTED here although the single apply takes them up to bs = 100. */
+int mgcr_op_apply_multi(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y);
 /* bytes the device layout of `op` occupies / streams per apply (for roofline accounting) */
 int mgcr_op_stored_bytes(mgcr_op_t op, int64_t *matrix_bytes, int32_t *ell_width, int64_t *tail_nnz);
 /* storage a Sparse ended up with: *format = 0 plain ELL slab (+ CSR tail), 1 row-pattern dictionary
@@ -158,7 +190,8 @@ int mgcr_set_option(const char *name, int value, int *previous);
  * workgroup (csrc/gcr_small.hip), "one_launch_fallbacks" = top-level solves that were repeated on the multi-kernel path
  * because a one-launch path gave up (foreign work on the device: its grid was not co-resident), "halo_split_exchanges" =
  * peer-write halo exchanges of distributed applies that ran split (store + publish | interior rows | wait | boundary rows),
- * "pw_tail_folds" = reductions folded and summed over the ranks inside their producing kernel. */
+ * "pw_tail_folds" = reductions folded and summed over the ranks inside their producing kernel, "multi_solves" = batched solves
+ * (mgcr_gcr_solve_multi) completed. */
 int mgcr_stat(const char *name, int64_t *value);
 
 /* Self-test of the hardware behaviour the one-launch solver paths (csrc/gcr_resident.hip, gcr_stepbuild.hip) build on: inside
@@ -194,6 +227,25 @@ typedef struct mgcr_gcr_param {
  * *n_iter = iterations performed (global_count); *converged = 0 iff n_iter == max_iter. */
 int mgcr_gcr_solve(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_vec_t rhs, mgcr_vec_t x,
                    double *hist, int32_t hist_cap, int32_t *n_iter, int32_t *converged);
+/* k independent solves A x_j = rhs_j that share every launch (batched restarted GCR, csrc/gcr_multi.hip).
+ * hist: [k][hist_cap] (may be NULL), row j as mgcr_gcr_solve fills it for column j; n_iter, converged: [k] (may be NULL).
+ * Every column has its own device-resident scalars and stop flag; a column that has stopped (|r|^2/|b|^2 <= tol^2, or
+ * whatever stops the single solve) is FROZEN — its x, residual, history and iteration count no longer change — while the
+ * others go on; the solve ends when every column has stopped or at max_iter.  x is updated in place; use_x0 as in
+ * mgcr_gcr_solve.
+ * Supported: restart mode (restart != 0, cycles of at most 16 steps), unpreconditioned, on the operators of
+ * mgcr_op_apply_multi.  MGCR_ERR_UNSUPPORTED: truncation != 0, restart == 0, restart > 16 (with max_iter >= 16), a left or
+ * right preconditioner, flexible, profile_spmv, distributed operators, GCR / MG objects as the operator.
+ * Arithmetic: the lean restart cycle of mgcr_gcr_solve per column, with the same rows per thread, grid size, summation trees
+ * and folds: history, iteration count, convergence flag and x of column j are BIT-IDENTICAL to mgcr_gcr_solve(A, param, rhs_j)
+ * with default options, for operators whose mgcr_op_xr_fuse_kind is 0 or 1 and more rows than the small-solve limit
+ * (mgcr_set_small_solve_rows).  Where the single solve sums in another order — the one-workgroup path at or below that limit,
+ * and mgcr_op_xr_fuse_kind == 2 (grids from 182^3: |r'|^2 and the start-up sums run over a banded row map) — the batched solve
+ * sums in the plain row order and the results agree to rounding only.  There is no one-workgroup batched form.
+ * The work vectors (2 + 2 * min(restart, max_iter + 1) blocks of n x k) are kept by the library from one batched solve to the
+ * next while n, k and the cycle length stay the same, and are freed by mgcr_finalize. */
+int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t rhs, mgcr_mvec_t x, double *hist, int32_t hist_cap,
+                         int32_t *n_iter, int32_t *converged);
 /* Unpreconditioned solves on a single-GPU Sparse / DiracOp with at most `rows` unknowns (default
  * 1024, $MGCR_SMALL_SOLVE_ROWS; and at most 16*rows stored entries) and <= 8 stored directions run
  * as ONE launch of one workgroup (latency regime: coarsest multigrid levels); 0 disables that path.
@@ -320,6 +372,8 @@ int mgcr_dbcsr_create(mgcr_comm_t comm, int64_t nb_global, int64_t brow0, int32_
 /* runs `reps` applies back to back on the library stream, bracketed by hipEvents there;
  * returns the average milliseconds per apply */
 int mgcr_bench_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y, int32_t reps, double *ms_avg);
+/* the same for the k-wide apply (tools/bench_multi_rhs.py) */
+int mgcr_bench_op_apply_multi(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y, int32_t reps, double *ms_avg);
 /* In-loop timing of the last solve that ran with profile_spmv = 1: total milliseconds, over its
  * *n_iter iterations, of the three phases of an iteration — [0] alpha / residual update (+ right
  * preconditioner), [1] operator apply (incl. halo exchange) + beta dot products, [2] direction build —

@@ -119,6 +119,21 @@ _SIGS = {
     "mgcr_set_small_solve_rows": (C.c_int, [C.c_int64]),
     "mgcr_gcr_last_profile": (C.c_int, [_dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mgcr_bench_op_apply": (C.c_int, [_vp, _vp, _vp, C.c_int32, _dp]),
+    "mgcr_mvec_create": (C.c_int, [C.c_int64, C.c_int32, C.POINTER(_vp)]),
+    "mgcr_mvec_destroy": (C.c_int, [_vp]),
+    "mgcr_mvec_size": (C.c_int64, [_vp]),
+    "mgcr_mvec_ncols": (C.c_int32, [_vp]),
+    "mgcr_mvec_zero": (C.c_int, [_vp]),
+    "mgcr_mvec_upload": (C.c_int, [_vp, _vp]),
+    "mgcr_mvec_download": (C.c_int, [_vp, _vp]),
+    "mgcr_mvec_set_column": (C.c_int, [_vp, C.c_int32, _vp]),
+    "mgcr_mvec_get_column": (C.c_int, [_vp, C.c_int32, _vp]),
+    "mgcr_mvec_dot": (C.c_int, [_vp, _vp, _dp]),
+    "mgcr_mvec_norm2": (C.c_int, [_vp, _dp]),
+    "mgcr_mvec_axpy": (C.c_int, [_dp, _vp, _vp]),
+    "mgcr_op_apply_multi": (C.c_int, [_vp, _vp, _vp]),
+    "mgcr_bench_op_apply_multi": (C.c_int, [_vp, _vp, _vp, C.c_int32, _dp]),
+    "mgcr_gcr_solve_multi": (C.c_int, [_vp, C.POINTER(GcrParamC), _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mgcr_timer_start": (C.c_int, []),
     "mgcr_timer_stop": (C.c_int, [_dp]),
 }

@@ -160,6 +160,97 @@ class Field:
             pass
 
 
+class MultiField:
+    """Block of k Fields on one mesh (multi-RHS; the reference has no counterpart).  On the device the columns are interleaved
+    (element (row i, column j) at i * k + j, include/mgcr.h); on the host a block is a (k, n) complex128 array."""
+
+    def __init__(self, dims, k, data=None):
+        _lib.init()
+        if isinstance(dims, (int, np.integer)):
+            dims = (int(dims),)
+        self.dims = tuple(int(d) for d in dims)
+        self.k = int(k)
+        n = int(np.prod(self.dims, dtype=np.int64))
+        h = C.c_void_p()
+        check(_lib.lib().mgcr_mvec_create(n, self.k, C.byref(h)))
+        self.h = h
+        self._n = n
+        if data is not None:
+            self.upload(data)
+
+    @classmethod
+    def from_fields(cls, fields):
+        """Packs Fields of one size into a block, on the device."""
+        fields = list(fields)
+        if not fields:
+            raise MgcrError(1, "MultiField.from_fields: no Fields")
+        out = cls(fields[0].dims, len(fields))
+        for j, f in enumerate(fields):
+            check(_lib.lib().mgcr_mvec_set_column(out.h, j, f.h))
+        return out
+
+    @classmethod
+    def like(cls, other):
+        return cls(other.dims, other.k)
+
+    def field_size(self):
+        return self._n
+
+    def ncols(self):
+        return self.k
+
+    def upload(self, data):
+        a = np.ascontiguousarray(data, dtype=c128)
+        if a.size != self._n * self.k:
+            raise MgcrError(1, "Dimension mismatch.")
+        check(_lib.lib().mgcr_mvec_upload(self.h, a.ctypes.data))
+        return self
+
+    def to_numpy(self):
+        out = np.empty((self.k, self._n), c128)
+        check(_lib.lib().mgcr_mvec_download(self.h, out.ctypes.data))
+        return out
+
+    def column(self, j):
+        """Column j as a new Field (device-side unpack)."""
+        out = Field(self.dims)
+        check(_lib.lib().mgcr_mvec_get_column(self.h, int(j), out.h))
+        return out
+
+    def set_column(self, j, field):
+        check(_lib.lib().mgcr_mvec_set_column(self.h, int(j), field.h))
+        return self
+
+    def set_zero(self):
+        check(_lib.lib().mgcr_mvec_zero(self.h))
+        return self
+
+    def dot(self, other):
+        """k dot products <self_j, other_j> (conj on self) in one pass; column j has the bits of Field.dot on that column."""
+        out = (C.c_double * (2 * self.k))()
+        check(_lib.lib().mgcr_mvec_dot(self.h, other.h, out))
+        return np.array([complex(out[2 * j], out[2 * j + 1]) for j in range(self.k)], c128)
+
+    def squarednorm(self):
+        out = (C.c_double * self.k)()
+        check(_lib.lib().mgcr_mvec_norm2(self.h, out))
+        return np.array(out[:], np.float64)
+
+    def axpy(self, alpha, x):
+        """self_j += alpha_j * x_j (alpha: one value, or k of them)."""
+        al = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, c128), (self.k,)))
+        check(_lib.lib().mgcr_mvec_axpy(al.ctypes.data_as(C.POINTER(C.c_double)), x.h, self.h))
+        return self
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                _lib.lib().mgcr_mvec_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
 class Operator:
     """Operator<num_type> (src/Operator.h:16-29)."""
 
@@ -180,6 +271,19 @@ class Operator:
             out = Field(f.dims if nrow == f.field_size() else (nrow,))
         check(_lib.lib().mgcr_op_apply(self.h, f.h, out.h))
         return out
+
+    def apply_multi(self, X, out=None):
+        """Y = op(X) for a MultiField: the matrix is streamed once for all k columns; column j has the bits of op(X.column(j))."""
+        if out is None:
+            nrow = self.get_nrow()
+            out = MultiField(X.dims if nrow == X.field_size() else (nrow,), X.k)
+        check(_lib.lib().mgcr_op_apply_multi(self.h, X.h, out.h))
+        return out
+
+    def bench_apply_multi(self, X, Y, reps=20):
+        ms = C.c_double()
+        check(_lib.lib().mgcr_bench_op_apply_multi(self.h, X.h, Y.h, reps, C.byref(ms)))
+        return ms.value
 
     def stored_bytes(self):
         b, w, t = C.c_int64(), C.c_int32(), C.c_int64()
@@ -402,6 +506,22 @@ class GCR(Operator):
         self.last_converged = bool(conv.value)
         self.last_history = hist[: it.value + 1].copy()
         return x
+
+    def solve_multi(self, RHS, X):
+        """k independent solves A x_j = rhs_j in lockstep (mgcr_gcr_solve_multi; restart mode, unpreconditioned).  X is updated
+        in place; last_history (k arrays), last_iterations and last_converged (lists) are kept per column."""
+        if self.A is None:
+            raise MgcrError(1, "GCR has no operator (call initialise first)")
+        k = RHS.k
+        cap = max(self.param.max_iter, 1) + 1
+        hist = np.zeros((k, cap), np.float64)
+        it, conv = (C.c_int32 * k)(), (C.c_int32 * k)()
+        pc = self.param._c()
+        check(_lib.lib().mgcr_gcr_solve_multi(self.A.h, C.byref(pc), RHS.h, X.h, hist.ctypes.data, cap, it, conv))
+        self.last_iterations = [int(v) for v in it]
+        self.last_converged = [bool(v) for v in conv]
+        self.last_history = [hist[j, : it[j] + 1].copy() for j in range(k)]
+        return X
 
 
 def legacy_dense_gcr(matrix, rhs, x, tol, max_iter, truncation, verbose=True):

@@ -212,6 +212,7 @@ int mgcr_stat(const char *name, int64_t *value) {
     else if (!strcmp(name, "one_launch_fallbacks")) *value = gcr_fallback_count();
     else if (!strcmp(name, "halo_split_exchanges")) *value = dist_halo_split_count();
     else if (!strcmp(name, "pw_tail_folds")) *value = comm_pw_tail_count();
+    else if (!strcmp(name, "multi_solves")) *value = gcr_multi_solve_count();
     else { set_error("mgcr_stat: unknown counter '%s'", name); return MGCR_ERR_INVALID; }
     return MGCR_OK;
 }
@@ -361,6 +362,67 @@ int mgcr_bench_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y, int32_t reps, 
     MGCR_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
     *ms_avg = (double)ms / reps;
     return MGCR_OK;
+}
+
+// ---- blocks of k Fields: k-wide apply (spmm.hip), batched GCR (gcr_multi.hip) ------------------------------------------
+static int apply_multi_checks(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y, const char *who) {
+    MGCR_CHECK(op && x && y, MGCR_ERR_INVALID, "%s: null argument", who);
+    MGCR_CHECK(op->kind != OP_GCR && op->kind != OP_MG, MGCR_ERR_UNSUPPORTED, "%s: GCR and MG objects cannot be applied to a block of Fields", who);
+    const Op *b0 = op->kind == OP_DIRAC ? op->base : op;
+    MGCR_CHECK(!op->dist && !op->comm && !b0->dist && !b0->comm, MGCR_ERR_UNSUPPORTED, "%s: distributed operators are not supported", who);
+    MGCR_CHECK(x->n == op->dim, MGCR_ERR_INVALID, "Sparse matrix dimension does not match Field dimension!");
+    const int64_t nrow = op->nrow ? op->nrow : op->dim;
+    MGCR_CHECK(y->n == nrow, MGCR_ERR_INVALID, "output block has %lld rows, operator has %lld", (long long)y->n, (long long)nrow);
+    MGCR_CHECK(x->k == y->k, MGCR_ERR_INVALID, "%s: input has %d columns, output has %d", who, (int)x->k, (int)y->k);
+    MGCR_CHECK(x != y && (x->d != y->d || !x->d), MGCR_ERR_INVALID, "%s: input and output must be different blocks", who);
+    return MGCR_OK;
+}
+
+int mgcr_op_apply_multi(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y) {
+    MGCR_TRY(require_ctx());
+    MGCR_TRY(apply_multi_checks(op, x, y, "mgcr_op_apply_multi"));
+    LOCK();
+    return op_apply_multi_raw(op, x->d, y->d, x->n, x->k);
+}
+
+int mgcr_bench_op_apply_multi(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y, int32_t reps, double *ms_avg) {
+    MGCR_TRY(require_ctx());
+    MGCR_CHECK(reps > 0 && ms_avg, MGCR_ERR_INVALID, "mgcr_bench_op_apply_multi: bad argument");
+    MGCR_TRY(apply_multi_checks(op, x, y, "mgcr_bench_op_apply_multi"));
+    LOCK();
+    Context &c = ctx();
+    MGCR_TRY(op_apply_multi_raw(op, x->d, y->d, x->n, x->k));  // warm-up
+    MGCR_HIP(hipEventRecord(c.ev0, c.stream));
+    for (int i = 0; i < reps; i++) MGCR_TRY(op_apply_multi_raw(op, x->d, y->d, x->n, x->k));
+    MGCR_HIP(hipEventRecord(c.ev1, c.stream));
+    MGCR_HIP(hipEventSynchronize(c.ev1));
+    float ms = 0.f;
+    MGCR_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+    *ms_avg = (double)ms / reps;
+    return MGCR_OK;
+}
+
+int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t rhs, mgcr_mvec_t x, double *hist, int32_t hist_cap,
+                         int32_t *n_iter, int32_t *converged) {
+    MGCR_TRY(require_ctx());
+    MGCR_CHECK(A && param && rhs && x, MGCR_ERR_INVALID, "mgcr_gcr_solve_multi: null argument");
+    MGCR_CHECK(param->truncation >= 0 && param->restart >= 0 && param->max_iter >= 0, MGCR_ERR_INVALID, "negative GCR parameter");
+    MGCR_CHECK(param->truncation == 0, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: truncation mode is not supported (restart mode only)");
+    MGCR_CHECK(param->restart != 0, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: restart mode only (restart != 0)");
+    MGCR_CHECK(!param->left_precond && !param->right_precond, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: preconditioners are not supported");
+    MGCR_CHECK(!param->flexible && !param->profile_spmv, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: flexible / profile_spmv are not supported");
+    MGCR_CHECK(A->kind != OP_GCR && A->kind != OP_MG, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: the operator must be a matrix");
+    {
+        const Op *b0 = A->kind == OP_DIRAC ? A->base : A;
+        MGCR_CHECK(!A->dist && !A->comm && !b0->dist && !b0->comm, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: distributed operators are not supported");
+    }
+    MGCR_CHECK(rhs->n == A->dim, MGCR_ERR_INVALID, "Field dimension does not match with Operator!");
+    MGCR_CHECK(x->n == A->dim, MGCR_ERR_INVALID, "x dimension does not match with Operator!");
+    MGCR_CHECK((A->nrow ? A->nrow : A->dim) == A->dim, MGCR_ERR_INVALID, "mgcr_gcr_solve_multi: the operator must be square");
+    MGCR_CHECK(rhs->k == x->k, MGCR_ERR_INVALID, "mgcr_gcr_solve_multi: rhs has %d columns, x has %d", (int)rhs->k, (int)x->k);
+    MGCR_CHECK(rhs != x && (rhs->d != x->d || !x->d), MGCR_ERR_INVALID, "rhs and x must be different blocks");
+    LOCK();
+    return gcr_multi_run(A, *param, rhs->d, x->d, x->n, x->k, hist, hist_cap, n_iter, converged);
 }
 
 }  // extern "C"

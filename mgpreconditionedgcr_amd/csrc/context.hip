@@ -78,6 +78,7 @@ int mgcr_finalize(void) {
     if (!c.ready) return MGCR_OK;
     hipStreamSynchronize(c.stream);
     resident_shutdown();
+    multi_release();
     hipEventDestroy(c.ev0);
     hipEventDestroy(c.ev1);
     hipHostFree(c.h_mail);

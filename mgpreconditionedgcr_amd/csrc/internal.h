@@ -72,6 +72,15 @@ struct Vec {
     cplx *w() { zero_known = false; return d; }
 };
 
+// Block of k Fields ("multi-vector"): row-major with the columns interleaved, element (row i, column j) at d[i * k + j] —
+// one gathered row of x is k contiguous values (k = 8: one 128-byte line)
+struct MVec {
+    int64_t n = 0;
+    int32_t k = 0;
+    cplx *d = nullptr;
+};
+constexpr int MV_MAX_K = 16;
+
 enum OpKind { OP_CSR = 1, OP_DIRAC = 2, OP_BCSR = 3, OP_GCR = 4, OP_MG = 5 };
 
 // ELL slab + CSR tail (int32 indices).
@@ -308,6 +317,15 @@ int gcr_state_set_param(GcrState *s, const mgcr_gcr_param *p);
 int gcr_apply_as_operator(GcrState *s, const cplx *f, cplx *y);
 void gcr_last_profile(double *phase_ms_total, int *n_iter, int *fused);
 
+// ---- mvec.hip / spmm.hip / gcr_multi.hip: blocks of k Fields ------------------------------------
+int mv_copy(cplx *dst, const cplx *src, int64_t n, int k);
+// y = op(x) for every column (column j bit-identical to op_apply_raw on column j); w != nullptr (plain Sparse only): y = w - op(x)
+int op_apply_multi_raw(Op *op, const cplx *x, cplx *y, int64_t n, int k, const cplx *w = nullptr);
+int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int64_t n, int k, double *hist, int hist_cap, int *n_iter,
+                  int *converged);
+int64_t gcr_multi_solve_count();
+void multi_release();   // frees the batched solve's cached work storage and the block BLAS-1 buffers (mgcr_finalize)
+
 // ---- gcr_small.hip ---------------------------------------------------------------------------
 void gcr_small_set_limit(int64_t rows);
 int64_t gcr_small_solve_count();
@@ -319,3 +337,4 @@ int gcr_small_run(Op *A, const mgcr_gcr_param &p, int storage, int restart, cons
 
 struct mgcr_vec_s : mgcr::Vec {};
 struct mgcr_op_s : mgcr::Op {};
+struct mgcr_mvec_s : mgcr::MVec {};

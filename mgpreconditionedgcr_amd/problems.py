@@ -100,3 +100,23 @@ def skewed_csr(nrow, rng, window=1 << 17, long_rows=0, long_len=2000):
     val.real = rng.uniform(-1, 1, nnz)
     val.imag = rng.uniform(-1, 1, nnz)
     return rowptr, col, val
+
+
+def unstructured_blocks(nb, bs, seed=5):
+    """Unstructured HierarchicalSparse of the benchmark's block-CSR workload (BASELINE configs[4]): skewed blocks per block
+    row (80 % of the block rows 5-9 blocks, 20 % 10-64), random block columns, diagonally dominant.  Returns unsorted
+    (block rows, block columns, blocks[nblk][bs][bs]) triplets."""
+    rng = np.random.default_rng(seed)
+    per_row = np.where(rng.random(nb) < 0.8, rng.integers(5, 10, nb), rng.integers(10, 65, nb))
+    rows = np.repeat(np.arange(nb, dtype=np.int32), per_row)
+    cols = rng.integers(0, nb, rows.size).astype(np.int32)
+    first = np.concatenate([[0], np.cumsum(per_row)[:-1]])
+    cols[first] = np.arange(nb, dtype=np.int32)
+    nblk = rows.size
+    blocks = np.empty((nblk, bs, bs), np.complex128)
+    for s in range(0, nblk, 20000):
+        e = min(nblk, s + 20000)
+        blocks[s:e] = (rng.uniform(-1, 1, (e - s, bs, bs)) + 1j * rng.uniform(-1, 1, (e - s, bs, bs))) * (0.5 / bs)
+    offsum = np.bincount(rows, weights=np.abs(blocks).sum(axis=(1, 2)) / bs, minlength=nb)
+    blocks[first] = np.eye(bs)[None] * (1.0 + offsum)[:, None, None]
+    return rows, cols, blocks
