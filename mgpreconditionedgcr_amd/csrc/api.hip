@@ -194,7 +194,11 @@ int mgcr_set_option(const char *name, int value, int *previous) {
     else if (!strcmp(name, "resident_solver")) prev = set_resident_enabled(value != 0);
     else if (!strcmp(name, "step_build")) prev = set_stepbuild_enabled(value != 0);
     else if (!strcmp(name, "start_build")) prev = set_start_build_enabled(value != 0);
-    else if (!strcmp(name, "step_build_keep_r")) prev = set_stepbuild_keepr_enabled(value != 0);
+    else if (!strcmp(name, "step_build_keep_r")) {   // accepted, without effect: step_keep_kernel took over those steps
+        static bool last = true;
+        prev = last;
+        last = value != 0;
+    }
     else if (!strcmp(name, "step_build_keep_all")) prev = set_stepbuild_keep_all_enabled(value != 0);
     else if (!strcmp(name, "halo_split")) prev = set_halo_split(value != 0);
     else if (!strcmp(name, "pw_tail")) prev = set_pw_tail_enabled(value != 0);

@@ -51,6 +51,32 @@ struct ResSync {
     double *ws;          // [RES_NV][RES_GRP]  sums over 64 workgroups each of the exchange being collected
     int *gave_up;        // LDS flag
 };
+// pw, ws, gave_up: the workgroup's LDS (nobody reads *gave_up before the barrier of its first exchange)
+__device__ __forceinline__ void res_sync_init(ResSync &s, const v4i *slots, unsigned gen0, int nblk, int lb, unsigned *abort_dev, int spin_limit,
+                                              double *pw, double *ws, int *gave_up) {
+    s.slots = res_rsrc(slots, (unsigned)RES_SLOT_BYTES);
+    s.gen = gen0;
+    s.nblk = nblk;
+    s.lb = lb;
+    s.abort_dev = abort_dev;
+    s.spin_limit = spin_limit;
+    s.pw = pw;
+    s.ws = ws;
+    s.gave_up = gave_up;
+    if (threadIdx.x == 0) *gave_up = 0;
+}
+// this workgroup's sum of scalar k of the exchange `kind`: {value, generation} into its slot
+__device__ __forceinline__ void res_post(const ResSync &s, int kind, int k, double value) {
+    const v4i w4 = {__double2loint(value), __double2hiint(value), (int)s.gen, 0};
+    __builtin_amdgcn_raw_buffer_store_b128(w4, s.slots, ((kind * RES_NV + k) * RES_BLK + s.lb) * 16, 0, RES_SC1);
+}
+// giving up: the other workgroups' polls (abort_dev) and the host (abort_host, host-mapped) learn of it
+__device__ __forceinline__ void res_abort(unsigned *abort_dev, int *abort_host) {
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(abort_host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
 
 // An exchange = contribute (every wave: its 64 rows' terms -> LDS), publish (one barrier; thread k adds the 16 wave
 // sums of scalar k in wave order — reduce.h block_sum_owner — and stores {sum, generation} into this workgroup's
@@ -75,8 +101,7 @@ __device__ __forceinline__ void res_publish(ResSync &s, int kind) {
         double t = 0.;
 #pragma unroll
         for (int w = 0; w < RED_THREADS / 64; w++) t += s.pw[threadIdx.x * 17 + w];   // 16 sets of 64 rows, whatever the thread count
-        const v4i w4 = {__double2loint(t), __double2hiint(t), (int)s.gen, 0};
-        __builtin_amdgcn_raw_buffer_store_b128(w4, s.slots, ((kind * RES_NV + (int)threadIdx.x) * RES_BLK + s.lb) * 16, 0, RES_SC1);
+        res_post(s, kind, (int)threadIdx.x, t);
     }
 }
 // Collect in two hops, so that no slot is read by more than a few workgroups at a time (256 workgroups polling the same

@@ -480,17 +480,6 @@ __global__ void __launch_bounds__(RED_THREADS) build_kernel(DevState *__restrict
     }
 }
 
-// step bookkeeping shared by the build kernels (src/GCR.h:270-274,288)
-__device__ __forceinline__ void close_step(DevState *st, int it, double rr, double *hist, int hist_cap, bool clear_pending) {
-    const int git = st->base + it;  // global_count
-    st->iter = git;
-    st->rr = rr;
-    if (git < hist_cap) hist[git] = sqrt(rr) / sqrt(st->bnorm2);
-    // continue while |r|^2/|b|^2 > tol^2 (src/GCR.h:288); NaN compares false -> stop, like the reference
-    if (!((rr / st->bnorm2) > st->tol2)) st->stop_at = git;
-    if (clear_pending) st->npend = 0;
-}
-
 // The last step of a nested solve whose caller only wants x (V-cycle post-smoother, coarsest solve): alpha and the
 // pending-x bookkeeping of xr_update_kernel<true, true>, without its pass over r and Ap — nobody reads that residual.
 __global__ void __launch_bounds__(RED_THREADS) alpha_only_kernel(DevState *st, int it, const double *__restrict__ partsA, int nblkA,
@@ -561,23 +550,7 @@ __global__ void __launch_bounds__(RED_THREADS, (NDT <= 5 ? 8 : 4)) build_lean_ke
     // closing (restart > 8: the cycle-closing step is close_x_kernel + this kernel with NDT = restart, writing
     // Ap_0' over slot 0 in place): no table row — the next cycle starts a new table
     if constexpr (NDT < LND)   // NDT == LND only ever runs as the closing step of a restart-16 cycle
-    if (!closing && blockIdx.x == 0 && (int)threadIdx.x <= NDT) {
-        // one thread per column of the new table row (thread 0: t_k, thread k: the unit diagonal), so that the
-        // loads of a column are independent and the whole row costs one memory round trip, not k^2 / 2 of them —
-        // this sits on the critical path of the short kernels of small systems
-        constexpr int k = NDT;
-        const int m = threadIdx.x;
-        cplx a = make_double2(0., 0.);
-        if (m == 0) {
-            for (int j = 0; j < k; j++) a = csub(a, cmul(sbeta[j], j == 0 ? make_double2(1., 0.) : lc->t[j]));
-            lc->t[k] = a;
-        } else if (m < k) {
-            for (int j = m; j < k; j++) a = csub(a, cmul(sbeta[j], j == m ? make_double2(1., 0.) : lc->T[j * LND + m]));
-            lc->T[k * LND + m] = a;
-        } else {
-            lc->T[k * LND + k] = make_double2(1., 0.);
-        }
-    }
+    if (!closing && blockIdx.x == 0 && (int)threadIdx.x <= NDT) lean_table_row<NDT>(lc, sbeta, (int)threadIdx.x);   // row k = NDT
     cplx beta[NDT];
 #pragma unroll
     for (int j = 0; j < NDT; j++) beta[j] = to_sgpr(sbeta[j]);
@@ -627,13 +600,7 @@ __global__ void __launch_bounds__(RED_THREADS / 2) close_x_kernel(DevState *__re
     __syncthreads();
     if (threadIdx.x < NDT) {
         const int m = threadIdx.x;
-        cplx a = make_double2(0., 0.);
-        if (m == 0) {
-            for (int j = 0; j < NDT; j++) a = cadd(a, cmul(sbeta[j], j == 0 ? make_double2(1., 0.) : lc->t[j]));
-        } else {
-            for (int j = m; j < NDT; j++) a = cadd(a, cmul(sbeta[j], j == m ? make_double2(1., 0.) : lc->T[j * LND + m]));
-        }
-        scp[m] = a;
+        scp[m] = lean_close_coef(lc, sbeta, NDT, m);
         scx[m] = lc->cx[m];
     }
     __syncthreads();
@@ -690,13 +657,7 @@ __global__ void __launch_bounds__(RED_THREADS, (NDT <= 2 ? 8 : 4)) build_close_k
     __syncthreads();
     if (threadIdx.x < NDT) {
         const int m = threadIdx.x;
-        cplx a = make_double2(0., 0.);
-        if (m == 0) {
-            for (int j = 0; j < NDT; j++) a = cadd(a, cmul(sbeta[j], j == 0 ? make_double2(1., 0.) : lc->t[j]));
-        } else {
-            for (int j = m; j < NDT; j++) a = cadd(a, cmul(sbeta[j], j == m ? make_double2(1., 0.) : lc->T[j * LND + m]));
-        }
-        scp[m] = a;
+        scp[m] = lean_close_coef(lc, sbeta, NDT, m);
     }
     __syncthreads();
     cplx beta[NDT], cp[NDT], cx[NDT];

@@ -197,6 +197,51 @@ __device__ __forceinline__ void lean_pending_update(LeanCoef *lc, int slot, cplx
     }
 }
 
+// The scalar stage of a lean step, between "the sums over all rows have arrived" and "stream the rows": ONE copy for the
+// three-kernel path (gcr.hip), the one-launch steps (gcr_stepbuild.hip) and the multi-RHS solve (gcr_multi.hip), which must all
+// produce the same bits.
+
+// step bookkeeping (src/GCR.h:270-274,288)
+__device__ __forceinline__ void close_step(DevState *st, int it, double rr, double *hist, int hist_cap, bool clear_pending) {
+    const int git = st->base + it;  // global_count
+    st->iter = git;
+    st->rr = rr;
+    if (git < hist_cap) hist[git] = sqrt(rr) / sqrt(st->bnorm2);
+    // continue while |r|^2/|b|^2 > tol^2 (src/GCR.h:288); NaN compares false -> stop, like the reference
+    if (!((rr / st->bnorm2) > st->tol2)) st->stop_at = git;
+    if (clear_pending) st->npend = 0;
+}
+
+// Row k of the coefficient table, p_k = D_k - sum_{j<k} beta_j p_j:  t_k = -sum_j beta_j t_j,  T_km = -sum_{j>=m} beta_j T_jm,
+// T_kk = 1.  One thread per column m <= k (thread 0: t_k, thread k: the unit diagonal), so that the loads of a column are
+// independent and the whole row costs one memory round trip, not k^2 / 2 of them — this sits on the critical path of the short
+// kernels of small systems.
+// (k is a template argument: passed as a plain int and folded by inlining, the one-launch steps' register counts change)
+template <int k>
+__device__ __forceinline__ void lean_table_row(LeanCoef *lc, const cplx *sbeta, int m) {
+    cplx c = make_double2(0., 0.);
+    if (m == 0) {
+        for (int j = 0; j < k; j++) c = csub(c, cmul(sbeta[j], j == 0 ? make_double2(1., 0.) : lc->t[j]));
+        lc->t[k] = c;
+    } else if (m < k) {
+        for (int j = m; j < k; j++) c = csub(c, cmul(sbeta[j], j == m ? make_double2(1., 0.) : lc->T[j * LND + m]));
+        lc->T[k * LND + m] = c;
+    } else {
+        lc->T[k * LND + k] = make_double2(1., 0.);
+    }
+}
+
+// the closing step's coefficient of P0 (m = 0) / D_m:  cp_m = sum_{j>=m} beta_j T_jm  (cp_0 = sum_j beta_j t_j), m < nd
+__device__ __forceinline__ cplx lean_close_coef(const LeanCoef *lc, const cplx *sbeta, int nd, int m) {
+    cplx c = make_double2(0., 0.);
+    if (m == 0) {
+        for (int j = 0; j < nd; j++) c = cadd(c, cmul(sbeta[j], j == 0 ? make_double2(1., 0.) : lc->t[j]));
+    } else {
+        for (int j = m; j < nd; j++) c = cadd(c, cmul(sbeta[j], j == m ? make_double2(1., 0.) : lc->T[j * LND + m]));
+    }
+    return c;
+}
+
 // gcr_resident.hip: a lean restarted solve on a small stencil-view operator in one launch
 bool gcr_resident_eligible(const Op *A, const mgcr_gcr_param &p, int storage, int restart, int64_t n, bool lean, bool nested_handoff);
 int gcr_resident_run(Op *A, const mgcr_gcr_param &p, int storage, int restart, const cplx *rhs, cplx *x, bool from_zero, bool alpha_only_last,

@@ -156,16 +156,6 @@ __global__ void __launch_bounds__(RED_THREADS) m_xr_kernel(const DevState *__res
     if (t < KC && m_active(st, c0 + t, k, it)) partsR[(size_t)(c0 + t) * RED_MAX_BLOCKS + blockIdx.x] = tot;
 }
 
-// step bookkeeping shared by the scalar kernels (close_step of gcr.hip)
-__device__ __forceinline__ void m_close_step(DevState *st, int it, double rr, double *hist, int hist_cap, bool clear_pending) {
-    const int git = st->base + it;
-    st->iter = git;
-    st->rr = rr;
-    if (git < hist_cap) hist[git] = sqrt(rr) / sqrt(st->bnorm2);
-    if (!((rr / st->bnorm2) > st->tol2)) st->stop_at = git;
-    if (clear_pending) st->npend = 0;
-}
-
 // the last step a solve can run: bookkeeping only (finish_step_kernel)
 __global__ void __launch_bounds__(RED_THREADS) m_finish_kernel(DevState *st, int it, const double *__restrict__ partsR, int nblk,
                                                                double *__restrict__ hist, int hist_cap) {
@@ -174,7 +164,7 @@ __global__ void __launch_bounds__(RED_THREADS) m_finish_kernel(DevState *st, int
     if (st[j].stop_at < st[j].base + it) return;
     double rr[1];
     fold_partials<1>(partsR + (size_t)j * RED_MAX_BLOCKS, nblk, RED_MAX_BLOCKS, rr, lds);
-    if (threadIdx.x == 0) m_close_step(st + j, it, rr[0], hist + (size_t)j * hist_cap, hist_cap, false);
+    if (threadIdx.x == 0) close_step(st + j, it, rr[0], hist + (size_t)j * hist_cap, hist_cap, false);
 }
 
 // <Ar, Ap_d> (conj on Ar) for the NDT directions of chunk blockIdx.z and the KC columns of group blockIdx.y; rows dealt by the
@@ -231,7 +221,7 @@ __global__ void __launch_bounds__(RED_THREADS) m_coef_kernel(DevState *st, int i
     }
     double rr[1];
     fold_partials<1>(partsR + (size_t)j * RED_MAX_BLOCKS, nblk, RED_MAX_BLOCKS, rr, lds);
-    if (threadIdx.x == 0) m_close_step(st + j, it, rr[0], hist + (size_t)j * hist_cap, hist_cap, closing != 0);
+    if (threadIdx.x == 0) close_step(st + j, it, rr[0], hist + (size_t)j * hist_cap, hist_cap, closing != 0);
     __syncthreads();
     const int m = threadIdx.x;
     if (m < lim) coef->beta[j][m] = sbeta[m];
@@ -250,13 +240,7 @@ __global__ void __launch_bounds__(RED_THREADS) m_coef_kernel(DevState *st, int i
             }
         }
     } else if (m < lim) {              // cp (build_close_kernel / close_x_kernel)
-        cplx a = make_double2(0., 0.);
-        if (m == 0) {
-            for (int q = 0; q < lim; q++) a = cadd(a, cmul(sbeta[q], q == 0 ? make_double2(1., 0.) : lc->t[q]));
-        } else {
-            for (int q = m; q < lim; q++) a = cadd(a, cmul(sbeta[q], q == m ? make_double2(1., 0.) : lc->T[q * LND + m]));
-        }
-        coef->cp[j][m] = a;
+        coef->cp[j][m] = lean_close_coef(lc, sbeta, lim, m);
     }
 }
 

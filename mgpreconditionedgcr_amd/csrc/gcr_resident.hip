@@ -463,16 +463,7 @@ __global__ void __launch_bounds__(RED_THREADS / RPT, RED_THREADS / RPT / 256) gc
     const __amdgpu_buffer_rsrc_t ring = res_rsrc(a.ring, (unsigned)(R + 1) * (unsigned)vbytes);
     const int nwave = T / 64, wave = (int)threadIdx.x >> 6;
     ResSync sy;
-    sy.slots = res_rsrc(a.slots, (unsigned)RES_SLOT_BYTES);
-    sy.gen = a.gen0;
-    sy.nblk = a.nlogical;
-    sy.lb = lb;
-    sy.abort_dev = a.abort_dev;
-    sy.spin_limit = a.spin_limit;
-    sy.pw = lds_pw;
-    sy.ws = lds_ws;
-    sy.gave_up = &gave_up;
-    if (threadIdx.x == 0) gave_up = 0;
+    res_sync_init(sy, a.slots, a.gen0, a.nlogical, lb, a.abort_dev, a.spin_limit, lds_pw, lds_ws, &gave_up);
     __syncthreads();
     ResState<R, RPT> S;
 #pragma unroll
@@ -527,10 +518,7 @@ __global__ void __launch_bounds__(RED_THREADS / RPT, RED_THREADS / RPT / 256) gc
         while (res_cycle<MODE, NS, R, RPT, 0>(a, S, tb, sy, ring, owner0)) {}
     __syncthreads();
     if (S.aborted) {
-        if (threadIdx.x == 0) {
-            __hip_atomic_store(a.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.abort_host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        res_abort(a.abort_dev, a.abort_host);
 #pragma unroll
         for (int h = 0; h < RPT; h++)
             if (S.act[h]) a.x[S.row[h]] = make_double2(__builtin_nan(""), __builtin_nan(""));
@@ -789,16 +777,7 @@ __global__ void __launch_bounds__(RED_THREADS) coherence_selftest_kernel(CohArgs
     __shared__ double lds_pw[RES_NV * 17], lds_ws[RES_NV * RES_GRP];
     __shared__ int gave_up;
     ResSync sy;
-    sy.slots = res_rsrc(a.slots, (unsigned)RES_SLOT_BYTES);
-    sy.gen = a.gen0;
-    sy.nblk = a.nblk;
-    sy.lb = (int)blockIdx.x;
-    sy.abort_dev = a.abort_dev;
-    sy.spin_limit = a.spin_limit;
-    sy.pw = lds_pw;
-    sy.ws = lds_ws;
-    sy.gave_up = &gave_up;
-    if (threadIdx.x == 0) gave_up = 0;
+    res_sync_init(sy, a.slots, a.gen0, a.nblk, (int)blockIdx.x, a.abort_dev, a.spin_limit, lds_pw, lds_ws, &gave_up);
     __syncthreads();
     const int i = (int)blockIdx.x * RED_THREADS + (int)threadIdx.x;
     const __amdgpu_buffer_rsrc_t ra = res_rsrc(a.a, (unsigned)a.n * 16u), rb = res_rsrc(a.b, (unsigned)a.n * 16u);

@@ -14,6 +14,10 @@
 // less.  The first trip's streams of the build and the update's first r are requested before an exchange is polled.
 // Everything else is the kernels' code: the same rows per thread (RowMap), the same per-thread accumulation order, the
 // same fold tree — the same bits (tests/test_gpu_stepbuild.py compares with the three-kernel path bit for bit).
+// The scalar stage between "the sums have arrived" and "stream the rows" (step bookkeeping, the coefficient table's row, the
+// closing coefficients) IS the three-kernel path's: gcr_dev.h; the exchange scaffolding is exchange_dev.h's.
+// Up to 3 stored directions (the closing step with XR at 3 excepted) step_keep_kernel runs the step, reading r once; beyond
+// that, and as the reference side of tests/test_gpu_stepbuild_keep_all.py, step_build_kernel.
 //
 // Needs all workgroups co-resident (they wait for each other): 64 VGPRs and <= 80 KB of LDS each, at most 2 x #CU
 // workgroups, no other process on the device (no live communicator).  Up to 5 stored directions (beyond that the
@@ -71,23 +75,23 @@ struct StepBuildArgs {
     int test_stall;          // tests: logical workgroup test_stall - 1 leaves before publishing anything (0: nobody)
 };
 
-// step bookkeeping (gcr.hip close_step; kept in step with it by tests/test_gpu_stepbuild.py)
-__device__ __forceinline__ void sb_close_step(DevState *st, int it, double rr, double *hist, int hist_cap, bool clear_pending) {
-    const int git = st->base + it;
-    st->iter = git;
-    st->rr = rr;
-    if (git < hist_cap) hist[git] = sqrt(rr) / sqrt(st->bnorm2);
-    if (!((rr / st->bnorm2) > st->tol2)) st->stop_at = git;
-    if (clear_pending) st->npend = 0;
+// The scalar part of a residual update (gcr.hip xr_update_kernel<true, true>) behind its exchange: alpha = <r,Ap'> / <Ap',Ap'>
+// in scalar registers; logical workgroup 0 records the denominator and the pending x update.
+__device__ __forceinline__ cplx sb_xr_alpha(const ResSync &sy, DevState *st, LeanCoef *lc, cplx *xr_den_slot, int xr_slot, int lb) {
+    const cplx num = make_double2(res_total(sy, 0), res_total(sy, 1)), den = make_double2(res_total(sy, 2), res_total(sy, 3));
+    const cplx alpha = to_sgpr(cdiv(num, den));
+    if (lb == 0 && threadIdx.x == 0) {
+        *xr_den_slot = den;
+        st->npend = xr_slot + 1;
+    }
+    if (lb == 0 && (int)threadIdx.x < LND) lean_pending_update(lc, xr_slot, alpha, (int)threadIdx.x);
+    return alpha;
 }
 
 // REALC: the instantiation for real stencil coefficients (no per-slot real / complex decision, 14 scalar registers less — the
 // kernels' scalar registers spill into vector-register lanes, which a wave then reads back one v_readlane at a time)
-// KEEPR (in-cycle steps with XR): the thread's residual rows, read once by the build, stay in registers (SB_MAX_TRIPS x 16 B)
-// until the update after the second exchange: one read of r per step less, and nothing but LDS left to wait for after that poll
-template <int MODE, int WT, int NDT, bool XR, bool CLOSE, bool REALC = false, bool KEEPR = false>
+template <int MODE, int WT, int NDT, bool XR, bool CLOSE, bool REALC = false>
 __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArgs a) {
-    static_assert(!KEEPR || (XR && !CLOSE), "KEEPR: the in-cycle step that ends with the next residual update");
     __shared__ double lds[(2 * NDT > 4 ? 2 * NDT : 4) * 17];
     __shared__ double lds_pw[2 * SB_MAX_ND * 17], lds_ws[2 * SB_MAX_ND * RES_GRP];
     __shared__ int gave_up;
@@ -98,16 +102,7 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
     if (lb >= a.nlogical) return;
     cplx *arL = reinterpret_cast<cplx *>(sb_smem);
     ResSync sy;
-    sy.slots = res_rsrc(a.slots, (unsigned)RES_SLOT_BYTES);
-    sy.gen = a.gen0;
-    sy.nblk = a.nlogical;
-    sy.lb = lb;
-    sy.abort_dev = a.abort_dev;
-    sy.spin_limit = a.spin_limit;
-    sy.pw = lds_pw;
-    sy.ws = lds_ws;
-    sy.gave_up = &gave_up;
-    if (threadIdx.x == 0) gave_up = 0;
+    res_sync_init(sy, a.slots, a.gen0, a.nlogical, lb, a.abort_dev, a.spin_limit, lds_pw, lds_ws, &gave_up);
     if (a.test_stall && lb == a.test_stall - 1) return;   // (tests) the others must notice, give up and say so
     int64_t i0, end, stride;
     row_range(a.rm, lb, a.nlogical, a.n, &i0, &end, &stride);
@@ -155,10 +150,7 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
     }
     const bool ok = res_collect<2 * NDT>(sy, 1);
     if (!ok) {   // somebody is missing: leave, with results nobody can mistake for numbers
-        if (threadIdx.x == 0) {
-            __hip_atomic_store(a.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.abort_host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        res_abort(a.abort_dev, a.abort_host);
         for (int64_t i = i0; i < end; i += stride) a.ap_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
         if ((int)threadIdx.x < 4) a.partsA[threadIdx.x * RED_MAX_BLOCKS + lb] = __builtin_nan("");
         return;
@@ -169,7 +161,7 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
         double rr[1];
         fold_partials<1>(a.partsR, a.nblkR, a.strideR, rr, lds);
         if (lb == 0 && threadIdx.x == 0) {
-            sb_close_step(a.st, a.it, rr[0], a.hist, a.hist_cap, CLOSE);
+            close_step(a.st, a.it, rr[0], a.hist, a.hist_cap, CLOSE);
             if (CLOSE) a.st->closed = 1;   // (P0' is written below, by every workgroup that reaches the close pass)
         }
         ends_here = !((rr[0] / a.st->bnorm2) > a.st->tol2);
@@ -177,34 +169,10 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
     if ((int)threadIdx.x < NDT) sbeta[threadIdx.x] = cdiv(make_double2(res_total(sy, 2 * threadIdx.x), res_total(sy, 2 * threadIdx.x + 1)), a.den[threadIdx.x]);
     __syncthreads();
     if constexpr (CLOSE) {   // gcr.hip build_close_kernel: cp_m = sum_{j >= m} beta_j T_jm (cp_0 = sum_j beta_j t_j), in every workgroup
-        if ((int)threadIdx.x < NDT) {
-            const int m = threadIdx.x;
-            const LeanCoef *lc = a.lc;
-            cplx c = make_double2(0., 0.);
-            if (m == 0) {
-                for (int j = 0; j < NDT; j++) c = cadd(c, cmul(sbeta[j], j == 0 ? make_double2(1., 0.) : lc->t[j]));
-            } else {
-                for (int j = m; j < NDT; j++) c = cadd(c, cmul(sbeta[j], j == m ? make_double2(1., 0.) : lc->T[j * LND + m]));
-            }
-            scp[m] = c;
-        }
+        if ((int)threadIdx.x < NDT) scp[threadIdx.x] = lean_close_coef(a.lc, sbeta, NDT, (int)threadIdx.x);
         __syncthreads();
     }
-    if (!CLOSE && lb == 0 && (int)threadIdx.x <= NDT) {   // row k = NDT of the coefficient table
-        constexpr int k = NDT;
-        const int m = threadIdx.x;
-        LeanCoef *lc = a.lc;
-        cplx c = make_double2(0., 0.);
-        if (m == 0) {
-            for (int j = 0; j < k; j++) c = csub(c, cmul(sbeta[j], j == 0 ? make_double2(1., 0.) : lc->t[j]));
-            lc->t[k] = c;
-        } else if (m < k) {
-            for (int j = m; j < k; j++) c = csub(c, cmul(sbeta[j], j == m ? make_double2(1., 0.) : lc->T[j * LND + m]));
-            lc->T[k * LND + m] = c;
-        } else {
-            lc->T[k * LND + k] = make_double2(1., 0.);
-        }
-    }
+    if (!CLOSE && lb == 0 && (int)threadIdx.x <= NDT) lean_table_row<NDT>(a.lc, sbeta, (int)threadIdx.x);   // row k = NDT of the table
     cplx beta[NDT];
 #pragma unroll
     for (int j = 0; j < NDT; j++) beta[j] = to_sgpr(sbeta[j]);
@@ -235,7 +203,8 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    cplx rk[KEEPR ? SB_MAX_TRIPS : 1];   // KEEPR: r of the thread's rows, for the update after the second exchange
+    // (kept as a lambda that returns the row's r: written as the loop's body, the same statements change the registers of thirty
+    // instantiations — profiles/scalar_stage_refactor_resource_usage.md)
     auto build_row = [&](int64_t i, int trip) -> cplx {
         cplx aj[NDT];
 #pragma unroll
@@ -253,16 +222,7 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
         v[2] += u.x; v[3] += u.y;
         return rv;
     };
-    if constexpr (KEEPR) {   // the same rows in the same order, with trip numbers known at compile time (register indices)
-#pragma unroll
-        for (int t = 0; t < SB_MAX_TRIPS; t++) {
-            const int64_t i = i0 + (int64_t)t * stride;
-            if (i < end) rk[t] = build_row(i, t);
-            __builtin_amdgcn_sched_barrier(0);   // (one trip's streams in registers at a time, as in the loop below)
-        }
-    } else {
-        for (int64_t i = i0; i < end; i += stride, trip++) (void)build_row(i, trip);
-    }
+    for (int64_t i = i0; i < end; i += stride, trip++) (void)build_row(i, trip);
     const double mine = block_sum_owner<4>(v, lds);
     if (threadIdx.x < 4) a.partsA[threadIdx.x * RED_MAX_BLOCKS + lb] = mine;
     if constexpr (XR) {
@@ -272,42 +232,21 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
             const v4i w4 = {__double2loint(mine), __double2hiint(mine), (int)sy.gen, 0};
             __builtin_amdgcn_raw_buffer_store_b128(w4, sy.slots, ((2 * RES_NV + (int)threadIdx.x) * RES_BLK + lb) * 16, 0, RES_SC1);
         }
-        const cplx xr0 = (!KEEPR && i0 < end) ? a.x[i0] : make_double2(0., 0.);   // (requested before the polls, like `pre` above)
+        const cplx xr0 = i0 < end ? a.x[i0] : make_double2(0., 0.);   // (requested before the polls, like `pre` above)
         if (!res_collect<4>(sy, 2)) {
-            if (threadIdx.x == 0) {
-                __hip_atomic_store(a.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(a.abort_host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            res_abort(a.abort_dev, a.abort_host);
             for (int64_t i = i0; i < end; i += stride) a.xr_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
             if (threadIdx.x == 0) a.partsR_out[lb] = __builtin_nan("");
             return;
         }
         if (ends_here) return;   // the step converged: the next one's kernels are no-ops (gcr_dev.h DevState::stop_at)
-        const cplx num = make_double2(res_total(sy, 0), res_total(sy, 1)), den = make_double2(res_total(sy, 2), res_total(sy, 3));
-        const cplx alpha = to_sgpr(cdiv(num, den));
-        if (lb == 0 && threadIdx.x == 0) {
-            *a.xr_den_slot = den;
-            a.st->npend = a.xr_slot + 1;
-        }
-        if (lb == 0 && (int)threadIdx.x < LND) lean_pending_update(a.lc, a.xr_slot, alpha, (int)threadIdx.x);
+        const cplx alpha = sb_xr_alpha(sy, a.st, a.lc, a.xr_den_slot, a.xr_slot, lb);
         double vr[1] = {0.};
-        if constexpr (KEEPR) {
-#pragma unroll
-            for (int t = 0; t < SB_MAX_TRIPS; t++) {
-                const int64_t i = i0 + (int64_t)t * stride;
-                if (i < end) {
-                    const cplx rn = csub(rk[t], cmul(alpha, arL[t * RED_THREADS + (int)threadIdx.x]));
-                    a.xr_out[i] = rn;
-                    vr[0] += rn.x * rn.x + rn.y * rn.y;
-                }
-            }
-        } else {
-            trip = 0;
-            for (int64_t i = i0; i < end; i += stride, trip++) {
-                const cplx rn = csub(i == i0 ? xr0 : a.x[i], cmul(alpha, arL[trip * RED_THREADS + (int)threadIdx.x]));
-                a.xr_out[i] = rn;
-                vr[0] += rn.x * rn.x + rn.y * rn.y;
-            }
+        trip = 0;
+        for (int64_t i = i0; i < end; i += stride, trip++) {
+            const cplx rn = csub(i == i0 ? xr0 : a.x[i], cmul(alpha, arL[trip * RED_THREADS + (int)threadIdx.x]));
+            a.xr_out[i] = rn;
+            vr[0] += rn.x * rn.x + rn.y * rn.y;
         }
         const double tot = block_sum_owner<1>(vr, lds);
         if (threadIdx.x == 0) a.partsR_out[lb] = tot;
@@ -365,16 +304,7 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs
     cplx *arL = reinterpret_cast<cplx *>(sb_smem);
     const int tid = (int)threadIdx.x;
     ResSync sy;
-    sy.slots = res_rsrc(a.slots, (unsigned)RES_SLOT_BYTES);
-    sy.gen = a.gen0;
-    sy.nblk = a.nlogical;
-    sy.lb = lb;
-    sy.abort_dev = a.abort_dev;
-    sy.spin_limit = a.spin_limit;
-    sy.pw = lds_pw;
-    sy.ws = lds_ws;
-    sy.gave_up = &gave_up;
-    if (threadIdx.x == 0) gave_up = 0;
+    res_sync_init(sy, a.slots, a.gen0, a.nlogical, lb, a.abort_dev, a.spin_limit, lds_pw, lds_ws, &gave_up);
     if (a.test_stall && lb == a.test_stall - 1) return;
     int64_t i0, end, stride;
     row_range(a.rm, lb, a.nlogical, a.n, &i0, &end, &stride);
@@ -433,10 +363,7 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs
 #pragma unroll
     for (int u = 0; u < SB_KEEP_TB; u++) pre[u] = row(u) < end ? ld_stream<NTS>(at(a.aps[0], u)) : make_double2(0., 0.);
     if (!res_collect<2 * NDT>(sy, 1)) {
-        if (threadIdx.x == 0) {
-            __hip_atomic_store(a.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.abort_host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        res_abort(a.abort_dev, a.abort_host);
         for (int64_t i = i0; i < end; i += stride) a.ap_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
         if (tid < 4) a.partsA[tid * RED_MAX_BLOCKS + lb] = __builtin_nan("");
         return;
@@ -447,7 +374,7 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs
         double rr[1];
         fold_partials<1>(a.partsR, a.nblkR, a.strideR, rr, lds);
         if (lb == 0 && threadIdx.x == 0) {
-            sb_close_step(a.st, a.it, rr[0], a.hist, a.hist_cap, CLOSE);
+            close_step(a.st, a.it, rr[0], a.hist, a.hist_cap, CLOSE);
             if (CLOSE) a.st->closed = 1;
         }
         ends_here = __builtin_amdgcn_readfirstlane(!((rr[0] / a.st->bnorm2) > a.st->tol2)) != 0;   // (decided here: not sunk to XR)
@@ -456,34 +383,12 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs
     __syncthreads();
     if constexpr (CLOSE) {
         if (tid < NDT) {
-            const int m = tid;
-            const LeanCoef *lc = a.lc;
-            cplx c = make_double2(0., 0.);
-            if (m == 0) {
-                for (int j = 0; j < NDT; j++) c = cadd(c, cmul(sbeta[j], j == 0 ? make_double2(1., 0.) : lc->t[j]));
-            } else {
-                for (int j = m; j < NDT; j++) c = cadd(c, cmul(sbeta[j], j == m ? make_double2(1., 0.) : lc->T[j * LND + m]));
-            }
-            scp[m] = c;
-            scx[m] = lc->cx[m];
+            scp[tid] = lean_close_coef(a.lc, sbeta, NDT, tid);
+            scx[tid] = a.lc->cx[tid];
         }
         __syncthreads();
     }
-    if (!CLOSE && lb == 0 && tid <= NDT) {
-        constexpr int k = NDT;
-        const int m = tid;
-        LeanCoef *lc = a.lc;
-        cplx c = make_double2(0., 0.);
-        if (m == 0) {
-            for (int j = 0; j < k; j++) c = csub(c, cmul(sbeta[j], j == 0 ? make_double2(1., 0.) : lc->t[j]));
-            lc->t[k] = c;
-        } else if (m < k) {
-            for (int j = m; j < k; j++) c = csub(c, cmul(sbeta[j], j == m ? make_double2(1., 0.) : lc->T[j * LND + m]));
-            lc->T[k * LND + m] = c;
-        } else {
-            lc->T[k * LND + k] = make_double2(1., 0.);
-        }
-    }
+    if (!CLOSE && lb == 0 && tid <= NDT) lean_table_row<NDT>(a.lc, sbeta, tid);
     {
         cplx beta[NDT];   // (in scalar registers once: read from LDS per batch, the compiler keeps them in vector registers)
 #pragma unroll
@@ -566,22 +471,13 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs
     }
     if constexpr (XR) {
         if (!res_collect<4>(sy, 2)) {
-            if (threadIdx.x == 0) {
-                __hip_atomic_store(a.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(a.abort_host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            res_abort(a.abort_dev, a.abort_host);
             for (int64_t i = i0; i < end; i += stride) a.xr_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
             if (threadIdx.x == 0) a.partsR_out[lb] = __builtin_nan("");
             return;
         }
         if (ends_here) return;
-        const cplx num = make_double2(res_total(sy, 0), res_total(sy, 1)), den = make_double2(res_total(sy, 2), res_total(sy, 3));
-        const cplx alpha = to_sgpr(cdiv(num, den));
-        if (lb == 0 && threadIdx.x == 0) {
-            *a.xr_den_slot = den;
-            a.st->npend = a.xr_slot + 1;
-        }
-        if (lb == 0 && tid < LND) lean_pending_update(a.lc, a.xr_slot, alpha, tid);
+        const cplx alpha = sb_xr_alpha(sy, a.st, a.lc, a.xr_den_slot, a.xr_slot, lb);
         double vr[1] = {0.};
 #pragma unroll
         for (int t = 0; t < SB_MAX_TRIPS; t++) {
@@ -637,16 +533,7 @@ __global__ void __launch_bounds__(RED_THREADS, 8) start_build_kernel(StartArgs a
     if (lb >= a.nlogical) return;
     cplx *apL = reinterpret_cast<cplx *>(sb_smem);
     ResSync sy;
-    sy.slots = res_rsrc(a.slots, (unsigned)RES_SLOT_BYTES);
-    sy.gen = a.gen0;
-    sy.nblk = a.nlogical;
-    sy.lb = lb;
-    sy.abort_dev = a.abort_dev;
-    sy.spin_limit = a.spin_limit;
-    sy.pw = lds_pw;
-    sy.ws = lds_ws;
-    sy.gave_up = &gave_up;
-    if (threadIdx.x == 0) gave_up = 0;
+    res_sync_init(sy, a.slots, a.gen0, a.nlogical, lb, a.abort_dev, a.spin_limit, lds_pw, lds_ws, &gave_up);
     if (a.test_stall && lb == a.test_stall - 1) return;
     int64_t i0, end, stride;
     row_range(a.rm, lb, a.nlogical, a.n, &i0, &end, &stride);
@@ -681,26 +568,19 @@ __global__ void __launch_bounds__(RED_THREADS, 8) start_build_kernel(StartArgs a
     }
     const cplx b0 = i0 < end ? a.b[i0] : make_double2(0., 0.);   // (requested before the polls)
     if (!res_collect<5>(sy, 1)) {
-        if (threadIdx.x == 0) {
-            __hip_atomic_store(a.abort_dev, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.abort_host, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        res_abort(a.abort_dev, a.abort_host);
         for (int64_t i = i0; i < end; i += stride) a.r_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
         if (threadIdx.x == 0) a.partsR_out[lb] = __builtin_nan("");
         return;
     }
     // ---- init_kernel's bookkeeping, then xr_update_kernel<true, true> of step 1 (slot 0) ----
-    const cplx num = make_double2(res_total(sy, 0), res_total(sy, 1)), den = make_double2(res_total(sy, 2), res_total(sy, 3));
-    const cplx alpha = to_sgpr(cdiv(num, den));
     if (lb == 0 && threadIdx.x == 0) {
         const double nb = res_total(sy, 4);
         a.st->bnorm2 = nb;
         a.st->rr = nb;
         a.hist[0] = sqrt(nb) / sqrt(nb);
-        *a.den0 = den;
-        a.st->npend = 1;
     }
-    if (lb == 0 && (int)threadIdx.x < LND) lean_pending_update(a.lc, 0, alpha, (int)threadIdx.x);
+    const cplx alpha = sb_xr_alpha(sy, a.st, a.lc, a.den0, 0, lb);
     double vr[1] = {0.};
 #pragma unroll
     for (int t = 0; t < SB_MAX_TRIPS; t++) {
@@ -715,75 +595,51 @@ __global__ void __launch_bounds__(RED_THREADS, 8) start_build_kernel(StartArgs a
     if (threadIdx.x == 0) a.partsR_out[lb] = tot;
 }
 
-static int g_stepbuild = -1;
-static bool stepbuild_enabled() {
-    if (g_stepbuild < 0) g_stepbuild = !(getenv("MGCR_STEPBUILD") && atoi(getenv("MGCR_STEPBUILD")) == 0);
-    return g_stepbuild != 0;
-}
-bool stepbuild_is_enabled() { return stepbuild_enabled(); }
-bool set_stepbuild_enabled(bool on) {
-    bool prev = stepbuild_enabled();
-    g_stepbuild = on ? 1 : 0;
-    return prev;
-}
+// a switch that an environment variable presets (unset or != 0: on) and mgcr_set_option changes
+struct EnvSwitch {
+    const char *env;
+    int v = -1;
+    bool on() {
+        if (v < 0) v = !(getenv(env) && atoi(getenv(env)) == 0);
+        return v != 0;
+    }
+    bool set(bool x) {   // returns the previous setting
+        const bool prev = on();
+        v = x ? 1 : 0;
+        return prev;
+    }
+};
+static EnvSwitch g_stepbuild{"MGCR_STEPBUILD"}, g_start_build{"MGCR_START_BUILD"};
+static EnvSwitch g_sb_keep_all{"MGCR_SB_KEEP_ALL"};   // off: the step_build_kernel dispatch below
+static EnvSwitch g_sb_real{"MGCR_SB_REAL"};            // the REALC instantiations
+bool stepbuild_is_enabled() { return g_stepbuild.on(); }
+bool set_stepbuild_enabled(bool on) { return g_stepbuild.set(on); }
+bool set_start_build_enabled(bool on) { return g_start_build.set(on); }
+bool set_stepbuild_keep_all_enabled(bool on) { return g_sb_keep_all.set(on); }
 static int64_t g_stepbuild_launches = 0;
 int64_t stepbuild_launch_count() { return g_stepbuild_launches; }
 
-// the instantiation a step with `nd` stored directions launches
-static bool sb_real_enabled() {
-    static const bool on = !(getenv("MGCR_SB_REAL") && atoi(getenv("MGCR_SB_REAL")) == 0);
-    return on;
-}
-// (KEEPR only where the instantiation keeps 0 scratch and 8 waves per SIMD — up to 2 stored directions; with 3..5 the kept rows
-// spill: tests/test_stepbuild_regs.py)
-template <int NDT> constexpr bool sb_keepr_fits() { return NDT <= 2; }
-static int g_sb_keepr = -1;
-static bool sb_keepr_enabled() {
-    if (g_sb_keepr < 0) g_sb_keepr = !(getenv("MGCR_SB_KEEPR") && atoi(getenv("MGCR_SB_KEEPR")) == 0);
-    return g_sb_keepr != 0;
-}
-bool set_stepbuild_keepr_enabled(bool on) {
-    const bool prev = sb_keepr_enabled();
-    g_sb_keepr = on ? 1 : 0;
-    return prev;
-}
+// The instantiation a step with `nd` stored directions launches (sb_kernel).
 // KEEP-ALL (step_keep_kernel) where an instantiation keeps 0 scratch and 8 waves per SIMD: up to 2 stored directions in every
-// form, 3 except the closing step with XR (tests/test_stepbuild_keep_all.py).  With more directions the kept rows spill (the
+// form, 3 except the closing step with XR (tests/test_stepbuild_keep_all_regs.py).  With more directions the kept rows spill (the
 // build's two trips of NDT streams, beta and the kept rows exceed 64 VGPRs): step_build_kernel takes those steps.
 template <int NDT, bool XR, bool CLOSE> constexpr bool sb_keep_fits() { return NDT <= 2 || (NDT == 3 && !(XR && CLOSE)); }
 template <int NDT, bool XR, bool CLOSE, bool R> const void *sb_keep() {
     if constexpr (sb_keep_fits<NDT, XR, CLOSE>()) return (const void *)step_keep_kernel<NDT, XR, CLOSE, R>;
     else return nullptr;
 }
-// off: the step_build_kernel dispatch below
-static int g_sb_keep_all = -1;
-static bool sb_keep_all_enabled() {
-    if (g_sb_keep_all < 0) g_sb_keep_all = !(getenv("MGCR_SB_KEEP_ALL") && atoi(getenv("MGCR_SB_KEEP_ALL")) == 0);
-    return g_sb_keep_all != 0;
-}
-bool set_stepbuild_keep_all_enabled(bool on) {
-    const bool prev = sb_keep_all_enabled();
-    g_sb_keep_all = on ? 1 : 0;
-    return prev;
-}
 static const void *sb_kernel(int nd, bool xr, bool close, bool realc) {
-    if (sb_keep_all_enabled() && (nd <= 2 || (nd == 3 && !(xr && close)))) {   // (sb_keep_fits)
+    if (g_sb_keep_all.on() && nd <= 3) {
 #define SKR(NDT, R) (close ? (xr ? sb_keep<NDT, true, true, R>() : sb_keep<NDT, false, true, R>()) \
                            : (xr ? sb_keep<NDT, true, false, R>() : sb_keep<NDT, false, false, R>()))
 #define SKK(NDT) (realc ? SKR(NDT, true) : SKR(NDT, false))
-        switch (nd) {
-            case 1: return SKK(1);
-            case 2: return SKK(2);
-            default: return SKK(3);
-        }
+        const void *keep = nd == 1 ? SKK(1) : nd == 2 ? SKK(2) : SKK(3);
 #undef SKK
 #undef SKR
+        if (keep) return keep;   // (nullptr: a form that does not fit, sb_keep_fits)
     }
-    const bool keepr = xr && !close && sb_keepr_enabled();
-#define SBX(NDT, R) ((keepr && sb_keepr_fits<NDT>()) ? (const void *)step_build_kernel<3, 7, NDT, true, false, R, sb_keepr_fits<NDT>()> \
-                                                     : (const void *)step_build_kernel<3, 7, NDT, true, false, R>)
 #define SBR(NDT, R) (close ? (xr ? (const void *)step_build_kernel<3, 7, NDT, true, true, R> : (const void *)step_build_kernel<3, 7, NDT, false, true, R>) \
-                           : (xr ? SBX(NDT, R) : (const void *)step_build_kernel<3, 7, NDT, false, false, R>))
+                           : (xr ? (const void *)step_build_kernel<3, 7, NDT, true, false, R> : (const void *)step_build_kernel<3, 7, NDT, false, false, R>))
 #define SBK(NDT) (realc ? SBR(NDT, true) : SBR(NDT, false))
     switch (nd) {
         case 1: return SBK(1);
@@ -794,7 +650,6 @@ static const void *sb_kernel(int nd, bool xr, bool close, bool realc) {
     }
 #undef SBK
 #undef SBR
-#undef SBX
 }
 // Do `grid` workgroups of this instantiation, with this much dynamic LDS, fit the chip AT ONCE?  The workgroups wait for each
 // other inside the launch, so the answer has to come from the runtime (registers and LDS of the code object that was actually
@@ -825,7 +680,7 @@ static size_t sb_lds_bytes(const CsrDev &A, int g) {
 
 // can step `lim` of a lean cycle on A run as one launch?  (single GPU, 7-slot stencil view, <= 5 stored directions, A r in LDS)
 bool csr_step_build_eligible(const CsrDev &A, const DistCsr *dist, int lim) {
-    if (!stepbuild_enabled() || dist || comm_live_count() > 0 || lim < 1 || lim > SB_MAX_ND) return false;
+    if (!g_stepbuild.on() || dist || comm_live_count() > 0 || lim < 1 || lim > SB_MAX_ND) return false;
     if (!csr_fusable(A, nullptr) || !csr_stencil_active(A) || A.sten_rare || sten_slots(A) != 7) return false;
     const int g = red_grid(A.nrow);
     if (g < 64 || g % 8 != 0) return false;   // (smaller systems have the resident solver or the xr-fused kernels)
@@ -835,11 +690,35 @@ bool csr_step_build_eligible(const CsrDev &A, const DistCsr *dist, int lim) {
     if (g > RES_BLK) return false;
     // every form the step may be launched in (with / without the next residual update, closing or not) must be co-resident
     const size_t lds = sb_lds_bytes(A, g);
-    const bool realc = sb_real_enabled() && row_mat(A, false, cplx{0., 0.}).realv;
+    const bool realc = g_sb_real.on() && row_mat(A, false, cplx{0., 0.}).realv;
     for (int xr = 0; xr < 2; xr++)
         for (int cl = 0; cl < 2; cl++)
             if (!launch_is_coresident(sb_kernel(lim, xr != 0, cl != 0, realc), RED_THREADS, lds, g)) return false;
     return true;
+}
+
+// the members the kernels share; `ngen`: exchange generations the launch may use
+template <class Args>
+static int sb_fill_common(Args &a, const CsrDev &A, bool shift, cplx k, DevState *st, const RowMap &rm, unsigned ngen) {
+    MGCR_TRY(exchange_shared_init());
+    const ExchangeShared &sh = exchange_shared();
+    a.m = row_mat(A, shift, k);
+    a.n = A.nrow;
+    a.nlogical = red_grid(A.nrow);
+    a.rm = rm;
+    a.st = st;
+    a.slots = sh.slots; a.abort_dev = sh.abort_dev; a.abort_host = sh.abort_host;
+    a.gen0 = exchange_take_generations(ngen);
+    a.test_stall = getenv("MGCR_TEST_STEPBUILD_STALL") ? atoi(getenv("MGCR_TEST_STEPBUILD_STALL")) : 0;
+    a.spin_limit = getenv("MGCR_TEST_RESIDENT_SPIN_LIMIT") ? atoi(getenv("MGCR_TEST_RESIDENT_SPIN_LIMIT")) : RES_SPIN_LIMIT;
+    return MGCR_OK;
+}
+static int sb_launch(const void *kernel, void *args, int grid, size_t lds_bytes, const char *who) {
+    MGCR_CHECK(launch_is_coresident(kernel, RED_THREADS, lds_bytes, grid), MGCR_ERR_INVALID, "%s: launch would not be co-resident", who);
+    void *kargs[1] = {args};
+    MGCR_HIP(hipLaunchKernel(kernel, dim3((unsigned)grid), dim3(RED_THREADS), kargs, lds_bytes, ctx().stream));
+    MGCR_HIP(hipGetLastError());
+    return MGCR_OK;
 }
 
 int csr_step_build(const CsrDev &A, const cplx *x, bool shift, cplx k, const cplx *const *aps, int nd, DevState *st, int it, const double *partsR,
@@ -847,46 +726,21 @@ int csr_step_build(const CsrDev &A, const cplx *x, bool shift, cplx k, const cpl
                    const RowMap &rm, cplx *xr_out, cplx *xr_den_slot, int xr_slot, double *partsR_out, const cplx *const *close_ps, cplx *close_p_out,
                    cplx *close_x) {
     MGCR_CHECK(nd >= 1 && nd <= SB_MAX_ND, MGCR_ERR_INVALID, "csr_step_build: 1..5 directions");
-    MGCR_TRY(exchange_shared_init());
-    ExchangeShared &sh = exchange_shared();
     StepBuildArgs a;
-    a.m = row_mat(A, shift, k);
+    MGCR_TRY(sb_fill_common(a, A, shift, k, st, rm, 3));
     a.x = x;
     for (int j = 0; j < SB_MAX_ND; j++) a.aps[j] = aps[j < nd ? j : 0];
-    a.n = A.nrow;
-    const int g = red_grid(A.nrow);
-    a.nlogical = g;
-    a.rm = rm;
-    a.st = st; a.it = it; a.partsR = partsR; a.nblkR = nblkR; a.strideR = strideR; a.hist = hist; a.hist_cap = hist_cap;
+    a.it = it; a.partsR = partsR; a.nblkR = nblkR; a.strideR = strideR; a.hist = hist; a.hist_cap = hist_cap;
     a.den = den; a.ap_out = ap_out; a.partsA = partsA; a.lc = lc;
-    a.slots = sh.slots; a.abort_dev = sh.abort_dev; a.abort_host = sh.abort_host;
     for (int j = 0; j < SB_MAX_ND; j++) a.ps[j] = close_ps ? close_ps[j < nd ? j : 0] : nullptr;
     a.p_out = close_p_out; a.xvec = close_x;
     a.xr_out = xr_out; a.xr_den_slot = xr_den_slot; a.xr_slot = xr_slot; a.partsR_out = partsR_out;
-    a.gen0 = exchange_take_generations(3);
-    a.test_stall = getenv("MGCR_TEST_STEPBUILD_STALL") ? atoi(getenv("MGCR_TEST_STEPBUILD_STALL")) : 0;
-    a.spin_limit = getenv("MGCR_TEST_RESIDENT_SPIN_LIMIT") ? atoi(getenv("MGCR_TEST_RESIDENT_SPIN_LIMIT")) : RES_SPIN_LIMIT;
-    const unsigned grid = (unsigned)g;
-    const size_t lds_bytes = sb_lds_bytes(A, g);
-    const void *kernel = sb_kernel(nd, xr_out != nullptr, close_ps != nullptr, sb_real_enabled() && a.m.realv);
-    MGCR_CHECK(launch_is_coresident(kernel, RED_THREADS, lds_bytes, g), MGCR_ERR_INVALID, "csr_step_build: launch would not be co-resident");
-    void *kargs[1] = {(void *)&a};
-    MGCR_HIP(hipLaunchKernel(kernel, dim3(grid), dim3(RED_THREADS), kargs, lds_bytes, ctx().stream));
-    MGCR_HIP(hipGetLastError());
+    MGCR_TRY(sb_launch(sb_kernel(nd, xr_out != nullptr, close_ps != nullptr, g_sb_real.on() && a.m.realv), &a, a.nlogical, sb_lds_bytes(A, a.nlogical),
+                       "csr_step_build"));
     g_stepbuild_launches++;
     return MGCR_OK;
 }
 
-static int g_start_build = -1;
-static bool start_build_enabled() {
-    if (g_start_build < 0) g_start_build = !(getenv("MGCR_START_BUILD") && atoi(getenv("MGCR_START_BUILD")) == 0);
-    return g_start_build != 0;
-}
-bool set_start_build_enabled(bool on) {
-    const bool prev = start_build_enabled();
-    g_start_build = on ? 1 : 0;
-    return prev;
-}
 static int64_t g_start_build_launches = 0;
 int64_t start_build_launch_count() { return g_start_build_launches; }
 static const void *start_kernel(bool realc) {
@@ -895,34 +749,19 @@ static const void *start_kernel(bool realc) {
 
 // can the start of a solve on A run as one launch?  (the conditions of a one-launch step, and its own kernel co-resident)
 bool csr_start_build_eligible(const CsrDev &A, const DistCsr *dist) {
-    if (!start_build_enabled() || !csr_step_build_eligible(A, dist, 1)) return false;
-    const bool realc = sb_real_enabled() && row_mat(A, false, cplx{0., 0.}).realv;
+    if (!g_start_build.on() || !csr_step_build_eligible(A, dist, 1)) return false;
+    const bool realc = g_sb_real.on() && row_mat(A, false, cplx{0., 0.}).realv;
     return launch_is_coresident(start_kernel(realc), RED_THREADS, sb_lds_bytes(A, red_grid(A.nrow)), red_grid(A.nrow));
 }
 
 int csr_start_build(const CsrDev &A, const cplx *b, bool shift, cplx k, cplx *ap0, DevState *st, double *hist, LeanCoef *lc, cplx *den0,
                     cplx *r_out, double *partsR_out, const RowMap &rm) {
-    MGCR_TRY(exchange_shared_init());
-    ExchangeShared &sh = exchange_shared();
     StartArgs a;
-    a.m = row_mat(A, shift, k);
+    MGCR_TRY(sb_fill_common(a, A, shift, k, st, rm, 1));
     a.b = b;
     a.ap0 = ap0;
-    a.n = A.nrow;
-    const int g = red_grid(A.nrow);
-    a.nlogical = g;
-    a.rm = rm;
-    a.st = st; a.hist = hist; a.lc = lc; a.den0 = den0; a.r_out = r_out; a.partsR_out = partsR_out;
-    a.slots = sh.slots; a.abort_dev = sh.abort_dev; a.abort_host = sh.abort_host;
-    a.gen0 = exchange_take_generations(1);
-    a.test_stall = getenv("MGCR_TEST_STEPBUILD_STALL") ? atoi(getenv("MGCR_TEST_STEPBUILD_STALL")) : 0;
-    a.spin_limit = getenv("MGCR_TEST_RESIDENT_SPIN_LIMIT") ? atoi(getenv("MGCR_TEST_RESIDENT_SPIN_LIMIT")) : RES_SPIN_LIMIT;
-    const size_t lds_bytes = sb_lds_bytes(A, g);
-    const void *kernel = start_kernel(sb_real_enabled() && a.m.realv);
-    MGCR_CHECK(launch_is_coresident(kernel, RED_THREADS, lds_bytes, g), MGCR_ERR_INVALID, "csr_start_build: launch would not be co-resident");
-    void *kargs[1] = {(void *)&a};
-    MGCR_HIP(hipLaunchKernel(kernel, dim3((unsigned)g), dim3(RED_THREADS), kargs, lds_bytes, ctx().stream));
-    MGCR_HIP(hipGetLastError());
+    a.hist = hist; a.lc = lc; a.den0 = den0; a.r_out = r_out; a.partsR_out = partsR_out;
+    MGCR_TRY(sb_launch(start_kernel(g_sb_real.on() && a.m.realv), &a, a.nlogical, sb_lds_bytes(A, a.nlogical), "csr_start_build"));
     g_start_build_launches++;
     return MGCR_OK;
 }

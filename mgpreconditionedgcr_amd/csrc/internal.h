@@ -208,7 +208,6 @@ bool set_stepbuild_enabled(bool on);   // gcr_stepbuild.hip: apply + dots + buil
 int64_t stepbuild_launch_count();
 bool set_start_build_enabled(bool on);         // ... and the start of a solve as one launch
 int64_t start_build_launch_count();
-bool set_stepbuild_keepr_enabled(bool on);     // ... an in-cycle step keeps r in registers for the next update
 bool set_stepbuild_keep_all_enabled(bool on);  // ... every one-launch step reads r once (step_keep_kernel)
 int coherence_selftest(int steps, int coherent, int64_t *rows_wrong);   // gcr_resident.hip
 bool stepbuild_is_enabled();

@@ -1,5 +1,5 @@
-"""The start of a solve as one launch (csrc/gcr_stepbuild.hip start_build_kernel, mgcr_set_option "start_build") and the in-cycle
-step that keeps r in registers for the next residual update ("step_build_keep_r"): each switched on and off must give the same
+"""The start of a solve as one launch (csrc/gcr_stepbuild.hip start_build_kernel, mgcr_set_option "start_build") and the one-launch
+steps that read r once and keep it in registers (step_keep_kernel, "step_build_keep_all"): each switched on and off must give the same
 iteration count, history and x bit for bit, and the one-launch start must actually have run where it is eligible."""
 import os
 import sys
@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 
 pytestmark = pytest.mark.gpu
 
-OFF = {"start_build": 0, "step_build_keep_r": 0}
+OFF = {"start_build": 0, "step_build_keep_all": 0}
 
 
 def _problem(n, dirac):
@@ -51,7 +51,7 @@ def test_parts_on_off_bit_for_bit(n, restart, max_it, dirac):
     on = _solve(op, dims, b, restart, max_it, 0.0, {})
     off = _solve(op, dims, b, restart, max_it, 0.0, OFF)
     start_off = _solve(op, dims, b, restart, max_it, 0.0, {"start_build": 0})
-    keep_off = _solve(op, dims, b, restart, max_it, 0.0, {"step_build_keep_r": 0})
+    keep_off = _solve(op, dims, b, restart, max_it, 0.0, {"step_build_keep_all": 0})
     for other in (off, start_off, keep_off):
         _same(on, other)
     assert off[3] == 0 and start_off[3] == 0

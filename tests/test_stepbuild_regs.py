@@ -11,10 +11,10 @@ import pytest
 CS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mgpreconditionedgcr_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-# (the in-cycle steps keep r in registers up to 2 stored directions: sb_keepr_fits)
-HEADLINE = ["step_build_kernel<3, 7, 1, true, false, true, true>", "step_build_kernel<3, 7, 2, true, false, true, true>",
-            "step_build_kernel<3, 7, 3, true, false, true, false>", "step_build_kernel<3, 7, 4, true, false, true, false>",
-            "step_build_kernel<3, 7, 5, true, true, true, false>", "start_build_kernel<true>", "start_build_kernel<false>"]
+# (up to 2 stored directions the default dispatch launches the kernels that read r once: sb_keep_fits)
+HEADLINE = ["step_keep_kernel<1, true, false, true>", "step_keep_kernel<2, true, false, true>",
+            "step_build_kernel<3, 7, 3, true, false, true>", "step_build_kernel<3, 7, 4, true, false, true>",
+            "step_build_kernel<3, 7, 5, true, true, true>", "start_build_kernel<true>", "start_build_kernel<false>"]
 
 
 @pytest.fixture(scope="module")
