@@ -3,8 +3,8 @@
 //
 //   * x, r and the stored directions live in HBM for the whole solve; p and Ap are not separate
 //     vectors but the ring slot that was written last (the reference copies them, :286-287);
-//   * per iteration three kernels instead of ~90 vector passes — one launch per iteration where A r fits
-//     the chip's LDS (gcr_stepbuild.hip), one launch per solve for small systems (gcr_resident.hip):
+//   * per iteration three kernels instead of ~90 vector passes; which of their forms a solve launches is
+//     decided once, in gcr_plan (SolvePlan), and enqueued by gcr_start and gcr_step's phases:
 //        xr_update   x += a p, r -= a Ap, |r|^2 partials                         6 V  (3 V when the
 //                    x update is deferred to the end of the restart cycle, see xr_update_kernel)
 //        apply+dots  Ar = A r and the <Ar, Aps[i]> partials for all stored i      B_matrix + (2+lim) V
@@ -14,16 +14,13 @@
 //                    ring slot, plus <r,Ap'> and <Ap',Ap'> partials and the step's bookkeeping
 //                    (history entry, convergence predicate)                        (4+2 lim) V
 //     = B_matrix + (9 + 3 lim) V of HBM traffic per iteration in the classic form, and
-//   * restart mode (restart <= 16) without the literal preconditioner hooks runs LEAN: inside a restart cycle the
-//     directions p_k are never formed.  Only x needs them, and x is updated once per cycle, so the
-//     solver keeps what p_k is a combination of — the cycle's first direction P0 and the residuals
-//     (or M r, flexible mode) D_1..D_k the later directions were started from — plus the small
-//     triangular table of coefficients p_k = t_k P0 + sum_m T_km D_m on the device.  The residual ring
-//     costs nothing (xr_update writes r into the slot instead of in place), build shrinks from
-//     (4+2 lim) V to (3+lim) V, and the step that closes the cycle applies x += sum_k alpha_k p_k and
-//     forms the next P0 from the same streams the classic closing step reads.  r, Ap and every scalar
-//     follow the same recurrences with the same bits; x differs by rounding only (MGCR_LEAN=0 selects
-//     the classic kernels);
+//   * LEAN (SolvePlan::lean): inside a restart cycle the directions p_k are never formed.  Only x needs them, and x is
+//     updated once per cycle, so the solver keeps what p_k is a combination of — the cycle's first direction P0 and the
+//     residuals (or M r, flexible mode) D_1..D_k the later directions were started from — plus the small triangular table of
+//     coefficients p_k = t_k P0 + sum_m T_km D_m on the device.  The residual ring costs nothing (xr_update writes r into the
+//     slot instead of in place), build shrinks from (4+2 lim) V to (3+lim) V, and the step that closes the cycle applies
+//     x += sum_k alpha_k p_k and forms the next P0 from the same streams the classic closing step reads.  r, Ap and every
+//     scalar follow the same recurrences with the same bits; x differs by rounding only;
 //   * all scalars (alpha, beta_i, norms, the iteration counter, the convergence flag and the
 //     residual history) stay on the device.  Reductions are two-stage and deterministic: producers
 //     write per-workgroup partials, consumers fold them in a fixed order (reduce.h), so the
@@ -41,6 +38,7 @@
 // with -ffp-contract=off so element-wise results round like the reference's.
 #include <climits>
 #include <cmath>
+#include <type_traits>
 
 #include "internal.h"
 #include "reduce.h"
@@ -49,16 +47,8 @@
 
 namespace mgcr {
 
-static int g_lean = -1;
-static bool lean_enabled() {
-    if (g_lean < 0) g_lean = !(getenv("MGCR_LEAN") && atoi(getenv("MGCR_LEAN")) == 0);
-    return g_lean != 0;
-}
-bool set_lean_enabled(bool on) {
-    bool prev = lean_enabled();
-    g_lean = on ? 1 : 0;
-    return prev;
-}
+static EnvSwitch g_lean{"MGCR_LEAN"};
+bool set_lean_enabled(bool on) { return g_lean.set(on); }
 
 // profile_spmv: hipEvents around the three phases of every iteration of the last profiled solve:
 // 0 = alpha/r update (+ preconditioner), 1 = operator apply + beta dot products, 2 = direction build
@@ -110,7 +100,7 @@ struct GcrState {
     double *dN = nullptr;   // [2]: |b|^2, |r0|^2
     cplx *alphas = nullptr; // [storage]: alpha of the deferred x updates of the current restart cycle
     LeanCoef *lc = nullptr;
-    // captured restart cycle (see gcr_run)
+    // captured restart cycle (gcr_capture_cycle)
     hipGraphExec_t graph_exec = nullptr;
     const cplx *graph_x = nullptr;
     int graph_R = 0;
@@ -119,33 +109,11 @@ struct GcrState {
 
 constexpr int64_t GRAPH_MAX_ROWS = 1 << 18;
 
-static bool bnorm_reuse_enabled() {
-    static const bool on = !(getenv("MGCR_BNORM_REUSE") && atoi(getenv("MGCR_BNORM_REUSE")) == 0);
-    return on;
-}
-static bool fuse_init_enabled() {
-    static const bool on = !(getenv("MGCR_FUSE_INIT") && atoi(getenv("MGCR_FUSE_INIT")) == 0);
-    return on;
-}
-static bool stepbuild_xr_enabled() {
-    static const bool on = !(getenv("MGCR_STEPBUILD_XR") && atoi(getenv("MGCR_STEPBUILD_XR")) == 0);
-    return on;
-}
-static bool stepbuild_close_enabled() {
-    static const bool on = !(getenv("MGCR_STEPBUILD_CLOSE") && atoi(getenv("MGCR_STEPBUILD_CLOSE")) == 0);
-    return on;
-}
-static int g_graph = -1;
-static bool graphs_enabled() {
-    // opt-in (MGCR_GRAPH=1 / mgcr_set_option("graph_replay")): see the measurements at the capture site in gcr_run
-    if (g_graph < 0) g_graph = getenv("MGCR_GRAPH") && atoi(getenv("MGCR_GRAPH")) != 0;
-    return g_graph != 0;
-}
-bool set_graph_enabled(bool on) {
-    bool prev = graphs_enabled();
-    g_graph = on ? 1 : 0;
-    return prev;
-}
+static EnvSwitch g_bnorm_reuse{"MGCR_BNORM_REUSE"}, g_fuse_init{"MGCR_FUSE_INIT"}, g_skip_dead_ap{"MGCR_SKIP_DEAD_AP"};
+static EnvSwitch g_stepbuild_xr{"MGCR_STEPBUILD_XR"}, g_stepbuild_close{"MGCR_STEPBUILD_CLOSE"};
+// opt-in (MGCR_GRAPH=1 / mgcr_set_option("graph_replay")): see the measurements at gcr_capture_cycle
+static EnvSwitch g_graph{"MGCR_GRAPH", false};
+bool set_graph_enabled(bool on) { return g_graph.set(on); }
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -292,13 +260,13 @@ __device__ __forceinline__ void flush_x_rows(const cplx *__restrict__ alphas, co
         cplx pv[NP];
 #pragma unroll
         for (int j = 0; j < NP; j++) pv[j] = (j == 0 ? p0 : d0.ps[j])[i];
-        cplx xv = assign ? make_double2(0., 0.) : x[i];   // assign: x0 = 0 was never materialised (gcr_run: assign_x)
+        cplx xv = assign ? make_double2(0., 0.) : x[i];   // assign: x0 = 0 was never materialised (SolvePlan::assign_x)
 #pragma unroll
         for (int j = 0; j < NP; j++) xv = cadd(xv, cmul(al[j], pv[j]));
         x[i] = xv;
     }
 }
-// p0_first: where P0 lives until the solve's first cycle is closed (gcr_run_once start1: b itself), d0.ps[0] after that
+// p0_first: where P0 lives until the solve's first cycle is closed (SolvePlan::start1: b itself), d0.ps[0] after that
 __global__ void __launch_bounds__(RED_THREADS) flush_x_kernel(DevState *__restrict__ st, const cplx *__restrict__ alphas, DirPtrs d0,
                                                               cplx *__restrict__ x, int64_t n, int assign, const cplx *p0_first) {
     const int np = st->npend;
@@ -502,7 +470,7 @@ __global__ void __launch_bounds__(RED_THREADS) alpha_only_kernel(DevState *st, i
 
 // Bookkeeping of a step without the direction build (src/GCR.h:270-274,288): the LAST iteration a solve can run
 // (count == max_iter) still updates x and r and records |r|, but the next search direction the reference goes on to
-// build (src/GCR.h:236-287: M r, A r, the beta dots, p, Ap) is never used — gcr_run stops after this kernel.
+// build (src/GCR.h:236-287: M r, A r, the beta dots, p, Ap) is never used — gcr_step's step_finish ends the step with this kernel.
 __global__ void __launch_bounds__(RED_THREADS) finish_step_kernel(DevState *st, int it, const double *__restrict__ partsR, int nblkR,
                                                                   int strideR, double *__restrict__ hist, int hist_cap) {
     __shared__ double lds[17];
@@ -900,22 +868,19 @@ struct SkipGuard {
     ~SkipGuard() { set_apply_skip(prev); }
 };
 
-static int launch_multidot(int g, int nd, const DevState *st, int it, const cplx *ar, const DirPtrs &d, int base, int64_t n, double *partsB,
-                           const RowMap &rm) {
-#define MD(NDT, U) KLAUNCH((multidot_kernel<NDT, U>), g, st, it, ar, d, base, n, rm, partsB)
-    switch (nd) {
-        case 1: MD(1, 2); break;
-        case 2: MD(2, 2); break;
-        case 3: MD(3, 1); break;
-        case 4: MD(4, 1); break;
-        case 5: MD(5, 1); break;
-        case 6: MD(6, 1); break;
-        case 7: MD(7, 1); break;
-        default: MD(8, 1); break;
+// Run-time direction count -> NDT template argument: f(std::integral_constant<int, N>{}) with N = nd for LO <= nd < HI and
+// N = HI for every other nd (the widest form, like the default: of a switch)
+template <int LO, int HI, typename F>
+static int dispatch_nd(int nd, F &&f) {
+    if constexpr (LO < HI) {
+        if (nd == LO) return f(std::integral_constant<int, LO>{});
+        return dispatch_nd<LO + 1, HI>(nd, f);
+    } else {
+        return f(std::integral_constant<int, HI>{});
     }
-#undef MD
-    return MGCR_OK;
 }
+template <typename F>
+static int dispatch_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 struct RedRef {  // where a consumer finds a reduction: slab of per-workgroup partials, or folded + all-reduced scalars
     const double *p;
@@ -926,49 +891,38 @@ struct BuildArgs {
     int g, nd;
     bool first, last, rdir, xupd;
     DevState *st;
-    int it;
-    RedRef B;
-    int book;
-    RedRef R;
-    double *hist;
-    int hist_cap;
-    const cplx *den;
+    int it, book, base, hist_cap;
+    RedRef B, R;
+    double *hist, *partsA;
     DirPtrs d;
-    int base;
-    const cplx *dir, *r, *ar;
-    cplx *accp, *accap, *p_out, *ap_out;
+    const cplx *den, *dir, *r, *ar, *alphas;
+    cplx *accp, *accap, *p_out, *ap_out, *x;
     int64_t n;
-    double *partsA;
-    cplx *x;
-    const cplx *alphas;
 };
 
-template <int NDT>
-static int launch_build_n(const BuildArgs &a) {
-    const int g = a.g;
-#define BK(F, L, R_, X_)                                                                                                       \
-    KLAUNCH((build_kernel<NDT, F, L, R_, X_>), g, a.st, a.it, a.B.p, a.B.nblk, a.B.stride, a.book, a.R.p, a.R.nblk, a.R.stride, \
-            a.hist, a.hist_cap, a.den, a.d, a.base, a.dir, a.r, a.ar, a.accp, a.accap, a.p_out, a.ap_out, a.n, a.partsA, a.x, a.alphas)
-    if (a.first && a.last) {
-        if (a.xupd) { if (a.rdir) BK(true, true, true, true); else BK(true, true, false, true); }
-        else { if (a.rdir) BK(true, true, true, false); else BK(true, true, false, false); }
-    } else if (a.first) BK(true, false, false, false);
-    else if (a.last) { if (a.rdir) BK(false, true, true, false); else BK(false, true, false, false); }
-    else BK(false, false, false, false);
-#undef BK
-    return MGCR_OK;
+// RDIR only exists for the chunk that reads r (LAST), XUPD only for a closing step of one chunk
+static int launch_build(const BuildArgs &a) {
+    return dispatch_nd<1, ND>(a.nd, [&](auto N) -> int {
+        auto bk = [&](auto fi, auto la, auto rd, auto xu) -> int {
+            KLAUNCH((build_kernel<decltype(N)::value, decltype(fi)::value, decltype(la)::value, decltype(rd)::value, decltype(xu)::value>), a.g,
+                    a.st, a.it, a.B.p, a.B.nblk, a.B.stride, a.book, a.R.p, a.R.nblk, a.R.stride, a.hist, a.hist_cap, a.den, a.d, a.base,
+                    a.dir, a.r, a.ar, a.accp, a.accap, a.p_out, a.ap_out, a.n, a.partsA, a.x, a.alphas);
+            return MGCR_OK;
+        };
+        constexpr std::true_type T{};
+        constexpr std::false_type F{};
+        if (a.first && a.last) return a.xupd ? (a.rdir ? bk(T, T, T, T) : bk(T, T, F, T)) : (a.rdir ? bk(T, T, T, F) : bk(T, T, F, F));
+        if (a.first) return bk(T, F, F, F);
+        if (a.last) return a.rdir ? bk(F, T, T, F) : bk(F, T, F, F);
+        return bk(F, F, F, F);
+    });
 }
 
-static int launch_build(const BuildArgs &a) {
-    switch (a.nd) {
-        case 1: return launch_build_n<1>(a);
-        case 2: return launch_build_n<2>(a);
-        case 3: return launch_build_n<3>(a);
-        case 4: return launch_build_n<4>(a);
-        case 5: return launch_build_n<5>(a);
-        case 6: return launch_build_n<6>(a);
-        case 7: return launch_build_n<7>(a);
-        default: return launch_build_n<8>(a);
+// the ring slots first .. first + nd - 1 in the first `width` entries (the unused ones repeat slot `first`)
+static void fill_dirs(DirPtrs &d, const GcrState *s, int first, int nd, int width) {
+    for (int j = 0; j < width; j++) {
+        const int sl = first + (j < nd ? j : 0);
+        d.ps[j] = s->ps[sl]; d.aps[j] = s->aps[sl]; d.slot[j] = sl;
     }
 }
 
@@ -976,117 +930,50 @@ struct LeanArgs {
     int g, nd;
     bool rdir;
     DevState *st;
-    int it;
+    int it, hist_cap;
     RedRef B, R;
-    double *hist;
-    int hist_cap;
-    const cplx *den;
+    double *hist, *partsA;
     DirPtrs d;
-    const cplx *dir, *r, *ar;
-    cplx *p_out, *ap_out;
+    const cplx *den, *dir, *r, *ar;
+    cplx *p_out, *ap_out, *x;
     int64_t n;
-    double *partsA;
-    cplx *x;
     LeanCoef *lc;
     const PwTail *pw = nullptr;   // multi-GPU: the kernel's last workgroup folds partsA and sums it over the ranks (up to 8 directions)
 };
 
-static int launch_build_lean(const LeanArgs &a, int closing) {
-#define BL(NDT)                                                                                                               \
-    KLAUNCH((build_lean_kernel<NDT>), a.g, a.st, a.it, a.B.p, a.B.nblk, a.B.stride, a.R.p, a.R.nblk, a.R.stride, a.hist,      \
-            a.hist_cap, a.den, a.d, a.r, a.ar, a.ap_out, a.n, a.partsA, a.lc, closing, PwTail{})
-#define BLP(NDT)                                                                                                              \
-    KLAUNCH((build_lean_kernel<NDT, true>), a.g, a.st, a.it, a.B.p, a.B.nblk, a.B.stride, a.R.p, a.R.nblk, a.R.stride, a.hist, \
-            a.hist_cap, a.den, a.d, a.r, a.ar, a.ap_out, a.n, a.partsA, a.lc, closing, *a.pw)
-    if (a.pw) {
-        switch (a.nd) {
-            case 1: BLP(1); break;
-            case 2: BLP(2); break;
-            case 3: BLP(3); break;
-            case 4: BLP(4); break;
-            case 5: BLP(5); break;
-            case 6: BLP(6); break;
-            case 7: BLP(7); break;
-            default: BLP(8); break;
-        }
+template <int HI, bool PW>
+static int launch_build_lean_upto(const LeanArgs &a, int closing) {
+    return dispatch_nd<1, HI>(a.nd, [&](auto N) -> int {
+        KLAUNCH((build_lean_kernel<decltype(N)::value, PW>), a.g, a.st, a.it, a.B.p, a.B.nblk, a.B.stride, a.R.p, a.R.nblk, a.R.stride,
+                a.hist, a.hist_cap, a.den, a.d, a.r, a.ar, a.ap_out, a.n, a.partsA, a.lc, closing, PW ? *a.pw : PwTail{});
         return MGCR_OK;
-    }
-    switch (a.nd) {
-        case 1: BL(1); break;
-        case 2: BL(2); break;
-        case 3: BL(3); break;
-        case 4: BL(4); break;
-        case 5: BL(5); break;
-        case 6: BL(6); break;
-        case 7: BL(7); break;
-        case 8: BL(8); break;
-        case 9: BL(9); break;
-        case 10: BL(10); break;
-        case 11: BL(11); break;
-        case 12: BL(12); break;
-        case 13: BL(13); break;
-        case 14: BL(14); break;
-        case 15: BL(15); break;
-        default: BL(16); break;
-    }
-#undef BL
-#undef BLP
-    return MGCR_OK;
+    });
+}
+static int launch_build_lean(const LeanArgs &a, int closing) {
+    return a.pw ? launch_build_lean_upto<ND, true>(a, closing) : launch_build_lean_upto<LND, false>(a, closing);
 }
 
 static int launch_close_x(const LeanArgs &a) {
-#define CX(NDT)                                                                                                               \
-    do {                                                                                                                      \
-        hipLaunchKernelGGL((close_x_kernel<NDT>), dim3(2 * a.g), dim3(RED_THREADS / 2), 0, ctx().stream, a.st, a.it, a.B.p,   \
-                           a.B.nblk, a.B.stride, a.den, a.d, a.dir, a.p_out, a.n, a.x, (const LeanCoef *)a.lc);               \
-        MGCR_HIP(hipGetLastError());                                                                                          \
-    } while (0)
-    switch (a.nd) {
-        case 9: CX(9); break;
-        case 10: CX(10); break;
-        case 11: CX(11); break;
-        case 12: CX(12); break;
-        case 13: CX(13); break;
-        case 14: CX(14); break;
-        case 15: CX(15); break;
-        default: CX(16); break;
-    }
-#undef CX
-    return MGCR_OK;
+    return dispatch_nd<ND + 1, LND>(a.nd, [&](auto N) -> int {
+        hipLaunchKernelGGL((close_x_kernel<decltype(N)::value>), dim3(2 * a.g), dim3(RED_THREADS / 2), 0, ctx().stream, a.st, a.it, a.B.p,
+                           a.B.nblk, a.B.stride, a.den, a.d, a.dir, a.p_out, a.n, a.x, (const LeanCoef *)a.lc);
+        MGCR_HIP(hipGetLastError());
+        return MGCR_OK;
+    });
 }
 
 static int launch_build_close(const LeanArgs &a) {
-#define BC(NDT)                                                                                                               \
-    do {                                                                                                                      \
-        if (a.pw && a.rdir)                                                                                                   \
-            KLAUNCH((build_close_kernel<NDT, true, true>), a.g, a.st, a.it, a.B.p, a.B.nblk, a.B.stride, a.R.p, a.R.nblk,     \
-                    a.R.stride, a.hist, a.hist_cap, a.den, a.d, a.dir, a.r, a.ar, a.p_out, a.ap_out, a.n, a.partsA, a.x,      \
-                    (const LeanCoef *)a.lc, *a.pw);                                                                           \
-        else if (a.pw)                                                                                                        \
-            KLAUNCH((build_close_kernel<NDT, false, true>), a.g, a.st, a.it, a.B.p, a.B.nblk, a.B.stride, a.R.p, a.R.nblk,    \
-                    a.R.stride, a.hist, a.hist_cap, a.den, a.d, a.dir, a.r, a.ar, a.p_out, a.ap_out, a.n, a.partsA, a.x,      \
-                    (const LeanCoef *)a.lc, *a.pw);                                                                           \
-        else if (a.rdir)                                                                                                      \
-            KLAUNCH((build_close_kernel<NDT, true>), a.g, a.st, a.it, a.B.p, a.B.nblk, a.B.stride, a.R.p, a.R.nblk,           \
-                    a.R.stride, a.hist, a.hist_cap, a.den, a.d, a.dir, a.r, a.ar, a.p_out, a.ap_out, a.n, a.partsA, a.x,      \
-                    (const LeanCoef *)a.lc, PwTail{});                                                                        \
-        else                                                                                                                  \
-            KLAUNCH((build_close_kernel<NDT, false>), a.g, a.st, a.it, a.B.p, a.B.nblk, a.B.stride, a.R.p, a.R.nblk,          \
-                    a.R.stride, a.hist, a.hist_cap, a.den, a.d, a.dir, a.r, a.ar, a.p_out, a.ap_out, a.n, a.partsA, a.x,      \
-                    (const LeanCoef *)a.lc, PwTail{});                                                                        \
-    } while (0)
-    switch (a.nd) {
-        case 1: BC(1); break;
-        case 2: BC(2); break;
-        case 3: BC(3); break;
-        case 4: BC(4); break;
-        case 5: BC(5); break;
-        case 6: BC(6); break;
-        case 7: BC(7); break;
-        default: BC(8); break;
-    }
-#undef BC
-    return MGCR_OK;
+    return dispatch_nd<1, ND>(a.nd, [&](auto N) -> int {
+        return dispatch_bool(a.rdir, [&](auto R) -> int {
+            return dispatch_bool(a.pw != nullptr, [&](auto P) -> int {
+                constexpr bool PW = decltype(P)::value;
+                KLAUNCH((build_close_kernel<decltype(N)::value, decltype(R)::value, PW>), a.g, a.st, a.it, a.B.p, a.B.nblk, a.B.stride,
+                        a.R.p, a.R.nblk, a.R.stride, a.hist, a.hist_cap, a.den, a.d, a.dir, a.r, a.ar, a.p_out, a.ap_out, a.n, a.partsA,
+                        a.x, (const LeanCoef *)a.lc, PW ? *a.pw : PwTail{});
+                return MGCR_OK;
+            });
+        });
+    });
 }
 
 // read back iteration count / history once the solve has been enqueued (not for nested solves)
@@ -1113,160 +1000,189 @@ static int gcr_finish(GcrState *s, double *hist, int hist_cap, int *n_iter, int 
     return MGCR_OK;
 }
 
-static int gcr_run_once(GcrState *s, const cplx *rhs, cplx *x, bool nested, double *hist, int hist_cap, int *n_iter, int *converged) {
-    Context &c = ctx();
-    MGCR_CHECK(s->A, MGCR_ERR_INVALID, "GCR has no operator (call initialise / mgcr_gcr_set_operator first)");
-    const int64_t n = s->A->dim;
-    MGCR_TRY(gcr_prepare(s, n));
-    const mgcr_gcr_param &p = s->p;
-    const int g = red_grid(n);
-    const bool flex = p.flexible && p.right_precond;
-    const SkipRef outer = get_apply_skip();  // outer solver's predicate: if that solve is over, this one is a no-op too
-    s->has_pending = false;
-    s->defer_it = 0;
-    s->partsN_of = nullptr;   // (set again below by the path that leaves |b|^2 partials behind)
-    const bool from_zero = s->x_from_zero;   // gcr_run_from_zero: x has to be zeroed here, unless the solve only ever ASSIGNS x
-    s->x_from_zero = false;
-
-    // small systems: the whole solve in one launch of one workgroup (gcr_small.hip)
-    if (gcr_small_eligible(s->A, p, s->storage, n)) {
-        if (from_zero) MGCR_TRY(k_zero_apply(x, n));
-        MGCR_TRY(ensure_slot(s, s->storage - 1));
-        MGCR_TRY(gcr_small_run(s->A, p, s->storage, s->restart, rhs, x, s->r, s->ar, s->ps.data(), s->aps.data(), s->hist,
-                               s->hist_cap, &s->st->stop_at));
-        s->r_after.assign((size_t)(p.max_iter > 0 ? p.max_iter : 1) + 1, (const cplx *)s->r);
-        if (nested) return MGCR_OK;
-        return gcr_finish(s, hist, hist_cap, n_iter, converged);
-    }
-
-    // systems of at most one row per thread of the chip: the whole solve in one launch, vectors in registers (gcr_resident.hip)
-    {
-        const bool lean0 = p.restart != 0 && s->storage <= LND && lean_enabled() && !p.left_precond && (!p.right_precond || flex);
-        const bool handoff = nested && (s->keep_pending || s->defer_residual);   // callers that take x or r in pieces (V-cycle pre-smoother)
-        if (!graphs_enabled() && gcr_resident_eligible(s->A, p, s->storage, s->restart, n, lean0, handoff)) {
-            if (!s->res_ring) MGCR_TRY(dalloc(&s->res_ring, (size_t)11 * n));   // the residual ring + P0 (freed with the other vectors)
-            MGCR_TRY(gcr_resident_run(s->A, p, s->storage, s->restart, rhs, x, from_zero, nested && s->discard_residual, s->st, s->hist,
-                                      s->hist_cap, s->res_ring, outer));
-            s->r_after.clear();
-            if (nested) return MGCR_OK;
-            MGCR_TRY(gcr_finish(s, hist, hist_cap, n_iter, converged));
-            return resident_check(true);
-        }
-    }
-    hipLaunchKernelGGL(reset_kernel, dim3(1), dim3(1), 0, c.stream, s->st, outer.p, outer.it, p.tol * p.tol);
-    MGCR_HIP(hipGetLastError());
-    SkipGuard guard(SkipRef{&s->st->stop_at, 0});
-
+// Every path decision of one solve, taken once (gcr_plan) before anything is enqueued: which kernels gcr_start and gcr_step launch.
+struct SolvePlan {
+    const cplx *rhs; cplx *x; int64_t n;
+    bool nested, from_zero;   // from_zero (gcr_run_from_zero): x has to be zeroed here, unless the solve only ever ASSIGNS x
+    const Op *b0;      // the Sparse behind A (A itself or a DiracOp's base); nullptr: A is something else
+    bool shift; cplx k;   // DiracOp: y = x - k A x
+    // Reductions.  Single GPU: consumers fold the producers' per-workgroup partials themselves.
+    // Multi-GPU: a one-workgroup fold writes the local sums, RCCL all-reduces them in place on the
+    // compute stream, and consumers read the global scalars (stride 1, one "partial").
+    Comm *comm; bool multi; int g;
+    RowMap rmap;       // row -> workgroup map of the dot-product kernels (gcr_dev.h): depends on how far the operator's rows reach
+    int max_it;        // do..while: at least one iteration
+    // the whole solve in one launch: of one workgroup (gcr_small.hip); with at most one row per thread of the chip, vectors in registers (gcr_resident.hip)
+    bool small, resident;
+    bool flex;
+    bool skip_tail;    // the literal r = M(r) of src/GCR.h:236-238 changes the residual that is recorded: that mode keeps the full last step
     // restart mode with all slots handled by one build launch: defer the x updates of a cycle ...
-    // ... and without the literal hooks (which replace r itself) the cycle runs lean (up to LND slots): see the
-    // file header
-    const bool lean = p.restart != 0 && s->storage <= LND && lean_enabled() && !p.left_precond && (!p.right_precond || flex);
-    const bool defer = lean || (p.restart != 0 && s->storage <= ND);
+    // ... and without the literal hooks (which replace r itself) the cycle runs lean (up to LND slots): see the file header
+    bool lean, defer;
     // A lean solve that ends before its first restart cycle closes (smoothers: 2 sweeps of GCR(10)) never
     // overwrites its first direction and never updates r in place (the residual ring takes the updates): P0
     // simply IS r0 — no copy — and from x0 = 0 r0 IS rhs, in which case |b|^2 = |r0|^2 comes out of the pass
     // that takes <r,Ap> and <Ap,Ap>.
-    const bool alias_p0 = lean && !flex && p.max_iter >= 1 && p.max_iter < p.restart;
-    const bool alias0 = alias_p0 && !p.use_x0;
-    const cplx *p0 = alias0 ? rhs : alias_p0 ? (const cplx *)s->r : (const cplx *)s->ps[0];
+    bool alias_p0, alias0;
+    const cplx *p0;
     // From x0 = 0, a solve that never closes a restart cycle touches x exactly once: flush_x_kernel at the end adds the
     // pending updates.  That kernel can just as well WRITE x = sum alpha_j p_j: no zeroing pass before, no read of x then.
-    const bool assign_x = from_zero && alias_p0 && !p.use_x0;
-    if (from_zero && !assign_x) MGCR_TRY(k_zero_apply(x, n));
-    // operator apply fused with the beta dot products: Sparse / DiracOp in a one-thread-per-row layout
-    // row -> workgroup map of the dot-product kernels (gcr_dev.h): depends on how far the operator's rows reach
-    int64_t reach = 0;
-    {
-        const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
-        if (b0 && b0->kind == OP_CSR) reach = b0->csr.reach;
-    }
-    const RowMap rmap = make_row_map(n, g, reach);
-    bool fuse_ok = false;
-    if ((s->A->kind == OP_CSR || s->A->kind == OP_DIRAC) && !p.left_precond) {
-        const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
-        fuse_ok = b0->kind == OP_CSR && csr_fusable(b0->csr, b0->dist) && b0->csr.nrow == n;
-    }
-    bool xr_fuse = false;   // set below once lean / flex / multi are known
+    bool assign_x;
+    bool fuse_ok;      // operator apply fused with the beta dot products: Sparse / DiracOp in a one-thread-per-row layout (gcr_fused.hip)
     // The plain start of a solve on a fusable Sparse / DiracOp (r0 = p0 = rhs: no x0, no preconditioner): r and p0 are
     // written by ONE kernel from one read of rhs, and Ap_0 = A rhs comes out of the pass that also takes <r0,Ap0>,
     // <Ap0,Ap0> and |r0|^2 = |b|^2 (gcr_fused.hip init_apply_kernel) — 3 launches instead of 6 and 6 V less traffic
     // per solve; same sums in the same order as the separate kernels (test_fused_apply_and_dots_same_bits).  Worth
     // ~45 us per solve, i.e. 2-3 % of a 20-iteration solve at 128^3.
-    const bool fuse_start = fuse_ok && !alias_p0 && !flex && !p.use_x0 && !p.left_precond && !p.right_precond && fuse_init_enabled();
+    bool fuse_start;
+    bool fuse_init;    // step 0 of a smoother-like solve on a fusable Sparse / DiracOp: Ap_0 and its dot products in one pass (gcr_fused.hip)
+    bool xr_fuse;      // latency regime: the residual update runs inside the apply kernel (gcr_fused.hip step_apply_xr*_kernel)
     // ... and where the steps are one launch each (gcr_stepbuild.hip), that start is ONE launch too (start_build_kernel): Ap0 = A b, the
     // sums, |b|^2 / hist[0], alpha and step 1's residual update r1 = b - alpha Ap0.  r and P0 are not copied: cycle 1 reads b where it
     // read them, the closing step reads P0 from b and writes P0' to its slot, flush_x_kernel picks P0 by DevState::closed.  Every
     // closing step of the solve has to be a one-launch step then (that sets `closed`): restart <= 5 directions, all of them stored.
-    bool start1 = false;
-    if (fuse_start && lean && s->restart > 1 && s->restart <= 5 && s->storage >= s->restart && rmap.band == 0 && !graphs_enabled() &&
-        stepbuild_close_enabled() && !(nested && p.max_iter <= 1 && (s->defer_residual || s->discard_residual))) {
-        const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
-        start1 = !csr_xr_fusable(b0->csr, b0->dist) && csr_start_build_eligible(b0->csr, b0->dist) &&
-                 csr_step_build_eligible(b0->csr, b0->dist, s->restart);
+    bool start1;
+    bool use_graph;    // replay a captured restart cycle (gcr_capture_cycle, gcr_loop)
+};
+
+static SolvePlan gcr_plan(const GcrState *s, const cplx *rhs, cplx *x, bool nested, bool from_zero) {
+    const mgcr_gcr_param &p = s->p;
+    const Op *A = s->A, *base = A->kind == OP_DIRAC ? A->base : A;
+    SolvePlan pl{};
+    pl.rhs = rhs; pl.x = x; pl.n = A->dim; pl.nested = nested; pl.from_zero = from_zero;
+    pl.b0 = base && base->kind == OP_CSR ? base : nullptr;
+    pl.shift = A->kind == OP_DIRAC; pl.k = A->k;
+    pl.max_it = p.max_iter > 0 ? p.max_iter : 1;
+    pl.flex = p.flexible && p.right_precond;
+    pl.skip_tail = !p.right_precond || pl.flex;
+    pl.lean = p.restart != 0 && s->storage <= LND && g_lean.on() && !p.left_precond && (!p.right_precond || pl.flex);
+    pl.small = gcr_small_eligible(A, p, s->storage, pl.n);
+    const bool handoff = nested && (s->keep_pending || s->defer_residual);   // callers that take x or r in pieces (V-cycle pre-smoother)
+    pl.resident = !pl.small && !g_graph.on() && gcr_resident_eligible(A, p, s->storage, s->restart, pl.n, pl.lean, handoff);
+    if (pl.small || pl.resident) return pl;   // (one launch for the whole solve: nothing below is consulted)
+    pl.comm = A->kind == OP_DIRAC ? A->base->comm : A->comm;
+    pl.multi = comm_collectives(pl.comm);
+    pl.g = red_grid(pl.n);
+    pl.rmap = make_row_map(pl.n, pl.g, pl.b0 ? pl.b0->csr.reach : 0);
+    pl.defer = pl.lean || (p.restart != 0 && s->storage <= ND);
+    pl.alias_p0 = pl.lean && !pl.flex && p.max_iter >= 1 && p.max_iter < p.restart;
+    pl.alias0 = pl.alias_p0 && !p.use_x0;
+    pl.p0 = pl.alias0 ? rhs : pl.alias_p0 ? (const cplx *)s->r : (const cplx *)s->ps[0];
+    pl.assign_x = from_zero && pl.alias_p0 && !p.use_x0;
+    pl.fuse_ok = pl.b0 && !p.left_precond && csr_fusable(pl.b0->csr, pl.b0->dist) && pl.b0->csr.nrow == pl.n;
+    pl.fuse_start = pl.fuse_ok && !pl.alias_p0 && !pl.flex && !p.use_x0 && !p.left_precond && !p.right_precond && g_fuse_init.on();
+    pl.fuse_init = pl.fuse_ok && pl.alias_p0 && g_fuse_init.on();
+    const bool xr_able = pl.fuse_ok && pl.lean && !pl.flex && s->restart > 1 && csr_xr_fusable(pl.b0->csr, pl.b0->dist);
+    pl.xr_fuse = xr_able && !pl.multi;
+    pl.start1 = pl.fuse_start && pl.lean && s->restart > 1 && s->restart <= 5 && s->storage >= s->restart &&
+                pl.rmap.band == 0 && !g_graph.on() && g_stepbuild_close.on() &&
+                !(nested && p.max_iter <= 1 && (s->defer_residual || s->discard_residual)) && !xr_able &&
+                csr_start_build_eligible(pl.b0->csr, pl.b0->dist) && csr_step_build_eligible(pl.b0->csr, pl.b0->dist, s->restart);
+    pl.use_graph = g_graph.on() && pl.n <= GRAPH_MAX_ROWS && pl.defer && !pl.multi && !p.left_precond && !p.right_precond &&
+                   !p.profile_spmv && pl.max_it >= 2 * s->restart && s->restart <= s->storage;
+    return pl;
+}
+
+// What moves from step to step: the slot ring, where r and P0 live, and where consumers find the newest reductions
+struct StepCursor {
+    int iter_count = 0;   // steps into the current restart cycle
+    int cur = 0;          // slot of the newest direction
+    int global = 0;       // steps enqueued (or replayed) so far
+    const cplx *rcur = nullptr;      // lean: where the current residual lives (s->r at the start of every cycle)
+    const cplx *p0_live = nullptr;   // where the closing step reads P0 (start1: b until cycle 1 closes)
+    bool xr_prefetched = false;      // the next iteration's residual update already ran at the end of this one's launch
+    RedRef refA{}, refR{};
+};
+
+// profile_spmv: 4 events per iteration, around its three phases | xr (+M) | apply + dots | build |
+struct PhaseMarks {
+    bool on = false;
+    std::vector<hipEvent_t> ev;
+    size_t iter0 = 0;
+    bool step_build = false, step_build_xr = false, step_build_close = false;   // one-launch steps seen (g_prof_fused)
+    // phase k of the iteration begins (k = 3: the iteration ends); phases that were skipped get empty intervals
+    int enter(int k) {
+        if (k == 0) iter0 = ev.size();
+        while (on && ev.size() < iter0 + (size_t)k + 1) {
+            hipEvent_t e;
+            MGCR_HIP(hipEventCreate(&e));
+            MGCR_HIP(hipEventRecord(e, ctx().stream));
+            ev.push_back(e);
+        }
+        return MGCR_OK;
     }
-    // r = rhs (src/GCR.h:189); the reference ignores x0 here unless use_x0 is requested
+    int read_out(const SolvePlan &pl) {
+        if (ev.empty()) return MGCR_OK;
+        MGCR_HIP(hipStreamSynchronize(ctx().stream));
+        for (int k = 0; k < 3; k++) g_prof_phase_ms[k] = 0.;
+        for (size_t i = 0; i + 3 < ev.size(); i += 4)
+            for (int k = 0; k < 3; k++) {
+                float ms = 0.f;
+                hipEventElapsedTime(&ms, ev[i + k], ev[i + k + 1]);
+                g_prof_phase_ms[k] += ms;
+            }
+        g_prof_iters = (int)(ev.size() / 4);
+        g_prof_fused = step_build_close ? 4 : step_build_xr ? 3 : step_build ? 2 : (pl.fuse_ok && pl.xr_fuse) ? 5 : pl.fuse_ok ? 1 : 0;
+        for (hipEvent_t e : ev) hipEventDestroy(e);
+        return MGCR_OK;
+    }
+};
+
+// r = rhs (src/GCR.h:189); p = r (or M r); Ap = A p; both go straight into slot 0 (src/GCR.h:190-191,208-211); the literal hooks
+static int start_vectors(GcrState *s, const SolvePlan &pl) {
+    const mgcr_gcr_param &p = s->p;
+    const int64_t n = pl.n;
+    // the reference ignores x0 here unless use_x0 is requested
     if (p.use_x0) {
-        MGCR_TRY(op_residual_raw(s->A, x, rhs, s->r, n));
-    } else if (start1) {
+        MGCR_TRY(op_residual_raw(s->A, pl.x, pl.rhs, s->r, n));
+    } else if (pl.start1) {
         // (r0 = P0 = rhs, read in place)
-    } else if (fuse_start) {
-        hipLaunchKernelGGL(copy2_kernel, dim3(g), dim3(RED_THREADS), 0, c.stream, s->r, s->ps[0], rhs, n, (const DevState *)s->st);
-        MGCR_HIP(hipGetLastError());
-    } else if (!alias0) {
-        MGCR_TRY(k_copy(s->r, rhs, n));
+    } else if (pl.fuse_start) {
+        KLAUNCH(copy2_kernel, pl.g, s->r, s->ps[0], pl.rhs, n, (const DevState *)s->st);
+    } else if (!pl.alias0) {
+        MGCR_TRY(k_copy(s->r, pl.rhs, n));
     }
-    // p = r (or M r); Ap = A p; both go straight into slot 0 (src/GCR.h:190-191,208-211)
-    if (flex) {
+    if (pl.flex) {
         MGCR_TRY(op_apply_raw((Op *)p.right_precond, s->r, s->z, n));
         MGCR_TRY(k_copy(s->ps[0], s->z, n));
-    } else if (!alias_p0 && !fuse_start) {
+    } else if (!pl.alias_p0 && !pl.fuse_start) {
         MGCR_TRY(k_copy(s->ps[0], s->r, n));
     }
-    // step 0 of a smoother-like solve on a fusable Sparse / DiracOp: Ap_0 and its dot products in one pass (gcr_fused.hip)
-    const bool fuse_init = fuse_ok && alias_p0 && fuse_init_enabled();
-    if (!fuse_init && !fuse_start) MGCR_TRY(op_apply_raw(s->A, p0, s->aps[0], n));
-    if (!flex) {  // literal hooks, src/GCR.h:197-204 (after p and Ap were formed)
+    if (!pl.fuse_init && !pl.fuse_start) MGCR_TRY(op_apply_raw(s->A, pl.p0, s->aps[0], n));
+    if (!pl.flex) {  // literal hooks, src/GCR.h:197-204 (after p and Ap were formed)
         if (p.right_precond) { MGCR_TRY(op_apply_raw((Op *)p.right_precond, s->r, s->tmp, n)); std::swap(s->r, s->tmp); }
         if (p.left_precond) { MGCR_TRY(op_apply_raw((Op *)p.left_precond, s->r, s->tmp, n)); std::swap(s->r, s->tmp); }
     }
-    // Reductions.  Single GPU: consumers fold the producers' per-workgroup partials themselves.
-    // Multi-GPU: a one-workgroup fold writes the local sums, RCCL all-reduces them in place on the
-    // compute stream, and consumers read the global scalars (stride 1, one "partial").
-    Comm *comm = s->A->kind == OP_DIRAC ? s->A->base->comm : s->A->comm;
-    const bool multi = comm_collectives(comm);
-    if (fuse_ok && lean && !flex && !multi && s->restart > 1) {
-        const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
-        xr_fuse = csr_xr_fusable(b0->csr, b0->dist);
-    }
-    MGCR_CHECK(!multi || (!p.left_precond && (!p.right_precond || flex)), MGCR_ERR_UNSUPPORTED,
-               "on a distributed operator only flexible right preconditioning is available (set flexible = 1)");
+    return MGCR_OK;
+}
+
+// |b|^2, |r0|^2, <r0,Ap0>, <Ap0,Ap0> in their five forms (the fused ones form Ap_0 as well); *normN: where |b|^2's partials are
+static int start_partials(GcrState *s, const SolvePlan &pl, StepCursor &c, const double **normN) {
+    const int64_t n = pl.n;
+    const int g = pl.g;
+    const cplx *rhs = pl.rhs, *none = nullptr;
     const DevState *cst = s->st;
-    const double *normN = s->partsN;
-    bool xr_prefetched = false;   // the next iteration's residual update already ran at the end of this one's launch
-    if (start1) {
-        const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
-        const int nxt1 = 1 % s->storage;   // where step 1 leaves its residual (one_iteration: dslot)
+    if (pl.start1) {
+        const int nxt1 = 1 % s->storage;   // where step 1 leaves its residual (step_residual_lean: dslot)
         MGCR_TRY(ensure_slot(s, nxt1));
-        MGCR_TRY(csr_start_build(b0->csr, rhs, s->A->kind == OP_DIRAC, s->A->k, s->aps[0], s->st, s->hist, s->lc, s->den,
-                                 nxt1 >= 1 ? s->ps[nxt1] : s->r, s->partsR, rmap));
-        xr_prefetched = true;
-    } else if (fuse_start) {
-        const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
-        MGCR_TRY(csr_init_apply(b0->csr, rhs, s->aps[0], s->A->kind == OP_DIRAC, s->A->k, (const cplx *)nullptr, s->partsA, s->partsR,
-                                s->partsN, b0->dist, rmap));
-    } else if (fuse_init) {
-        const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
-        if (!alias0 && !multi && s->bnorm_src && s->bnorm_src->partsN_of == rhs && s->bnorm_src->partsN_g == g && bnorm_reuse_enabled()) {
-            normN = s->bnorm_src->partsN;   // |b|^2: the partials of the solve that ran on this b just before
-            MGCR_TRY(csr_init_apply(b0->csr, p0, s->aps[0], s->A->kind == OP_DIRAC, s->A->k, (const cplx *)nullptr, s->partsA, s->partsR,
-                                    (double *)nullptr, b0->dist, rmap));
-        } else
-        MGCR_TRY(csr_init_apply(b0->csr, p0, s->aps[0], s->A->kind == OP_DIRAC, s->A->k, alias0 ? (const cplx *)nullptr : rhs, s->partsA,
-                                s->partsR, s->partsN, b0->dist, rmap));
-        if (normN == s->partsN) { s->partsN_of = rhs; s->partsN_g = g; }
-    } else if (alias0) {
+        MGCR_TRY(csr_start_build(pl.b0->csr, rhs, pl.shift, pl.k, s->aps[0], s->st, s->hist, s->lc, s->den, nxt1 >= 1 ? s->ps[nxt1] : s->r,
+                                 s->partsR, pl.rmap));
+        c.xr_prefetched = true;
+    } else if (pl.fuse_start) {
+        MGCR_TRY(csr_init_apply(pl.b0->csr, rhs, s->aps[0], pl.shift, pl.k, none, s->partsA, s->partsR, s->partsN, pl.b0->dist, pl.rmap));
+    } else if (pl.fuse_init) {
+        const GcrState *src = s->bnorm_src;
+        double *partsN = s->partsN;
+        if (!pl.alias0 && !pl.multi && src && src->partsN_of == rhs && src->partsN_g == g && g_bnorm_reuse.on()) {
+            *normN = src->partsN;   // |b|^2: the partials of the solve that ran on this b just before
+            partsN = nullptr;
+        }
+        MGCR_TRY(csr_init_apply(pl.b0->csr, pl.p0, s->aps[0], pl.shift, pl.k, (pl.alias0 || !partsN) ? none : rhs, s->partsA, s->partsR, partsN,
+                                pl.b0->dist, pl.rmap));
+        if (partsN) { s->partsN_of = rhs; s->partsN_g = g; }
+    } else if (pl.alias0) {
         KLAUNCH(init3_partials_kernel, g, rhs, (const cplx *)s->aps[0], n, s->partsN, s->partsR, s->partsA, cst, 0);
-    } else if (alias_p0) {
+    } else if (pl.alias_p0) {
         KLAUNCH(norm_partials_kernel, g, rhs, n, s->partsN, cst, 0);
         KLAUNCH(init3_partials_kernel, g, (const cplx *)s->r, (const cplx *)s->aps[0], n, (double *)nullptr, s->partsR, s->partsA, cst, 0);
     } else {
@@ -1274,345 +1190,424 @@ static int gcr_run_once(GcrState *s, const cplx *rhs, cplx *x, bool nested, doub
         KLAUNCH(norm_partials_kernel, g, (const cplx *)s->r, n, s->partsR, cst, 0);
         KLAUNCH(dot2_partials_kernel, g, (const cplx *)s->r, (const cplx *)s->aps[0], n, s->partsA, cst, 0);
     }
-    RedRef refA = {s->partsA, g, RED_MAX_BLOCKS}, refR = {s->partsR, g, RED_MAX_BLOCKS};
-    if (multi) {
-        MGCR_TRY(comm_fold_allreduce(comm, s->partsN, 1, s->partsR, 1, s->dN, g));
-        MGCR_TRY(comm_fold_allreduce(comm, s->partsA, 4, nullptr, 0, s->dA, g));
+    return MGCR_OK;
+}
+
+// step 0: r, P0, Ap_0, the initial reductions and the step's bookkeeping; leaves the cursor at the first iteration
+static int gcr_start(GcrState *s, const SolvePlan &pl, StepCursor &c) {
+    const mgcr_gcr_param &p = s->p;
+    const int g = pl.g;
+    MGCR_TRY(start_vectors(s, pl));
+    MGCR_CHECK(!pl.multi || (!p.left_precond && (!p.right_precond || pl.flex)), MGCR_ERR_UNSUPPORTED,
+               "on a distributed operator only flexible right preconditioning is available (set flexible = 1)");
+    const double *normN = s->partsN;
+    MGCR_TRY(start_partials(s, pl, c, &normN));
+    c.refA = {s->partsA, g, RED_MAX_BLOCKS};
+    c.refR = {s->partsR, g, RED_MAX_BLOCKS};
+    if (pl.multi) {
+        MGCR_TRY(comm_fold_allreduce(pl.comm, s->partsN, 1, s->partsR, 1, s->dN, g));
+        MGCR_TRY(comm_fold_allreduce(pl.comm, s->partsA, 4, nullptr, 0, s->dA, g));
         KLAUNCH(init_kernel, 1, s->st, (const double *)s->dN, 1, 1, (const double *)(s->dN + 1), 1, 1, s->hist);
-        refA = {s->dA, 1, 1};
-        refR = {s->dRB, 1, 1};
-    } else if (!start1) {
+        c.refA = {s->dA, 1, 1};
+        c.refR = {s->dRB, 1, 1};
+    } else if (!pl.start1) {
         KLAUNCH(init_kernel, 1, s->st, normN, g, RED_MAX_BLOCKS, (const double *)s->partsR, g, RED_MAX_BLOCKS, s->hist);
     }
-
-    const int max_it = p.max_iter > 0 ? p.max_iter : 1;  // do..while: at least one iteration
-    // the literal r = M(r) of src/GCR.h:236-238 changes the residual that is recorded: that mode keeps the full last step
-    const bool skip_tail = !p.right_precond || flex;
+    c.rcur = (pl.alias0 || pl.start1) ? pl.rhs : s->r;
+    c.p0_live = pl.start1 ? pl.rhs : (const cplx *)s->ps[0];
     // where each step leaves the (true recurrence) residual — not with the literal hooks, which replace r by M r
     s->r_after.clear();
-    if (!p.left_precond && (!p.right_precond || flex) && max_it <= LND) s->r_after.assign((size_t)max_it + 1, nullptr);
-    int check_every = p.check_every > 0 ? p.check_every : 10;
-    const cplx *rcur = (alias0 || start1) ? rhs : s->r;  // lean: where the current residual lives (s->r at the start of every cycle)
-    const cplx *p0_live = start1 ? rhs : (const cplx *)s->ps[0];   // where the closing step reads P0 (start1: b until cycle 1 closes)
-    int iter_count = 0, cur = 0, global = 0;
-    bool done = false;
-    std::vector<hipEvent_t> prof_events;
-    bool prof_step_build = false, prof_step_build_xr = false, prof_step_build_close = false;
-    // one iteration, enqueued on the library stream; `it` = iteration number relative to DevState::base
-    auto one_iteration = [&](int it, bool last = false) -> int {
-        iter_count++;
-        set_apply_skip(SkipRef{&s->st->stop_at, it});
-        auto mark = [&]() -> int {
-            if (!(p.profile_spmv && !nested)) return MGCR_OK;
-            hipEvent_t e;
-            MGCR_HIP(hipEventCreate(&e));
-            MGCR_HIP(hipEventRecord(e, c.stream));
-            prof_events.push_back(e);
-            return MGCR_OK;
-        };
-        MGCR_TRY(mark());  // 4 events per iteration: | xr (+M) | apply + dots | build |
-        // slot the new direction goes to (src/GCR.h:277-287)
-        const int lim = s->storage < iter_count ? s->storage : iter_count;  // src/GCR.h:251
-        int ic_next = iter_count;
-        if (iter_count % s->restart == 0) ic_next = 0;
-        const int nxt = ic_next % s->storage;
-        MGCR_TRY(ensure_slot(s, nxt));
-        // alpha, x, r
-        const cplx *dir;
-        bool xr_now = false;
-        const cplx *xr_in = nullptr;
-        if (lean) {
-            // D_nxt, what direction nxt is started from, lands in the p slot of that direction (nxt >= 1);
-            // the step that closes the cycle only needs it for its own build
-            cplx *dslot = nxt >= 1 ? s->ps[nxt] : (flex ? s->z : s->r);
-            cplx *r_out = flex ? s->r : dslot;
-            if (last && skip_tail && nested && s->defer_residual && !multi && !flex && !s->r_after.empty()) {
-                // the caller forms this step's residual itself, from the previous one, Ap and alpha (ResidualSel)
-                KLAUNCH(alpha_only_kernel, 1, s->st, it, refA.p, refA.nblk, refA.stride, s->den + cur, cur, s->lc, s->alphas + cur);
-                s->defer_r_prev = rcur; s->defer_ap = s->aps[cur]; s->defer_alpha = s->alphas + cur; s->defer_it = global;
-                s->r_after[(size_t)global] = rcur;   // placeholder: never read (st->iter == defer_it takes the on-the-fly path)
-                for (int k = 0; k < 3; k++) MGCR_TRY(mark());
-                iter_count = ic_next;
-                cur = nxt;
-                return MGCR_OK;
-            }
-            if (last && skip_tail && nested && s->discard_residual && !multi) {
-                KLAUNCH(alpha_only_kernel, 1, s->st, it, refA.p, refA.nblk, refA.stride, s->den + cur, cur, s->lc, (cplx *)nullptr);
-                s->r_after.clear();
-                for (int k = 0; k < 3; k++) MGCR_TRY(mark());
-                iter_count = ic_next;
-                cur = nxt;
-                return MGCR_OK;
-            }
-            xr_now = xr_fuse && !(last && skip_tail);   // latency regime: the update runs inside the apply kernel below
-            xr_in = rcur;
-            if (xr_prefetched) xr_prefetched = false;   // the previous step's launch ended with this update (gcr_stepbuild.hip)
-            else if (!xr_now)
-            KLAUNCH((xr_update_kernel<true, true>), g, s->st, it, refA.p, refA.nblk, refA.stride, (const cplx *)nullptr,
-                    (const cplx *)s->aps[cur], x, rcur, r_out, n, s->partsR, s->den + cur, s->alphas, cur, s->lc);
-            rcur = r_out;
-            dir = r_out;
-            if (flex && !(last && skip_tail)) {
-                MGCR_TRY(op_apply_raw((Op *)p.right_precond, s->r, dslot, n));
-                dir = dslot;
-            }
-        } else {
-        if (defer)
-            KLAUNCH((xr_update_kernel<true, false>), g, s->st, it, refA.p, refA.nblk, refA.stride, (const cplx *)s->ps[cur],
-                    (const cplx *)s->aps[cur], x, (const cplx *)s->r, s->r, n, s->partsR, s->den + cur, s->alphas, cur, s->lc);
-        else
-            KLAUNCH((xr_update_kernel<false, false>), g, s->st, it, refA.p, refA.nblk, refA.stride, (const cplx *)s->ps[cur],
-                    (const cplx *)s->aps[cur], x, (const cplx *)s->r, s->r, n, s->partsR, s->den + cur, s->alphas, cur, s->lc);
-        dir = s->r;
-        if (flex && !(last && skip_tail)) {
-            MGCR_TRY(op_apply_raw((Op *)p.right_precond, s->r, s->z, n));
-            dir = s->z;
-        } else if (p.right_precond && !flex) {  // src/GCR.h:236-238
-            MGCR_TRY(op_apply_raw((Op *)p.right_precond, s->r, s->tmp, n));
-            std::swap(s->r, s->tmp);
-            dir = s->r;
-            KLAUNCH(norm_partials_kernel, g, (const cplx *)s->r, n, s->partsR, cst, it);
-        }
-        }
-        if (!s->r_after.empty() && global < (int)s->r_after.size()) s->r_after[(size_t)global] = lean ? rcur : (const cplx *)s->r;
-        if (last && skip_tail) {
-            // nothing after this iteration: no preconditioner apply, no A r, no beta dots, no direction build — only the
-            // step's bookkeeping (the x updates still pending are applied by flush_x_kernel below)
-            MGCR_TRY(mark());
-            MGCR_TRY(mark());
-            RedRef fr = refR;
-            if (multi) {
-                MGCR_TRY(comm_fold_allreduce(comm, s->partsR, 1, nullptr, 0, s->dRB, g));
-                fr = {s->dRB, 1, 1};
-            }
-            KLAUNCH(finish_step_kernel, 1, s->st, it, fr.p, fr.nblk, fr.stride, s->hist, s->hist_cap);
-            MGCR_TRY(mark());
-            iter_count = ic_next;
-            cur = nxt;
-            return MGCR_OK;
-        }
-        MGCR_TRY(mark());
-        const int nchunk = (lim + ND - 1) / ND;
-        int ch0 = 0;
-        // apply + dots + build in ONE launch (gcr_stepbuild.hip) where A r of a thread's rows fits LDS: not the step that closes a cycle
-        bool step_build = false;
-        const bool closes = ic_next == 0;   // (lim == restart then; up to 5 directions the closing step has its one-launch form too)
-        if (fuse_ok && lean && !flex && !multi && !xr_now && rmap.band == 0 && (!closes || stepbuild_close_enabled()) &&
-            !graphs_enabled()) {   // (a captured cycle would replay the exchange's generation numbers)
-            const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
-            step_build = csr_step_build_eligible(b0->csr, b0->dist, lim);
-        }
-        if (step_build) {
-            prof_step_build = true;
-            const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
-            const cplx *vecs[FND];
-            for (int j = 0; j < FND; j++) vecs[j] = s->aps[j < lim ? j : 0];
-            // ... and, unless the next step is the solve's last (whose update takes other kernels), that step's residual update too:
-            // r and the new Ap of a thread's rows are on the chip, alpha costs one more exchange instead of a launch
-            cplx *xr_out = nullptr;
-            const bool next_is_special_last = global + 1 == max_it && nested && (s->defer_residual || s->discard_residual);
-            if (global + 1 <= max_it && !next_is_special_last && stepbuild_xr_enabled()) {
-                const int ic2 = ((ic_next + 1) % s->restart == 0) ? 0 : ic_next + 1;
-                const int nxt2 = ic2 % s->storage;
-                MGCR_TRY(ensure_slot(s, nxt2));
-                xr_out = nxt2 >= 1 ? s->ps[nxt2] : s->r;
-            }
-            const cplx *cps[FND];
-            for (int j = 0; j < FND; j++) cps[j] = j < lim && j > 0 ? s->ps[j] : p0_live;
-            MGCR_TRY(csr_step_build(b0->csr, dir, s->A->kind == OP_DIRAC, s->A->k, vecs, lim, s->st, it, refR.p, refR.nblk, refR.stride, s->hist,
-                                    s->hist_cap, s->den, s->aps[nxt], s->partsA, s->lc, rmap, xr_out, s->den + nxt, nxt, s->partsR,
-                                    closes ? cps : nullptr, closes ? s->ps[0] : nullptr, closes ? x : nullptr));
-            xr_prefetched = xr_out != nullptr;
-            prof_step_build_xr = prof_step_build_xr || xr_prefetched;
-            prof_step_build_close = prof_step_build_close || closes;
-            if (closes) p0_live = s->ps[0];
-            MGCR_TRY(mark());
-            MGCR_TRY(mark());
-            iter_count = ic_next;
-            cur = nxt;
-            return MGCR_OK;
-        }
-        bool tail_rb = false;   // the fold + exchange of |r|^2 and the beta numerators ran inside the apply kernel
-        if (fuse_ok) {
-            // Ar = A dir and the <Ar, Aps_j> partials of the first FND = 10 stored directions in one pass (gcr_fused.hip);
-            // with more than that (restart > 10) multidot_kernel takes directions 8.. in its chunks of ND = 8 (8 and 9 twice:
-            // the same sums, the same bits)
-            const int nf = lim < FND ? lim : FND;
-            const cplx *vecs[FND];
-            for (int j = 0; j < FND; j++) vecs[j] = s->aps[j < nf ? j : 0];
-            const Op *b0 = s->A->kind == OP_DIRAC ? s->A->base : s->A;
-            if (xr_now)
-                MGCR_TRY(csr_step_apply_xr(b0->csr, xr_in, s->aps[cur], const_cast<cplx *>(dir), s->ar, s->A->kind == OP_DIRAC, s->A->k, vecs,
-                                           nf, s->partsB, s->partsR, s->st, it, refA.p, refA.nblk, refA.stride, s->den + cur, cur, s->lc, rmap));
-            else {
-                // multi-GPU, scalars by peer writes: the apply kernel's last workgroup folds |r|^2 (the residual update's partials)
-                // and the beta numerators and sums them over the ranks — no fold + exchange launch behind it (pw_tail_dev.h)
-                PwTail pw;
-                if (multi && lim <= FND && csr_step_apply_has_pw_tail(b0->csr, b0->dist) && comm_pw_tail_begin(comm, &pw)) {
-                    pw.pa = s->partsR; pw.na = 1; pw.pb = s->partsB; pw.nb = 2 * lim; pw.out = s->dRB; pw.nblk = g;
-                    MGCR_TRY(csr_step_apply(b0->csr, dir, s->ar, s->A->kind == OP_DIRAC, s->A->k, vecs, nf, s->partsB, b0->dist, rmap, &pw));
-                    tail_rb = true;
-                } else
-                MGCR_TRY(csr_step_apply(b0->csr, dir, s->ar, s->A->kind == OP_DIRAC, s->A->k, vecs, nf, s->partsB, b0->dist, rmap));
-            }
-            ch0 = lim <= FND ? nchunk : 1;
-        } else {
-            MGCR_TRY(op_apply_raw(s->A, dir, s->ar, n));  // src/GCR.h:242
-            if (p.left_precond) {                         // src/GCR.h:245-247
-                MGCR_TRY(op_apply_raw((Op *)p.left_precond, s->ar, s->tmp, n));
-                std::swap(s->ar, s->tmp);
-            }
-        }
-        for (int ch = ch0; ch < nchunk; ch++) {
-            DirPtrs d;
-            int nd = lim - ch * ND < ND ? lim - ch * ND : ND;
-            for (int j = 0; j < ND; j++) {
-                int sl = ch * ND + (j < nd ? j : 0);
-                d.ps[j] = s->ps[sl]; d.aps[j] = s->aps[sl]; d.slot[j] = sl;
-            }
-            MGCR_TRY(launch_multidot(g, nd, cst, it, (const cplx *)s->ar, d, ch * ND, n, s->partsB, rmap));
-        }
-        MGCR_TRY(mark());
-        bool tail_a = false;    // ... and that of <r,Ap'>, <Ap',Ap'> inside the build kernel
-        RedRef refB = {s->partsB, g, RED_MAX_BLOCKS};
-        if (multi) {  // one all-reduce for |r|^2 and all beta numerators of the step
-            if (!tail_rb) MGCR_TRY(comm_fold_allreduce(comm, s->partsR, 1, s->partsB, 2 * lim, s->dRB, g));
-            refB = {s->dRB + 1, 1, 1};
-        }
-        // (start1 makes every closing step a one-launch step: P0 is read from b only there)
-        MGCR_CHECK(!(start1 && ic_next == 0 && p0_live != s->ps[0]), MGCR_ERR_INVALID, "gcr: a cycle closed off the one-launch path after a one-launch start");
-        if (lean) {
-            LeanArgs a;
-            a.g = g; a.nd = lim; a.rdir = flex; a.st = s->st; a.it = it; a.B = refB; a.R = refR; a.hist = s->hist;
-            a.hist_cap = s->hist_cap; a.den = s->den;
-            for (int j = 0; j < LND; j++) { int sl = j < lim ? j : 0; a.d.ps[j] = s->ps[sl]; a.d.aps[j] = s->aps[sl]; a.d.slot[j] = sl; }
-            a.dir = dir; a.r = rcur; a.ar = s->ar; a.p_out = s->ps[0]; a.ap_out = s->aps[nxt]; a.n = n; a.partsA = s->partsA;
-            a.x = x; a.lc = s->lc;
-            PwTail pwa;
-            if (multi && lim <= ND && comm_pw_tail_begin(comm, &pwa)) {   // the build kernel folds and exchanges <r,Ap'>, <Ap',Ap'> itself
-                pwa.pa = s->partsA; pwa.na = 4; pwa.pb = nullptr; pwa.nb = 0; pwa.out = s->dA; pwa.nblk = g;
-                a.pw = &pwa;
-                tail_a = true;
-            }
-            if (ic_next != 0) {
-                // the next step is the solve's last and all it takes from this one are <r,Ap'>, <Ap',Ap'> (alpha_only_kernel: the caller — a
-                // post-smoother's, a coarsest solve's — discards the residual): Ap' itself is never read, so it is not written
-                static const bool skip_dead_ap = !(getenv("MGCR_SKIP_DEAD_AP") && atoi(getenv("MGCR_SKIP_DEAD_AP")) == 0);
-                if (skip_dead_ap && global + 1 == max_it && skip_tail && nested && s->discard_residual && !multi) a.ap_out = nullptr;
-                MGCR_TRY(launch_build_lean(a, 0));              // lim == nxt
-            } else if (lim <= ND) {
-                MGCR_TRY(launch_build_close(a));                // lim == restart: closes the cycle
-            } else {                                            // ... in two kernels when restart > 8
-                MGCR_TRY(launch_close_x(a));
-                MGCR_TRY(launch_build_lean(a, 1));
-            }
-        } else
-        for (int ch = 0; ch < nchunk; ch++) {
-            BuildArgs a;
-            a.g = g;
-            a.nd = lim - ch * ND < ND ? lim - ch * ND : ND;
-            for (int j = 0; j < ND; j++) {
-                int sl = ch * ND + (j < a.nd ? j : 0);
-                a.d.ps[j] = s->ps[sl]; a.d.aps[j] = s->aps[sl]; a.d.slot[j] = sl;
-            }
-            a.first = ch == 0; a.last = ch == nchunk - 1; a.rdir = dir != s->r;
-            // the step that closes a restart cycle streams every ps slot of the cycle: apply the deferred x updates there
-            a.xupd = defer && ic_next == 0;
-            a.st = s->st; a.it = it; a.B = refB; a.book = a.last ? 1 : 0; a.R = refR; a.hist = s->hist; a.hist_cap = s->hist_cap;
-            a.den = s->den; a.base = ch * ND; a.dir = dir; a.r = s->r; a.ar = s->ar; a.accp = s->accp; a.accap = s->accap;
-            a.p_out = s->ps[nxt]; a.ap_out = s->aps[nxt]; a.n = n; a.partsA = s->partsA; a.x = x; a.alphas = s->alphas;
-            MGCR_TRY(launch_build(a));
-        }
-        if (multi && !tail_a) {
-            MGCR_TRY(comm_fold_allreduce(comm, s->partsA, 4, nullptr, 0, s->dA, g));
-        }
-        MGCR_TRY(mark());
-        iter_count = ic_next;
-        cur = nxt;
-        return MGCR_OK;
-    };
+    if (!p.left_precond && (!p.right_precond || pl.flex) && pl.max_it <= LND) s->r_after.assign((size_t)pl.max_it + 1, nullptr);
+    return MGCR_OK;
+}
 
-    // hipGraph (opt-in, MGCR_GRAPH=1): in restart mode every cycle of R iterations is the same launch sequence with the
-    // same arguments (iteration numbers are base-relative, base lives on the device), so one cycle can be captured once
-    // and replayed.  Measured on MI355X: +11 % iterations/s on the 3072-row sample while an iteration was 4 launches;
-    // since it shrank to 3 (fused apply + dots) replay no longer pays at any size — eager launches run 1-4 % FASTER
-    // from 512 to 1.4 M rows (e.g. 64^3: 33.6 k against 32.3 k it/s), equal on the sample: the loop is bound by the
-    // GPU-side dependency between consecutive short kernels (~8 us each), not by the host's launch cost.  Hence off
-    // by default, and gated to <= 2^18 rows when on.
-    const int R = s->restart;
-    bool use_graph = graphs_enabled() && n <= GRAPH_MAX_ROWS && defer && !multi && !p.left_precond && !p.right_precond &&
-                     !p.profile_spmv && max_it >= 2 * R && R <= s->storage;
-    if (use_graph) s->r_after.clear();   // replayed cycles do not pass through the host-side step counter
-    if (use_graph && (s->graph_exec == nullptr || s->graph_x != x || s->graph_R != R || s->graph_n != n)) {
-        if (s->graph_exec) { hipGraphExecDestroy(s->graph_exec); s->graph_exec = nullptr; }
-        hipGraph_t graph = nullptr;
-        MGCR_HIP(hipStreamBeginCapture(c.stream, hipStreamCaptureModeThreadLocal));
-        int rc = MGCR_OK;
-        for (int i = 1; i <= R && rc == MGCR_OK; i++) rc = one_iteration(i);
-        if (rc == MGCR_OK) {
-            hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, c.stream, s->st, R);
+// One iteration's constants (from the cursor) and what its phases hand to each other
+struct Step {
+    int it;         // iteration number relative to DevState::base
+    bool tail;      // the last iteration the solve can run, and nothing of the next direction is wanted (skip_tail)
+    int lim;        // stored directions, src/GCR.h:251
+    int ic_next;    // iter_count after this step (0: the step closes a restart cycle)
+    int nxt;        // slot the new direction goes to (src/GCR.h:277-287)
+    const cplx *dir = nullptr;     // what the new direction is started from: r, or M r
+    bool xr_now = false;           // the residual update runs inside the apply kernel
+    const cplx *xr_in = nullptr;   // ... from this residual
+    bool ended = false;            // the residual update was all this step had to do (alpha_only_kernel)
+};
+
+// alpha, x, r of a lean step (r goes to the residual ring); with both endings of a nested solve whose caller does not want the last residual
+static int step_residual_lean(GcrState *s, const SolvePlan &pl, StepCursor &c, Step &st) {
+    const int cur = c.cur;
+    // D_nxt, what direction nxt is started from, lands in the p slot of that direction (nxt >= 1);
+    // the step that closes the cycle only needs it for its own build
+    cplx *dslot = st.nxt >= 1 ? s->ps[st.nxt] : (pl.flex ? s->z : s->r);
+    cplx *r_out = pl.flex ? s->r : dslot;
+    const bool alpha_only = st.tail && pl.nested && !pl.multi;   // a nested solve's last step whose caller does not read its residual:
+    const bool deferred = alpha_only && s->defer_residual && !pl.flex && !s->r_after.empty();   // ... it forms it itself (ResidualSel)
+    if (deferred || (alpha_only && s->discard_residual)) {
+        KLAUNCH(alpha_only_kernel, 1, s->st, st.it, c.refA.p, c.refA.nblk, c.refA.stride, s->den + cur, cur, s->lc,
+                deferred ? s->alphas + cur : (cplx *)nullptr);
+        if (deferred) {   // from the previous residual, Ap and alpha
+            s->defer_r_prev = c.rcur; s->defer_ap = s->aps[cur]; s->defer_alpha = s->alphas + cur; s->defer_it = c.global;
+            s->r_after[(size_t)c.global] = c.rcur;   // placeholder: never read (st->iter == defer_it takes the on-the-fly path)
+        } else {
+            s->r_after.clear();
         }
-        hipError_t e = hipStreamEndCapture(c.stream, &graph);
-        if (rc != MGCR_OK) { if (graph) hipGraphDestroy(graph); return rc; }
-        MGCR_HIP(e);
-        e = hipGraphInstantiate(&s->graph_exec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        MGCR_HIP(e);
-        s->graph_x = x; s->graph_R = R; s->graph_n = n;
-        // the capture pass walked the host-side cycle state through one full cycle: back at its start
+        st.ended = true;
+        return MGCR_OK;
     }
+    st.xr_now = pl.xr_fuse && !st.tail;
+    st.xr_in = c.rcur;
+    if (c.xr_prefetched) c.xr_prefetched = false;   // the previous step's launch ended with this update (gcr_stepbuild.hip)
+    else if (!st.xr_now)
+        KLAUNCH((xr_update_kernel<true, true>), pl.g, s->st, st.it, c.refA.p, c.refA.nblk, c.refA.stride, (const cplx *)nullptr,
+                (const cplx *)s->aps[cur], pl.x, c.rcur, r_out, pl.n, s->partsR, s->den + cur, s->alphas, cur, s->lc);
+    c.rcur = r_out;
+    st.dir = r_out;
+    if (pl.flex && !st.tail) {
+        MGCR_TRY(op_apply_raw((Op *)s->p.right_precond, s->r, dslot, pl.n));
+        st.dir = dslot;
+    }
+    return MGCR_OK;
+}
+
+// alpha, x, r of a classic step (r in place), and the preconditioner: flexible, or the literal hook
+static int step_residual_classic(GcrState *s, const SolvePlan &pl, StepCursor &c, Step &st) {
+    const mgcr_gcr_param &p = s->p;
+    const int cur = c.cur;
+    MGCR_TRY(dispatch_bool(pl.defer, [&](auto D) -> int {
+        KLAUNCH((xr_update_kernel<decltype(D)::value, false>), pl.g, s->st, st.it, c.refA.p, c.refA.nblk, c.refA.stride,
+                (const cplx *)s->ps[cur], (const cplx *)s->aps[cur], pl.x, (const cplx *)s->r, s->r, pl.n, s->partsR, s->den + cur, s->alphas,
+                cur, s->lc);
+        return MGCR_OK;
+    }));
+    st.dir = s->r;
+    if (pl.flex && !st.tail) {
+        MGCR_TRY(op_apply_raw((Op *)p.right_precond, s->r, s->z, pl.n));
+        st.dir = s->z;
+    } else if (p.right_precond && !pl.flex) {  // src/GCR.h:236-238
+        MGCR_TRY(op_apply_raw((Op *)p.right_precond, s->r, s->tmp, pl.n));
+        std::swap(s->r, s->tmp);
+        st.dir = s->r;
+        KLAUNCH(norm_partials_kernel, pl.g, (const cplx *)s->r, pl.n, s->partsR, (const DevState *)s->st, st.it);
+    }
+    return MGCR_OK;
+}
+
+// Nothing after the solve's last iteration: no preconditioner apply, no A r, no beta dots, no direction build — only the
+// step's bookkeeping (the x updates still pending are applied by flush_x_kernel)
+static int step_finish(GcrState *s, const SolvePlan &pl, const StepCursor &c, const Step &st) {
+    RedRef fr = c.refR;
+    if (pl.multi) {
+        MGCR_TRY(comm_fold_allreduce(pl.comm, s->partsR, 1, nullptr, 0, s->dRB, pl.g));
+        fr = {s->dRB, 1, 1};
+    }
+    KLAUNCH(finish_step_kernel, 1, s->st, st.it, fr.p, fr.nblk, fr.stride, s->hist, s->hist_cap);
+    return MGCR_OK;
+}
+
+// apply + dots + build in ONE launch (gcr_stepbuild.hip) where A r of a thread's rows fits LDS; up to 5 directions the step
+// that closes a cycle has its one-launch form too
+static bool step_is_one_launch(const SolvePlan &pl, const Step &st) {
+    return pl.fuse_ok && pl.lean && !pl.flex && !pl.multi && !st.xr_now && pl.rmap.band == 0 &&
+           (st.ic_next != 0 || g_stepbuild_close.on()) && !g_graph.on() &&   // (a captured cycle would replay the exchange's generation numbers)
+           csr_step_build_eligible(pl.b0->csr, pl.b0->dist, st.lim);
+}
+static int step_one_launch(GcrState *s, const SolvePlan &pl, StepCursor &c, PhaseMarks &marks, const Step &st) {
+    const int lim = st.lim;
+    const bool closes = st.ic_next == 0;   // (lim == restart then)
+    const cplx *vecs[FND], *cps[FND];
+    for (int j = 0; j < FND; j++) { vecs[j] = s->aps[j < lim ? j : 0]; cps[j] = j < lim && j > 0 ? s->ps[j] : c.p0_live; }
+    // ... and, unless the next step is the solve's last (whose update takes other kernels), that step's residual update too:
+    // r and the new Ap of a thread's rows are on the chip, alpha costs one more exchange instead of a launch
+    cplx *xr_out = nullptr;
+    const bool next_is_special_last = c.global + 1 == pl.max_it && pl.nested && (s->defer_residual || s->discard_residual);
+    if (c.global + 1 <= pl.max_it && !next_is_special_last && g_stepbuild_xr.on()) {
+        const int ic2 = ((st.ic_next + 1) % s->restart == 0) ? 0 : st.ic_next + 1;
+        const int nxt2 = ic2 % s->storage;
+        MGCR_TRY(ensure_slot(s, nxt2));
+        xr_out = nxt2 >= 1 ? s->ps[nxt2] : s->r;
+    }
+    MGCR_TRY(csr_step_build(pl.b0->csr, st.dir, pl.shift, pl.k, vecs, lim, s->st, st.it, c.refR.p, c.refR.nblk, c.refR.stride, s->hist,
+                            s->hist_cap, s->den, s->aps[st.nxt], s->partsA, s->lc, pl.rmap, xr_out, s->den + st.nxt, st.nxt, s->partsR,
+                            closes ? cps : nullptr, closes ? s->ps[0] : nullptr, closes ? pl.x : nullptr));
+    c.xr_prefetched = xr_out != nullptr;
+    marks.step_build = true;
+    marks.step_build_xr = marks.step_build_xr || c.xr_prefetched;
+    marks.step_build_close = marks.step_build_close || closes;
+    if (closes) c.p0_live = s->ps[0];
+    return MGCR_OK;
+}
+
+// Ar = A dir (+ the literal left hook) and the <Ar, Aps_j> partials; *tail_rb: the fold + exchange of |r|^2 and the beta
+// numerators ran inside the apply kernel
+static int step_apply_dots(GcrState *s, const SolvePlan &pl, const StepCursor &c, const Step &st, bool *tail_rb) {
+    const int lim = st.lim, nchunk = (lim + ND - 1) / ND;
+    int ch0 = 0;
+    if (pl.fuse_ok) {
+        // Ar = A dir and the <Ar, Aps_j> partials of the first FND = 10 stored directions in one pass (gcr_fused.hip);
+        // with more than that (restart > 10) multidot_kernel takes directions 8.. in its chunks of ND = 8 (8 and 9 twice:
+        // the same sums, the same bits)
+        const int nf = lim < FND ? lim : FND;
+        const cplx *vecs[FND];
+        for (int j = 0; j < FND; j++) vecs[j] = s->aps[j < nf ? j : 0];
+        const CsrDev &M = pl.b0->csr;
+        DistCsr *dist = pl.b0->dist;
+        // multi-GPU, scalars by peer writes: the apply kernel's last workgroup folds |r|^2 (the residual update's partials)
+        // and the beta numerators and sums them over the ranks — no fold + exchange launch behind it (pw_tail_dev.h)
+        PwTail pw;
+        if (st.xr_now) {
+            MGCR_TRY(csr_step_apply_xr(M, st.xr_in, s->aps[c.cur], const_cast<cplx *>(st.dir), s->ar, pl.shift, pl.k, vecs, nf, s->partsB,
+                                       s->partsR, s->st, st.it, c.refA.p, c.refA.nblk, c.refA.stride, s->den + c.cur, c.cur, s->lc, pl.rmap));
+        } else {
+            *tail_rb = pl.multi && lim <= FND && csr_step_apply_has_pw_tail(M, dist) && comm_pw_tail_begin(pl.comm, &pw);
+            if (*tail_rb) { pw.pa = s->partsR; pw.na = 1; pw.pb = s->partsB; pw.nb = 2 * lim; pw.out = s->dRB; pw.nblk = pl.g; }
+            MGCR_TRY(csr_step_apply(M, st.dir, s->ar, pl.shift, pl.k, vecs, nf, s->partsB, dist, pl.rmap, *tail_rb ? &pw : nullptr));
+        }
+        ch0 = lim <= FND ? nchunk : 1;
+    } else {
+        MGCR_TRY(op_apply_raw(s->A, st.dir, s->ar, pl.n));  // src/GCR.h:242
+        if (s->p.left_precond) {                            // src/GCR.h:245-247
+            MGCR_TRY(op_apply_raw((Op *)s->p.left_precond, s->ar, s->tmp, pl.n));
+            std::swap(s->ar, s->tmp);
+        }
+    }
+    for (int ch = ch0; ch < nchunk; ch++) {
+        DirPtrs d;
+        const int nd = lim - ch * ND < ND ? lim - ch * ND : ND;
+        fill_dirs(d, s, ch * ND, nd, ND);
+        MGCR_TRY((dispatch_nd<1, ND>(nd, [&](auto N) -> int {
+            constexpr int NDT = decltype(N)::value;
+            KLAUNCH((multidot_kernel<NDT, (NDT <= 2 ? 2 : 1)>), pl.g, (const DevState *)s->st, st.it, (const cplx *)s->ar, d, ch * ND, pl.n,
+                    pl.rmap, s->partsB);
+            return MGCR_OK;
+        })));
+    }
+    return MGCR_OK;
+}
+
+// the lean build: inside a cycle (build_lean_kernel), or closing it in one kernel or, with restart > 8, in two;
+// *tail_a: the build kernel folded and exchanged <r,Ap'>, <Ap',Ap'> itself
+static int step_build_lean(GcrState *s, const SolvePlan &pl, const StepCursor &c, const Step &st, RedRef refB, bool *tail_a) {
+    const int lim = st.lim;
+    LeanArgs a;
+    a.g = pl.g; a.nd = lim; a.rdir = pl.flex; a.st = s->st; a.it = st.it; a.B = refB; a.R = c.refR; a.hist = s->hist;
+    a.hist_cap = s->hist_cap; a.den = s->den;
+    fill_dirs(a.d, s, 0, lim, LND);
+    a.dir = st.dir; a.r = c.rcur; a.ar = s->ar; a.p_out = s->ps[0]; a.ap_out = s->aps[st.nxt]; a.n = pl.n; a.partsA = s->partsA;
+    a.x = pl.x; a.lc = s->lc;
+    PwTail pwa;
+    if (pl.multi && lim <= ND && comm_pw_tail_begin(pl.comm, &pwa)) {
+        pwa.pa = s->partsA; pwa.na = 4; pwa.pb = nullptr; pwa.nb = 0; pwa.out = s->dA; pwa.nblk = pl.g;
+        a.pw = &pwa;
+        *tail_a = true;
+    }
+    if (st.ic_next != 0) {
+        // the next step is the solve's last and all it takes from this one are <r,Ap'>, <Ap',Ap'> (alpha_only_kernel: the caller — a
+        // post-smoother's, a coarsest solve's — discards the residual): Ap' itself is never read, so it is not written
+        if (g_skip_dead_ap.on() && c.global + 1 == pl.max_it && pl.skip_tail && pl.nested && s->discard_residual && !pl.multi)
+            a.ap_out = nullptr;
+        return launch_build_lean(a, 0);     // lim == nxt
+    }
+    if (lim <= ND) return launch_build_close(a);   // lim == restart: closes the cycle
+    MGCR_TRY(launch_close_x(a));                   // ... in two kernels when restart > 8
+    return launch_build_lean(a, 1);
+}
+
+// the classic build: p' and Ap' in chunks of ND stored directions
+static int step_build_classic(GcrState *s, const SolvePlan &pl, const Step &st, RedRef refB, RedRef refR) {
+    const int lim = st.lim, nchunk = (lim + ND - 1) / ND;
+    for (int ch = 0; ch < nchunk; ch++) {
+        BuildArgs a;
+        a.g = pl.g;
+        a.nd = lim - ch * ND < ND ? lim - ch * ND : ND;
+        fill_dirs(a.d, s, ch * ND, a.nd, ND);
+        a.first = ch == 0; a.last = ch == nchunk - 1; a.rdir = st.dir != s->r;
+        // the step that closes a restart cycle streams every ps slot of the cycle: apply the deferred x updates there
+        a.xupd = pl.defer && st.ic_next == 0;
+        a.st = s->st; a.it = st.it; a.B = refB; a.book = a.last ? 1 : 0; a.R = refR; a.hist = s->hist; a.hist_cap = s->hist_cap;
+        a.den = s->den; a.base = ch * ND; a.dir = st.dir; a.r = s->r; a.ar = s->ar; a.accp = s->accp; a.accap = s->accap;
+        a.p_out = s->ps[st.nxt]; a.ap_out = s->aps[st.nxt]; a.n = pl.n; a.partsA = s->partsA; a.x = pl.x; a.alphas = s->alphas;
+        MGCR_TRY(launch_build(a));
+    }
+    return MGCR_OK;
+}
+
+// apply + dots, then the build, with the multi-GPU reductions between and behind them
+static int step_general(GcrState *s, const SolvePlan &pl, StepCursor &c, PhaseMarks &marks, const Step &st) {
+    bool tail_rb = false, tail_a = false;
+    MGCR_TRY(step_apply_dots(s, pl, c, st, &tail_rb));
+    MGCR_TRY(marks.enter(2));
+    RedRef refB = {s->partsB, pl.g, RED_MAX_BLOCKS};
+    if (pl.multi) {  // one all-reduce for |r|^2 and all beta numerators of the step
+        if (!tail_rb) MGCR_TRY(comm_fold_allreduce(pl.comm, s->partsR, 1, s->partsB, 2 * st.lim, s->dRB, pl.g));
+        refB = {s->dRB + 1, 1, 1};
+    }
+    // (start1 makes every closing step a one-launch step: P0 is read from b only there)
+    MGCR_CHECK(!(pl.start1 && st.ic_next == 0 && c.p0_live != s->ps[0]), MGCR_ERR_INVALID,
+               "gcr: a cycle closed off the one-launch path after a one-launch start");
+    if (pl.lean) MGCR_TRY(step_build_lean(s, pl, c, st, refB, &tail_a));
+    else MGCR_TRY(step_build_classic(s, pl, st, refB, c.refR));
+    if (pl.multi && !tail_a) MGCR_TRY(comm_fold_allreduce(pl.comm, s->partsA, 4, nullptr, 0, s->dA, pl.g));
+    return MGCR_OK;
+}
+
+// one iteration, enqueued on the library stream; `it` = iteration number relative to DevState::base
+static int gcr_step(GcrState *s, const SolvePlan &pl, StepCursor &c, PhaseMarks &marks, int it, bool last) {
+    c.iter_count++;
+    set_apply_skip(SkipRef{&s->st->stop_at, it});
+    Step st;
+    st.it = it; st.tail = last && pl.skip_tail;
+    st.lim = s->storage < c.iter_count ? s->storage : c.iter_count;
+    st.ic_next = c.iter_count % s->restart == 0 ? 0 : c.iter_count;
+    st.nxt = st.ic_next % s->storage;
+    MGCR_TRY(marks.enter(0));
+    MGCR_TRY(ensure_slot(s, st.nxt));
+    MGCR_TRY(pl.lean ? step_residual_lean(s, pl, c, st) : step_residual_classic(s, pl, c, st));
+    if (!st.ended) {
+        if (!s->r_after.empty() && c.global < (int)s->r_after.size()) s->r_after[(size_t)c.global] = pl.lean ? c.rcur : (const cplx *)s->r;
+        if (st.tail) {
+            MGCR_TRY(marks.enter(2));   // (the bookkeeping counts as the build phase)
+            MGCR_TRY(step_finish(s, pl, c, st));
+        } else {
+            MGCR_TRY(marks.enter(1));
+            if (step_is_one_launch(pl, st)) MGCR_TRY(step_one_launch(s, pl, c, marks, st));
+            else MGCR_TRY(step_general(s, pl, c, marks, st));
+        }
+    }
+    MGCR_TRY(marks.enter(3));
+    c.iter_count = st.ic_next;
+    c.cur = st.nxt;
+    return MGCR_OK;
+}
+
+// hipGraph (opt-in, MGCR_GRAPH=1): in restart mode every cycle of R iterations is the same launch sequence with the
+// same arguments (iteration numbers are base-relative, base lives on the device), so one cycle can be captured once
+// and replayed.  Measured on MI355X: +11 % iterations/s on the 3072-row sample while an iteration was 4 launches;
+// since it shrank to 3 (fused apply + dots) replay no longer pays at any size — eager launches run 1-4 % FASTER
+// from 512 to 1.4 M rows (e.g. 64^3: 33.6 k against 32.3 k it/s), equal on the sample: the loop is bound by the
+// GPU-side dependency between consecutive short kernels (~8 us each), not by the host's launch cost.  Hence off
+// by default, and gated to <= 2^18 rows when on.
+// The capture pass walks the cursor through one full cycle, which leaves it where it started: at the start of a cycle.
+static int gcr_capture_cycle(GcrState *s, const SolvePlan &pl, StepCursor &c, PhaseMarks &marks) {
+    const int R = s->restart;
+    if (s->graph_exec && s->graph_x == pl.x && s->graph_R == R && s->graph_n == pl.n) return MGCR_OK;
+    hipStream_t stream = ctx().stream;
+    if (s->graph_exec) { hipGraphExecDestroy(s->graph_exec); s->graph_exec = nullptr; }
+    hipGraph_t graph = nullptr;
+    MGCR_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+    int rc = MGCR_OK;
+    for (int i = 1; i <= R && rc == MGCR_OK; i++) rc = gcr_step(s, pl, c, marks, i, false);
+    if (rc == MGCR_OK) {
+        hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, stream, s->st, R);
+    }
+    hipError_t e = hipStreamEndCapture(stream, &graph);
+    if (rc != MGCR_OK) { if (graph) hipGraphDestroy(graph); return rc; }
+    MGCR_HIP(e);
+    e = hipGraphInstantiate(&s->graph_exec, graph, nullptr, nullptr, 0);
+    hipGraphDestroy(graph);
+    MGCR_HIP(e);
+    s->graph_x = pl.x; s->graph_R = R; s->graph_n = pl.n;
+    return MGCR_OK;
+}
+
+// the iterations: replayed cycle by cycle where a captured one exists, enqueued one by one otherwise; a top-level solve looks at
+// the device-side stop predicate every check_every iterations
+static int gcr_loop(GcrState *s, const SolvePlan &pl, StepCursor &c, PhaseMarks &marks) {
+    Context &cx = ctx();
+    const int R = s->restart, max_it = pl.max_it;
+    const int check_every = s->p.check_every > 0 ? s->p.check_every : 10;
     int rel = 0;  // iterations enqueued eagerly since the last advance of DevState::base
     int last_check = 0;
-    while (global < max_it && !done) {
-        if (use_graph && iter_count == 0 && rel == 0 && max_it - global >= R) {
-            MGCR_HIP(hipGraphLaunch(s->graph_exec, c.stream));
-            global += R;
+    bool done = false;
+    while (c.global < max_it && !done) {
+        if (pl.use_graph && c.iter_count == 0 && rel == 0 && max_it - c.global >= R) {
+            MGCR_HIP(hipGraphLaunch(s->graph_exec, cx.stream));
+            c.global += R;
         } else {
-            global++;
+            c.global++;
             rel++;
-            MGCR_TRY(one_iteration(rel, global == max_it));
+            MGCR_TRY(gcr_step(s, pl, c, marks, rel, c.global == max_it));
         }
-        if (!nested && (global / check_every != last_check || global == max_it)) {
-            last_check = global / check_every;
-            MGCR_HIP(hipMemcpyAsync(c.h_mail, s->st, sizeof(DevState), hipMemcpyDeviceToHost, c.stream));
-            MGCR_HIP(hipStreamSynchronize(c.stream));
-            const DevState *hs = (const DevState *)c.h_mail;
+        if (!pl.nested && (c.global / check_every != last_check || c.global == max_it)) {
+            last_check = c.global / check_every;
+            MGCR_HIP(hipMemcpyAsync(cx.h_mail, s->st, sizeof(DevState), hipMemcpyDeviceToHost, cx.stream));
+            MGCR_HIP(hipStreamSynchronize(cx.stream));
+            const DevState *hs = (const DevState *)cx.h_mail;
             if (hs->stop_at != INT_MAX) done = true;
         }
     }
-    if (defer) {  // x updates still pending (solve ended inside a restart cycle); ps[0..npend) hold their directions
-        DirPtrs d0;
-        for (int j = 0; j < LND; j++) { int sl = j < s->storage ? j : 0; d0.ps[j] = s->ps[sl]; d0.aps[j] = s->aps[sl]; d0.slot[j] = sl; }
-        d0.ps[0] = p0;
-        if (assign_x && s->keep_pending && nested) {
-            // the caller writes x = sum coef_j v_j itself, together with whatever else it has to add (V-cycle: + P x_c)
-            for (int j = 0; j < LND; j++) s->pending.v[j] = d0.ps[j];
-            s->pending.coef = lean ? (const cplx *)s->lc->cx : (const cplx *)s->alphas;
-            s->pending.st = s->st;
-            s->has_pending = true;
-        } else {
-        // (npend is not cleared afterwards: nothing reads it again before the next solve's reset_kernel zeroes it)
-        KLAUNCH(flush_x_kernel, g, s->st, lean ? (const cplx *)s->lc->cx : (const cplx *)s->alphas, d0, x, n, assign_x ? 1 : 0,
-                start1 ? rhs : (const cplx *)nullptr);
-        }
+    return MGCR_OK;
+}
+
+// x updates still pending (solve ended inside a restart cycle); ps[0..npend) hold their directions
+static int gcr_flush_x(GcrState *s, const SolvePlan &pl) {
+    DirPtrs d0;
+    fill_dirs(d0, s, 0, s->storage, LND);
+    d0.ps[0] = pl.p0;
+    const cplx *coef = pl.lean ? (const cplx *)s->lc->cx : (const cplx *)s->alphas;
+    if (pl.assign_x && s->keep_pending && pl.nested) {
+        // the caller writes x = sum coef_j v_j itself, together with whatever else it has to add (V-cycle: + P x_c)
+        for (int j = 0; j < LND; j++) s->pending.v[j] = d0.ps[j];
+        s->pending.coef = coef;
+        s->pending.st = s->st;
+        s->has_pending = true;
+        return MGCR_OK;
     }
+    // (npend is not cleared afterwards: nothing reads it again before the next solve's reset_kernel zeroes it)
+    KLAUNCH(flush_x_kernel, pl.g, s->st, coef, d0, pl.x, pl.n, pl.assign_x ? 1 : 0, pl.start1 ? pl.rhs : (const cplx *)nullptr);
+    return MGCR_OK;
+}
+
+static int gcr_run_once(GcrState *s, const cplx *rhs, cplx *x, bool nested, double *hist, int hist_cap, int *n_iter, int *converged) {
+    MGCR_CHECK(s->A, MGCR_ERR_INVALID, "GCR has no operator (call initialise / mgcr_gcr_set_operator first)");
+    const int64_t n = s->A->dim;
+    MGCR_TRY(gcr_prepare(s, n));
+    const mgcr_gcr_param &p = s->p;
+    const SkipRef outer = get_apply_skip();  // outer solver's predicate: if that solve is over, this one is a no-op too
+    s->has_pending = false;
+    s->defer_it = 0;
+    s->partsN_of = nullptr;   // (set again by the start that leaves |b|^2 partials behind)
+    const SolvePlan pl = gcr_plan(s, rhs, x, nested, s->x_from_zero);
+    s->x_from_zero = false;
+
+    if (pl.small) {
+        if (pl.from_zero) MGCR_TRY(k_zero_apply(x, n));
+        MGCR_TRY(ensure_slot(s, s->storage - 1));
+        MGCR_TRY(gcr_small_run(s->A, p, s->storage, s->restart, rhs, x, s->r, s->ar, s->ps.data(), s->aps.data(), s->hist,
+                               s->hist_cap, &s->st->stop_at));
+        s->r_after.assign((size_t)pl.max_it + 1, (const cplx *)s->r);
+        if (nested) return MGCR_OK;
+        return gcr_finish(s, hist, hist_cap, n_iter, converged);
+    }
+    if (pl.resident) {
+        if (!s->res_ring) MGCR_TRY(dalloc(&s->res_ring, (size_t)11 * n));   // the residual ring + P0 (freed with the other vectors)
+        MGCR_TRY(gcr_resident_run(s->A, p, s->storage, s->restart, rhs, x, pl.from_zero, nested && s->discard_residual, s->st, s->hist,
+                                  s->hist_cap, s->res_ring, outer));
+        s->r_after.clear();
+        if (nested) return MGCR_OK;
+        MGCR_TRY(gcr_finish(s, hist, hist_cap, n_iter, converged));
+        return resident_check(true);
+    }
+
+    hipLaunchKernelGGL(reset_kernel, dim3(1), dim3(1), 0, ctx().stream, s->st, outer.p, outer.it, p.tol * p.tol);
+    MGCR_HIP(hipGetLastError());
+    SkipGuard guard(SkipRef{&s->st->stop_at, 0});
+    if (pl.from_zero && !pl.assign_x) MGCR_TRY(k_zero_apply(x, n));
+    StepCursor cursor;
+    PhaseMarks marks;
+    marks.on = p.profile_spmv && !nested;
+    MGCR_TRY(gcr_start(s, pl, cursor));
+    if (pl.use_graph) {
+        s->r_after.clear();   // replayed cycles do not pass through the host-side step counter
+        MGCR_TRY(gcr_capture_cycle(s, pl, cursor, marks));
+    }
+    MGCR_TRY(gcr_loop(s, pl, cursor, marks));
+    if (pl.defer) MGCR_TRY(gcr_flush_x(s, pl));
     if (nested) return MGCR_OK;
-    if (!prof_events.empty()) {
-        MGCR_HIP(hipStreamSynchronize(c.stream));
-        for (int k = 0; k < 3; k++) g_prof_phase_ms[k] = 0.;
-        for (size_t i = 0; i + 3 < prof_events.size(); i += 4)
-            for (int k = 0; k < 3; k++) {
-                float ms = 0.f;
-                hipEventElapsedTime(&ms, prof_events[i + k], prof_events[i + k + 1]);
-                g_prof_phase_ms[k] += ms;
-            }
-        g_prof_iters = (int)(prof_events.size() / 4);
-        g_prof_fused = prof_step_build_close ? 4 : prof_step_build_xr ? 3 : prof_step_build ? 2 : (fuse_ok && xr_fuse) ? 5 : fuse_ok ? 1 : 0;
-        for (hipEvent_t e : prof_events) hipEventDestroy(e);
-    }
+    MGCR_TRY(marks.read_out(pl));
     const int frc = gcr_finish(s, hist, hist_cap, n_iter, converged);
-    if (multi) MGCR_TRY(comm_check(comm));   // a peer-write wait that timed out poisoned the scalars with NaN
-    MGCR_TRY(resident_check(true));          // a one-launch step (gcr_stepbuild.hip) that was not co-resident gave up: gcr_run repeats the solve
+    if (pl.multi) MGCR_TRY(comm_check(pl.comm));   // a peer-write wait that timed out poisoned the scalars with NaN
+    MGCR_TRY(resident_check(true));                // a one-launch step (gcr_stepbuild.hip) that was not co-resident gave up: gcr_run repeats the solve
     return frc;
 }
 

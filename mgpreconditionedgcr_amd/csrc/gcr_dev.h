@@ -30,7 +30,7 @@ struct DevState {
     double rr;     // |r|^2 of the last finished step
     double tol2;
     int closed;    // a restart cycle of this solve has been closed (set by gcr_stepbuild.hip's closing step, cleared by reset_kernel):
-                   // until then P0 may still be read from b itself (gcr.hip start1)
+                   // until then P0 may still be read from b itself (gcr.hip SolvePlan::start1)
 };
 
 // Where a finished solve left its recurrence residual, by the number of steps it actually ran (a solve that

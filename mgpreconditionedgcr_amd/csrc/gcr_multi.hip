@@ -515,7 +515,7 @@ int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int6
         global++;
         const int it = global;
         const bool last = global == max_it;
-        // slot bookkeeping of gcr_run_once's one_iteration
+        // slot bookkeeping of gcr.hip's gcr_step
         iter_count++;
         const int lim = storage < iter_count ? storage : iter_count;
         int ic_next = iter_count;

@@ -23,7 +23,7 @@
 // workgroups, no other process on the device (no live communicator).  Up to 5 stored directions (beyond that the
 // kernels need 128 registers: one workgroup per CU).  Bounded polls as in gcr_resident.hip: a missing workgroup makes the
 // others leave with NaN results, the solve returns an error and the one-launch paths switch themselves off.
-// The host (gcr.hip gcr_run) knows which launch already performed the next update (xr_prefetched); a solve that stops
+// The host (gcr.hip gcr_step) knows which launch already performed the next update (StepCursor::xr_prefetched); a solve that stops
 // on the device turns the whole launch, or its update part, into a no-op like any other kernel of the solve.
 #include <climits>
 #include <cstdlib>
@@ -595,20 +595,6 @@ __global__ void __launch_bounds__(RED_THREADS, 8) start_build_kernel(StartArgs a
     if (threadIdx.x == 0) a.partsR_out[lb] = tot;
 }
 
-// a switch that an environment variable presets (unset or != 0: on) and mgcr_set_option changes
-struct EnvSwitch {
-    const char *env;
-    int v = -1;
-    bool on() {
-        if (v < 0) v = !(getenv(env) && atoi(getenv(env)) == 0);
-        return v != 0;
-    }
-    bool set(bool x) {   // returns the previous setting
-        const bool prev = on();
-        v = x ? 1 : 0;
-        return prev;
-    }
-};
 static EnvSwitch g_stepbuild{"MGCR_STEPBUILD"}, g_start_build{"MGCR_START_BUILD"};
 static EnvSwitch g_sb_keep_all{"MGCR_SB_KEEP_ALL"};   // off: the step_build_kernel dispatch below
 static EnvSwitch g_sb_real{"MGCR_SB_REAL"};            // the REALC instantiations

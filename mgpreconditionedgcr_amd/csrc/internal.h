@@ -187,6 +187,23 @@ int k_fold(const double *parts, int nblk, int nscal, double *out_dev);
 // two slabs in one launch: na scalars of pa -> outa, nb scalars of pb -> outb
 int k_fold2(const double *pa, int na, double *outa, const double *pb, int nb, double *outb, int nblk);
 
+// a switch that an environment variable presets (set: on unless it reads 0; unset: `dflt`) and mgcr_set_option changes
+struct EnvSwitch {
+    const char *env;
+    bool dflt;
+    int v = -1;
+    constexpr EnvSwitch(const char *env_, bool dflt_ = true) : env(env_), dflt(dflt_) {}
+    bool on() {
+        if (v < 0) v = getenv(env) ? atoi(getenv(env)) != 0 : dflt;
+        return v != 0;
+    }
+    bool set(bool x) {   // returns the previous setting
+        const bool prev = on();
+        v = x ? 1 : 0;
+        return prev;
+    }
+};
+
 // ---- spmv.hip --------------------------------------------------------------------------------
 int csr_build_device(int64_t nrow, int64_t ncol, const int64_t *h_rowptr, const int64_t *h_col,
                      const double *h_val_ri, CsrDev *out);
