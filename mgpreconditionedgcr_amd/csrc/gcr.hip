@@ -868,20 +868,6 @@ struct SkipGuard {
     ~SkipGuard() { set_apply_skip(prev); }
 };
 
-// Run-time direction count -> NDT template argument: f(std::integral_constant<int, N>{}) with N = nd for LO <= nd < HI and
-// N = HI for every other nd (the widest form, like the default: of a switch)
-template <int LO, int HI, typename F>
-static int dispatch_nd(int nd, F &&f) {
-    if constexpr (LO < HI) {
-        if (nd == LO) return f(std::integral_constant<int, LO>{});
-        return dispatch_nd<LO + 1, HI>(nd, f);
-    } else {
-        return f(std::integral_constant<int, HI>{});
-    }
-}
-template <typename F>
-static int dispatch_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
-
 struct RedRef {  // where a consumer finds a reduction: slab of per-workgroup partials, or folded + all-reduced scalars
     const double *p;
     int nblk, stride;

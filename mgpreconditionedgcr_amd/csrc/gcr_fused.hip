@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(RED_THREADS, ((MODE == 1 || (MODE == 3 && WT <
 
 
 // The same step for an operator with a stencil view whose near slots are slots 1..5 of 7 (a 3-D grid up to n = 256: +-1, +-n
-// within STEN_TILE / 2 rows; spmv.hip sten_try), with the workgroup's 1024 entries of x per trip staged in an LDS window
+// within STEN_TILE / 2 rows; spmv_build.hip sten_try), with the workgroup's 1024 entries of x per trip staged in an LDS window
 // (+ halo) that serves those five slots: a row then issues ONE coalesced load of its own entry, the two far gathers and
 // — registers now allowing it — its direction streams TOGETHER, i.e. one memory round trip per trip instead of two, and
 // 3.5 instead of 7 loads per row go through L1 / L2.  Two window buffers alternate, so one barrier per trip suffices (a

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mgcr.h"
@@ -97,7 +98,7 @@ struct CsrDev {
     cplx *ell_val = nullptr;       // complex slab, or ...
     double *ell_val_re = nullptr;  // ... real slab when every stored value has a zero imaginary part (12 B/nnz)
     int32_t *ell_col = nullptr;
-    // Row-pattern dictionary (spmv.hip): rows whose (column - row, value) tuples coincide share one
+    // Row-pattern dictionary (spmv_build.hip pat_try): rows whose (column - row, value) tuples coincide share one
     // table entry and store a 2-byte id.  pat_mode 1: offsets and values in the table (no slab at all);
     // 2: offsets only (values stay in the slab, ell_col is dropped); 0: plain ELL.
     int pat_mode = 0;
@@ -107,7 +108,7 @@ struct CsrDev {
     double *pat_re = nullptr, *pat_im = nullptr;  // [npat][W], mode 1
     bool pat_real = false;        // mode 1: every imaginary part is zero
     int64_t reach = 0;            // max |column - row| over the pattern table (0: unknown) — how far a row's gathers go
-    // Stencil view of a mode-1 dictionary (spmv.hip sten_try), what the apply kernels read when it exists: the
+    // Stencil view of a mode-1 dictionary (spmv_build.hip sten_try), what the apply kernels read when it exists: the
     // ascending superset of all patterns' column offsets (sten_ns <= STEN_MAX slots), ONE value per slot, and per
     // wave of 64 rows one 64-bit presence word per slot (sten_planes[wave * sten_stride + slot], bit l = row
     // 64 * wave + l has the slot).  A row's x loads then depend on nothing but the row number.
@@ -123,7 +124,7 @@ struct CsrDev {
     int32_t sten_halo = 0;        // largest |offset| among them (0: no window)
     uint32_t sten_near_f = 0;     // the same for the fused GCR step kernels, whose window spans RED_THREADS rows: within RED_THREADS / 2
     int32_t sten_halo_f = 0;
-    // Banded irregular matrices (spmv.hip ell_window_try): when at least 90 % of the slab's columns lie within win_h rows of their
+    // Banded irregular matrices (spmv_build.hip ell_window_try): when at least 90 % of the slab's columns lie within win_h rows of their
     // row, the stand-alone apply stages x[r0 - win_h, r0 + 1024 + win_h) of each 1024-row tile in LDS and serves those gathers
     // from there (0: no window)
     int32_t win_h = 0;
@@ -144,6 +145,7 @@ struct CsrDev {
 };
 constexpr int TAIL_CAP = 2048;      // entries per chunk (32 KB of LDS products, 8 entries per thread in flight)
 constexpr int TAIL_THREADS = 256;
+constexpr int ELL_WIN_ROWS = 1024;   // rows per workgroup of the window kernel
 
 struct BcsrDev {
     int32_t nbrow = 0, nbcol = 0, bs = 0, nblocks = 0;
@@ -204,12 +206,36 @@ struct EnvSwitch {
     }
 };
 
-// ---- spmv.hip --------------------------------------------------------------------------------
+// Run-time value -> template argument.  dispatch_nd: f(std::integral_constant<int, N>{}) with N = nd for LO <= nd < HI and
+// N = HI for every other nd (the widest form, like the default: of a switch); dispatch_value: the first listed V equal to v, the
+// last one for every other v
+template <int LO, int HI, typename F>
+static int dispatch_nd(int nd, F &&f) {
+    if constexpr (LO < HI) {
+        if (nd == LO) return f(std::integral_constant<int, LO>{});
+        return dispatch_nd<LO + 1, HI>(nd, f);
+    } else {
+        return f(std::integral_constant<int, HI>{});
+    }
+}
+template <int V0, int... VS, typename F>
+static int dispatch_value(int v, F &&f) {
+    if constexpr (sizeof...(VS) > 0) {
+        if (v != V0) return dispatch_value<VS...>(v, f);
+    }
+    return f(std::integral_constant<int, V0>{});
+}
+template <typename F>
+static int dispatch_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// ---- spmv_build.hip (formats) / spmv.hip (apply) ------------------------------------------------
 int csr_build_device(int64_t nrow, int64_t ncol, const int64_t *h_rowptr, const int64_t *h_col,
                      const double *h_val_ri, CsrDev *out);
 void csr_free(CsrDev *c);
 bool set_patterns_enabled(bool on);
 bool set_stencil_enabled(bool on);
+bool stencil_enabled();
+int ell_band_count(const CsrDev &A, unsigned long long *d_cnt);   // cnt[0], cnt[1] += slab columns within 1024 / 4096 rows of their row
 bool csr_stencil_active(const CsrDev &A);  // the apply kernels read A through its stencil view (CsrDev::sten_*)
 int set_spmv_part(int part);
 bool set_lean_enabled(bool on);

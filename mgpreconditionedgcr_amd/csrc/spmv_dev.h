@@ -174,7 +174,7 @@ __device__ __forceinline__ cplx sten_term(const RowMat &m, int c, cplx xv) {
     if (REALV > 0 || (REALV < 0 && m.realv)) return make_double2(m.sten_re[c] * xv.x, m.sten_re[c] * xv.y);
     return cmul(make_double2(m.sten_re[c], m.sten_im[c]), xv);
 }
-// Rare-tail layout with RowMat::sten_pre: slot STEN_COMMON (7) comes FIRST in its rows' storage order (spmv.hip sten_try) — its term
+// Rare-tail layout with RowMat::sten_pre: slot STEN_COMMON (7) comes FIRST in its rows' storage order (spmv_build.hip sten_try) — its term
 // opens the row sum.  plw = the wave's presence word of that slot; xf(j) fetches column j.
 template <int REALV, class XF>
 __device__ __forceinline__ cplx sten_pre_sum(const RowMat &m, int64_t row, uint64_t plw, int lane, XF xf) {

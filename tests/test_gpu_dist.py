@@ -81,7 +81,7 @@ def test_distributed_gcr_matches_single_process(tmp_path, world):
         N, rowptr, col, val, gran = problem(kind)
         A = Sparse(N, N, rowptr, col, val)
         # stencil view on EVERY rank: the upper halo column a rarely present slot behind the common ones, the lower one — first in its
-        # rows' storage order — a slot summed before them (spmv.hip sten_try: leading slot)
+        # rows' storage order — a slot summed before them (spmv_build.hip sten_try: leading slot)
         assert all(res[r][kind]["format"] == (3 if kind == "poisson48" else 0) for r in range(world)), [res[r][kind]["format"] for r in range(world)]
         # the per-iteration scalars went through the peer-write mailboxes (self-test passed on every rank), unless
         # the run asked for the transport's own all-reduce

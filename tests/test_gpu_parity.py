@@ -338,7 +338,7 @@ def test_block_csr_vs_oracle(bs, nb):
 @pytest.mark.parametrize("bs,nb", [(9, 41), (12, 41), (16, 41), (18, 41), (20, 41), (23, 41), (27, 41), (32, 41), (4, 1500), (7, 1100)])
 def test_block_csr_more_shapes_vs_oracle(bs, nb):
     """Block sizes with 2 .. 16 loads of 64 entries per block, block rows with 0, 1 and up to 12 blocks, duplicates; and, from
-    1024 block rows on, the wave kernels are dealt the rows longest first (spmv.hip bcsr_build_device): every row is still
+    1024 block rows on, the wave kernels are dealt the rows longest first (spmv_build.hip bcsr_build_device): every row is still
     summed by one wave in its stored order — the bits of the oracle (src/HierarchicalSparse.h:101-161)."""
     rng = np.random.default_rng(1000 + bs)
     rows, cols = [], []
@@ -420,7 +420,7 @@ def test_row_pattern_storage_is_bit_exact(case):
     xf = Field((N,), x)
     k = 0.3 - 0.2j
     # constant-coefficient stencils additionally get the stencil view (format 3: 7 slots, presence words per wave,
-    # csrc/spmv.hip sten_try), which the apply kernels then read instead of the dictionary: both must give the bits
+    # csrc/spmv_build.hip sten_try), which the apply kernels then read instead of the dictionary: both must give the bits
     for stencil in (1, 0):
         prev = mg.set_option("stencil_storage", stencil)
         try:
