@@ -9,6 +9,7 @@
 #include <mutex>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/mgcr.h"
@@ -168,7 +169,7 @@ struct Op {
     BcsrDev bcsr;        // OP_BCSR
     GcrState *gcr = nullptr;  // OP_GCR
     MgState *mg = nullptr;    // OP_MG
-    DistCsr *dist = nullptr;  // OP_CSR / OP_BCSR row block of a distributed matrix (comm.hip)
+    DistCsr *dist = nullptr;  // OP_CSR / OP_BCSR row block of a distributed matrix (halo.hip; owned)
     Comm *comm = nullptr;     // communicator the operator's Fields are distributed over (borrowed)
 };
 
@@ -204,6 +205,19 @@ struct EnvSwitch {
         v = x ? 1 : 0;
         return prev;
     }
+};
+
+// a device buffer that is freed unless it is handed over (release): temporaries, and allocations on their way into a structure
+template <typename T>
+struct DevBuf {   // move-only
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.release()) {}
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); return *this; }
+    ~DevBuf() { if (p) hipFree(p); }
+    hipError_t malloc(size_t count) { return hipMalloc((void **)&p, sizeof(T) * count); }
+    bool alloc(size_t count) { return malloc(count) == hipSuccess; }
+    T *release() { T *q = p; p = nullptr; return q; }
 };
 
 // Run-time value -> template argument.  dispatch_nd: f(std::integral_constant<int, N>{}) with N = nd for LO <= nd < HI and
@@ -292,9 +306,9 @@ struct SkipRef {
 void set_apply_skip(SkipRef s);
 SkipRef get_apply_skip();
 
-// ---- comm.hip --------------------------------------------------------------------------------
+// ---- comm.hip (communicator, all-reduces) / halo.hip (distributed operator, halo exchange) ---------
 // overlap_interior: the caller multiplies the rows that need no halo between begin and end — a peer-write exchange is then split
-// into store + publish (begin) and the wait for the neighbours (end)
+// into store + publish (begin) and the wait for the neighbours (end), which must follow even when those rows fail to launch
 int dist_halo_begin(DistCsr *d, const cplx *x, bool overlap_interior = false);
 int64_t dist_halo_split_count();
 bool set_halo_split(bool on);
@@ -305,11 +319,13 @@ bool dist_halo_overlaps();  // MGCR_HALO_OVERLAP: exchange on the communication 
 const cplx *dist_halo_ptr(DistCsr *d);  // halo segment of the exchange begun last (peer-write: alternates between two slots)
 int dist_halo_kind(DistCsr *d);
 void dist_info(DistCsr *d, const cplx **xh, int64_t *interior_begin, int64_t *interior_end);
-void dist_free(DistCsr *d);
-Comm *dist_comm(DistCsr *d);
+void dist_free(DistCsr *d);   // the DistCsr with its partition plan and device buffers; the communicator is borrowed and stays
+Comm *dist_comm(DistCsr *d);  // borrowed: the communicator outlives every operator made on it (mgcr_comm_destroy is the caller's)
 void dist_sizes(DistCsr *d, int64_t *nloc, int64_t *nh, int64_t *row0, int64_t *n_global, int *rank, int *nranks);
-int comm_allreduce_host_pub(Comm *c, double *buf, int64_t count);
+int comm_allreduce_host(Comm *c, double *buf, int64_t count);   // host-level (set-up): in-place sum of `count` doubles over all ranks
 int dist_exchange_rows_host(DistCsr *d, const double *own, int w, double *halo);
+// Collective.  Fill op->csr / op->bcsr, op->dist and op->comm; the partition plan they build ends up inside op->dist.  On success
+// the DistCsr belongs to the Op (whoever destroys the Op calls dist_free); on failure nothing is left in *op to free.
 int dist_csr_create(Comm *c, int64_t n_global, int64_t row0, int64_t nloc, const int64_t *rowptr, const int64_t *col,
                     const double *val_ri, Op *op);
 int dist_bcsr_create(Comm *c, int64_t nb_global, int64_t brow0, int32_t nbloc, int32_t bs, const int32_t *browptr,

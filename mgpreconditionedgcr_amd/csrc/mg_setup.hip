@@ -291,7 +291,7 @@ int mg_level_setup_device(Op *A, int ndim, const int64_t *dims, const int32_t *b
         comm = dist_comm(dist);
         std::vector<double> cnt((size_t)nranks, 0.);
         cnt[(size_t)rank] = (double)nagg;
-        MGCR_TRY(comm_allreduce_host_pub(comm, cnt.data(), nranks));
+        MGCR_TRY(comm_allreduce_host(comm, cnt.data(), nranks));
         nagg_glob = 0;
         for (int r = 0; r < nranks; r++) { if (r == rank) agg_off = nagg_glob; nagg_glob += (int64_t)cnt[(size_t)r]; }
         std::vector<int32_t> h_agg((size_t)n);

@@ -708,6 +708,14 @@ static int ell_rows(const CsrDev &A, int64_t row_begin, int64_t row_count, const
     return A.L == 1 ? slab_rows<SHIFT>(A, r) : lanes_rows<SHIFT>(A, r);
 }
 
+// dist_halo_end for a begun exchange, also when the interior rows between the two fail to launch: the wait half of a split
+// peer-write exchange is never skipped (halo.hip), or the next exchange would meet a stale pending wait
+struct HaloEnd {
+    DistCsr *d;
+    int end() { DistCsr *q = d; d = nullptr; return dist_halo_end(q); }
+    ~HaloEnd() { if (d) dist_halo_end(d); }
+};
+
 template <bool SHIFT>
 static int csr_apply_t(const CsrDev &A, const cplx *x, cplx *y, cplx k, DistCsr *dist, const cplx *w) {
     if (A.nrow == 0) return MGCR_OK;
@@ -719,9 +727,10 @@ static int csr_apply_t(const CsrDev &A, const cplx *x, cplx *y, cplx k, DistCsr 
         dist_info(dist, &xh, &ib, &ie);
         n_own = (int32_t)A.nrow;
         MGCR_TRY(dist_halo_begin(dist, x, ie > ib && g_spmv_part == 0));
+        HaloEnd halo{dist};
         xh = dist_halo_ptr(dist);
         MGCR_TRY(ell_rows<SHIFT>(A, ib, ie - ib, x, xh, n_own, y, k, w));
-        MGCR_TRY(dist_halo_end(dist));
+        MGCR_TRY(halo.end());
         MGCR_TRY(ell_rows<SHIFT>(A, 0, ib, x, xh, n_own, y, k, w));
         MGCR_TRY(ell_rows<SHIFT>(A, ie, A.nrow - ie, x, xh, n_own, y, k, w));
     } else if (g_spmv_part != 2) {

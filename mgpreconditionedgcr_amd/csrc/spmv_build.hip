@@ -72,19 +72,8 @@ __global__ void col_check_kernel(int64_t nnz, const int64_t *__restrict__ col, i
     if (i < nnz && (col[i] < 0 || col[i] >= ncol)) *bad = 1;
 }
 
-// Ownership during a build: every device buffer belongs to a DevBuf or to the structure under construction, which a BuildGuard
-// frees unless the build hands it over.  So any early return gives back what was allocated.
-template <typename T>
-struct DevBuf {   // move-only
-    T *p = nullptr;
-    DevBuf() = default;
-    DevBuf(DevBuf &&o) noexcept : p(o.release()) {}
-    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); return *this; }
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t malloc(size_t count) { return hipMalloc((void **)&p, sizeof(T) * count); }
-    bool alloc(size_t count) { return malloc(count) == hipSuccess; }
-    T *release() { T *q = p; p = nullptr; return q; }
-};
+// Ownership during a build: every device buffer belongs to a DevBuf (internal.h) or to the structure under construction, which a
+// BuildGuard frees unless the build hands it over.  So any early return gives back what was allocated.
 template <typename D, void (*FREE)(D *)>
 struct BuildGuard {
     D d;
