@@ -1,6 +1,8 @@
 """Blocks of k Fields on the GPU: pack / unpack, block BLAS-1, the k-wide apply and the batched GCR.  Everything is compared
 bit for bit (np.array_equal) with the single-Field entry points on the same columns — the two rules of include/mgcr.h
-(mgcr_op_apply_multi, mgcr_gcr_solve_multi)."""
+(mgcr_op_apply_multi, mgcr_gcr_solve_multi).  The comparison of the batched solve with the CPU oracle in device summation order — cycle
+lengths, ragged column groups, frozen columns, x0 through every apply form — is in tests/test_gpu_multi_rhs_edges.py (cases:
+tests/multi_rhs_cases.py, their premises on the CPU: tests/test_multi_rhs_cases.py)."""
 import os
 
 import numpy as np
