@@ -3,6 +3,7 @@
 #pragma once
 #include "internal.h"
 #include "reduce.h"
+#include "fused_form.h"   // host only: which form of the fused apply kernels an operator takes, the padded grid, the reach threshold
 
 namespace mgcr {
 

@@ -526,90 +526,84 @@ __global__ void __launch_bounds__(RED_THREADS, 8) sten_apply_carry_kernel(RowMat
     }
 }
 
-static int g_fuse = -1;
-static bool fuse_enabled() {
-    if (g_fuse < 0) g_fuse = !(getenv("MGCR_FUSE") && atoi(getenv("MGCR_FUSE")) == 0);
-    return g_fuse != 0;
-}
-bool set_fuse_enabled(bool on) {
-    bool prev = fuse_enabled();
-    g_fuse = on ? 1 : 0;
-    return prev;
-}
+static EnvSwitch g_fuse("MGCR_FUSE"), g_fused_tile("MGCR_FUSED_TILE"), g_tile_carry("MGCR_TILE_CARRY"), g_xr_tile("MGCR_XR_FUSE_TILE"),
+    g_apply_carry("MGCR_APPLY_CARRY");
+bool set_fuse_enabled(bool on) { return g_fuse.set(on); }
 bool csr_fusable(const CsrDev &A, const DistCsr *dist) {
     if (A.pat_mode == 1 && (int64_t)A.npat * A.W * 20 > 48 * 1024) return false;  // pattern table must fit LDS
     // a row block of a distributed matrix qualifies when its halo exchange is ordered on the compute stream
     // (the default): the one kernel then simply runs after it
     if (dist ? dist_halo_overlaps() : A.nrow != A.ncol) return false;
-    return fuse_enabled() && A.L == 1 && A.n_tail_rows == 0 && A.nrow >= 1 && A.W >= 1;
+    return g_fuse.on() && A.L == 1 && A.n_tail_rows == 0 && A.nrow >= 1 && A.W >= 1;
 }
 
-template <int MODE, int WT, bool PW = false>
-static void launch_nd(int nd, unsigned grid, size_t lds_bytes, const RowMat &m, const cplx *x, cplx *y, const DotVecs &d, int64_t n,
-                      int g, double *parts, SkipRef sk, const RowMap &rm, const PwTail &pw = PwTail{}) {
-#define SK(NDT)                                                                                                          \
-    hipLaunchKernelGGL((step_apply_kernel<MODE, WT, NDT, PW>), dim3(grid), dim3(RED_THREADS), lds_bytes, ctx().stream, m, x, y, d, n, \
-                       g, rm, parts, sk.p, sk.it, pw)
-    switch (nd) {
-        case 1: SK(1); break;
-        case 2: SK(2); break;
-        case 3: SK(3); break;
-        case 4: SK(4); break;
-        case 5: SK(5); break;
-        case 6: SK(6); break;
-        case 7: SK(7); break;
-        case 8: SK(8); break;
-        case 9: SK(9); break;
-        default: SK(10); break;
-    }
-#undef SK
-}
-
-template <int NS, bool RARE, bool PW = false, bool CARRY = false>
-static void launch_tile_nd(int nd, unsigned grid, size_t lds_bytes, const RowMat &m, const cplx *x, cplx *y, const DotVecs &d, int64_t n,
-                           int g, double *parts, SkipRef sk, const RowMap &rm, const PwTail &pw = PwTail{}) {
-#define SKT(NDT)                                                                                                              \
-    do {                                                                                                                      \
-        static bool big_lds = false;   /* up to 2 x 2048 x 16 B of window + the reduction scratch: above the 64 KiB default */ \
-        if (!big_lds) {                                                                                                       \
-            hipFuncSetAttribute((const void *)step_apply_tile_kernel<NS, RARE, NDT, PW, CARRY>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024); \
-            big_lds = true;                                                                                                   \
-        }                                                                                                                     \
-        hipLaunchKernelGGL((step_apply_tile_kernel<NS, RARE, NDT, PW, CARRY>), dim3(grid), dim3(RED_THREADS), lds_bytes, ctx().stream, m, x, y, d, n, \
-                           g, rm, parts, sk.p, sk.it, pw);                                                                    \
-    } while (0)
-    switch (nd) {
-        case 1: SKT(1); break;
-        case 2: SKT(2); break;
-        case 3: SKT(3); break;
-        case 4: SKT(4); break;
-        case 5: SKT(5); break;
-        case 6: SKT(6); break;
-        case 7: SKT(7); break;
-        case 8: SKT(8); break;
-        case 9: SKT(9); break;
-        default: SKT(10); break;
-    }
-#undef SKT
-}
 static int64_t fused_tile_min_reach() {
-    static const int64_t r = getenv("MGCR_FUSED_TILE_REACH") ? atoll(getenv("MGCR_FUSED_TILE_REACH")) : (int64_t)1 << 15;
+    static const int64_t r = env_int64("MGCR_FUSED_TILE_REACH", FUSED_TILE_REACH_DEFAULT);
     return r;
 }
 // the far slots of the 7-slot view are exactly one step of the banded row map away (step_apply_tile_kernel: CARRY)
 // (the CARRY instantiations are also the ones compiled for real stencil coefficients — no per-slot real / complex decision, 14 scalar
 // registers less: what lets them keep 64 vector registers without spills)
 static bool tile_carry(const CsrDev &A, const RowMap &rm) {
-    static const bool on = !(getenv("MGCR_TILE_CARRY") && atoi(getenv("MGCR_TILE_CARRY")) == 0);
     const int64_t step = rm.plane ? rm.plane : (int64_t)rm.per * RED_THREADS;
     // (7 slots, or the 7 + 2 of a distributed row block: its halo columns are rarely present slots of their own — the carried far
     // values of a boundary plane's rows are masked like the gathered ones were)
-    return on && rm.band != 0 && A.sten_off[6] == step && A.sten_off[0] == -step && sten_slots(A) == (A.sten_rare ? 9 : 7) &&
+    return g_tile_carry.on() && rm.band != 0 && A.sten_off[6] == step && A.sten_off[0] == -step && sten_slots(A) == (A.sten_rare ? 9 : 7) &&
            row_mat(A, false, cplx{0., 0.}).realv;
 }
-static bool fused_tile_enabled() {
-    static const bool on = !(getenv("MGCR_FUSED_TILE") && atoi(getenv("MGCR_FUSED_TILE")) == 0);
-    return on;
+
+// ---- the form an operator's launches take (fused_form.h), and that form as template arguments -----------------------------------
+static FusedOperator fused_operator(const CsrDev &A) {
+    return FusedOperator{csr_stencil_active(A), A.sten_rare != 0, sten_slots(A), A.sten_near_f, A.sten_halo_f, A.reach, A.pat_mode, A.W,
+                         row_mat_lds_bytes(A)};
+}
+static FusedSetup fused_setup() { return FusedSetup{g_fused_tile.on(), g_xr_tile.on(), fused_tile_min_reach(), RED_THREADS, sizeof(cplx)}; }
+static bool tile_regime(const CsrDev &A) { return fused_windowed_regime(fused_operator(A), fused_setup()); }
+static FusedForm form_of(const CsrDev &A, const RowMap &rm, FusedUse use, bool pw = false, bool xr_ap_ok = true) {
+    const FusedOperator op = fused_operator(A);
+    const FusedSetup s = fused_setup();
+    return fused_form(op, s, use, pw, fused_windowed_regime(op, s) && tile_carry(A, rm), xr_ap_ok);
+}
+static int no_such_form() {
+    set_error("fused GCR apply: no kernel of this form");
+    return MGCR_ERR_INVALID;
+}
+// tile(NS, RARE) for a windowed form, plain(MODE, WT) for every other: the (MODE, WT) and (NS, RARE) pairs fused_form selects, no others
+template <typename FT, typename FP>
+static int dispatch_form(const FusedForm &f, FT &&tile, FP &&plain) {
+    if (f.windowed)
+        return dispatch_bool(f.rare, [&](auto RARE) -> int { return tile(std::integral_constant<int, decltype(RARE)::value ? 9 : 7>{}, RARE); });
+    return dispatch_value<4, 3, 1, 2, 0>(f.mode, [&](auto MODE) -> int {
+        return dispatch_value<9, 7, 0>(f.ns, [&](auto WT) -> int {
+            constexpr int M = decltype(MODE)::value, W = decltype(WT)::value;
+            if constexpr (M == 4 ? W == 9 : M == 3 ? W != 0 : W != 9) return plain(MODE, WT);
+            else return no_such_form();
+        });
+    });
+}
+// a windowed kernel: up to 2 x 2048 x 16 B of window + the reduction scratch is above the 64 KiB default, asked for once per instantiation
+template <auto KERNEL, typename... AA>
+static int launch_windowed(unsigned grid, size_t lds, AA... args) {
+    static bool big_lds = false;
+    if (!big_lds) {
+        (void)hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
+        big_lds = true;
+    }
+    return launch(KERNEL, grid, RED_THREADS, lds, args...);
+}
+// row block of a distributed matrix: the halo exchange of x is enqueued first, the kernel reads the segment it filled
+static int dist_prologue(DistCsr *dist, const CsrDev &A, const cplx *x, RowMat *m) {
+    if (!dist) return MGCR_OK;
+    m->n_own = (int32_t)A.nrow;
+    MGCR_TRY(dist_halo_begin(dist, x));
+    MGCR_TRY(dist_halo_end(dist));
+    m->xh = dist_halo_ptr(dist);
+    return MGCR_OK;
+}
+static DotVecs dot_vecs(const cplx *const *vecs, int nd) {
+    DotVecs d;
+    for (int j = 0; j < FND; j++) d.v[j] = vecs[j < nd ? j : 0];
+    return d;
 }
 
 // y = A x (or x - k A x) + partials of <y, vecs_j>, j < nd <= FND, laid out like gcr.hip's partsB;
@@ -628,115 +622,30 @@ int csr_step_apply(const CsrDev &A, const cplx *x, cplx *y, bool shift, cplx k, 
     MGCR_CHECK(x != y, MGCR_ERR_INVALID, "SpMV cannot run in place");
     MGCR_CHECK(nd >= 1 && nd <= FND, MGCR_ERR_INVALID, "csr_step_apply: 1..10 vectors");
     RowMat m = row_mat(A, shift, k);
-    if (dist) {
-        int64_t ib = 0, ie = 0;
-        dist_info(dist, &m.xh, &ib, &ie);
-        m.n_own = (int32_t)A.nrow;
-        MGCR_TRY(dist_halo_begin(dist, x));
-        MGCR_TRY(dist_halo_end(dist));
-        m.xh = dist_halo_ptr(dist);
-    }
-    DotVecs d;
-    for (int j = 0; j < FND; j++) d.v[j] = vecs[j < nd ? j : 0];
+    MGCR_TRY(dist_prologue(dist, A, x, &m));
+    const DotVecs d = dot_vecs(vecs, nd);
     const int g = red_grid(A.nrow);
-    const unsigned grid = (unsigned)(g >= 64 ? (g + 7) / 8 * 8 : g);  // multiple of 8 => XCD bands
-    const size_t lds_bytes = row_mat_lds_bytes(A);
+    const unsigned grid = fused_grid(g);
     const SkipRef sk = get_apply_skip();
-#define ST_W(MODE)                                                                              \
-    do {                                                                                        \
-        if (pw && A.W == 7) launch_nd<MODE, 7, true>(nd, grid, lds_bytes, m, x, y, d, A.nrow, g, parts, sk, rm, *pw); \
-        else if (pw) launch_nd<MODE, 0, true>(nd, grid, lds_bytes, m, x, y, d, A.nrow, g, parts, sk, rm, *pw);        \
-        else if (A.W == 7) launch_nd<MODE, 7>(nd, grid, lds_bytes, m, x, y, d, A.nrow, g, parts, sk, rm); \
-        else launch_nd<MODE, 0>(nd, grid, lds_bytes, m, x, y, d, A.nrow, g, parts, sk, rm);          \
-    } while (0)
-#define ST_S(MODE, NS) launch_nd<MODE, NS>(nd, grid, 0, m, x, y, d, A.nrow, g, parts, sk, rm)
-    if (csr_stencil_active(A) && A.sten_near_f == 0x3eu && A.sten_halo_f > 0 && (A.sten_rare || sten_slots(A) == 7) && fused_tile_enabled() &&
-        A.reach >= fused_tile_min_reach()) {
-        // 3-D stencil: x staged in an LDS window per trip (step_apply_tile_kernel)
-        const size_t win = 2 * (size_t)(RED_THREADS + 2 * A.sten_halo_f) * sizeof(cplx);
-        const bool carry = tile_carry(A, rm);
-        if (A.sten_rare && pw && carry) launch_tile_nd<9, true, true, true>(nd, grid, win, m, x, y, d, A.nrow, g, parts, sk, rm, *pw);
-        else if (A.sten_rare && pw) launch_tile_nd<9, true, true>(nd, grid, win, m, x, y, d, A.nrow, g, parts, sk, rm, *pw);
-        else if (A.sten_rare && carry) launch_tile_nd<9, true, false, true>(nd, grid, win, m, x, y, d, A.nrow, g, parts, sk, rm);
-        else if (A.sten_rare) launch_tile_nd<9, true>(nd, grid, win, m, x, y, d, A.nrow, g, parts, sk, rm);
-        else if (pw) launch_tile_nd<7, false, true>(nd, grid, win, m, x, y, d, A.nrow, g, parts, sk, rm, *pw);
-        else if (carry) launch_tile_nd<7, false, false, true>(nd, grid, win, m, x, y, d, A.nrow, g, parts, sk, rm);
-        else launch_tile_nd<7, false>(nd, grid, win, m, x, y, d, A.nrow, g, parts, sk, rm);
-    } else if (csr_stencil_active(A)) {   // MODE 4: rare-tail layout (7 common + 2 rare slots)
-        if (A.sten_rare && pw) launch_nd<4, 9, true>(nd, grid, 0, m, x, y, d, A.nrow, g, parts, sk, rm, *pw);
-        else if (pw && sten_slots(A) == 7) launch_nd<3, 7, true>(nd, grid, 0, m, x, y, d, A.nrow, g, parts, sk, rm, *pw);
-        else if (pw) launch_nd<3, 9, true>(nd, grid, 0, m, x, y, d, A.nrow, g, parts, sk, rm, *pw);
-        else if (A.sten_rare) ST_S(4, 9);
-        else if (sten_slots(A) == 7) ST_S(3, 7);
-        else ST_S(3, 9);
-    }
-    else if (A.pat_mode == 1) ST_W(1);
-    else if (A.pat_mode == 2) ST_W(2);
-    else ST_W(0);
-#undef ST_S
-#undef ST_W
-    MGCR_HIP(hipGetLastError());
-    return MGCR_OK;
-}
-
-
-template <int MODE, int WT>
-static void launch_xr_nd(int nd, unsigned grid, size_t lds_bytes, const RowMat &m, const cplx *r_in, const cplx *ap, cplx *r_out, cplx *y,
-                         const DotVecs &d, int64_t n, int g, const RowMap &rm, double *parts, double *partsR, DevState *st, int it,
-                         const double *partsA, int nblkA, int strideA, cplx *den_slot, int slot, LeanCoef *lc) {
-#define SX(NDT)                                                                                                                       \
-    hipLaunchKernelGGL((step_apply_xr_kernel<MODE, WT, NDT>), dim3(grid), dim3(RED_THREADS), lds_bytes, ctx().stream, m, r_in, ap, r_out, y, \
-                       d, n, g, rm, parts, partsR, st, it, partsA, nblkA, strideA, den_slot, slot, lc)
-    switch (nd) {
-        case 1: SX(1); break;
-        case 2: SX(2); break;
-        case 3: SX(3); break;
-        case 4: SX(4); break;
-        case 5: SX(5); break;
-        case 6: SX(6); break;
-        case 7: SX(7); break;
-        case 8: SX(8); break;
-        case 9: SX(9); break;
-        default: SX(10); break;
-    }
-#undef SX
-}
-
-static bool tile_regime(const CsrDev &A) {   // where csr_step_apply / csr_init_apply stage x in the LDS window
-    return csr_stencil_active(A) && A.sten_near_f == 0x3eu && A.sten_halo_f > 0 && (A.sten_rare || sten_slots(A) == 7) && fused_tile_enabled() &&
-           A.reach >= fused_tile_min_reach();
-}
-static bool xr_tile_enabled() {
-    static const bool on = !(getenv("MGCR_XR_FUSE_TILE") && atoi(getenv("MGCR_XR_FUSE_TILE")) == 0);
-    return on;
-}
-template <int NS, bool RARE>
-static void launch_xr_tile_nd(int nd, unsigned grid, size_t lds_bytes, const RowMat &m, const cplx *r_in, const cplx *ap, cplx *r_out, cplx *y,
-                              const DotVecs &d, int64_t n, int g, const RowMap &rm, double *parts, double *partsR, DevState *st,
-                              int it, const double *partsA, int nblkA, int strideA, cplx *den_slot, int slot, LeanCoef *lc) {
-#define SXT(NDT)                                                                                                                       \
-    do {                                                                                                                               \
-        static bool big_lds = false;                                                                                                   \
-        if (!big_lds) {                                                                                                                \
-            hipFuncSetAttribute((const void *)step_apply_xr_tile_kernel<NS, RARE, NDT, (NDT <= XR_TILE_APC_NDT)>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024); \
-            big_lds = true;                                                                                                            \
-        }                                                                                                                              \
-        hipLaunchKernelGGL((step_apply_xr_tile_kernel<NS, RARE, NDT, (NDT <= XR_TILE_APC_NDT)>), dim3(grid), dim3(RED_THREADS), lds_bytes, ctx().stream, m, r_in, ap, r_out, \
-                           y, d, n, g, rm, parts, partsR, st, it, partsA, nblkA, strideA, den_slot, slot, lc);                \
-    } while (0)
-    switch (nd) {
-        case 1: SXT(1); break;
-        case 2: SXT(2); break;
-        case 3: SXT(3); break;
-        case 4: SXT(4); break;
-        case 5: SXT(5); break;
-        case 6: SXT(6); break;
-        case 7: SXT(7); break;
-        case 8: SXT(8); break;
-        case 9: SXT(9); break;
-        default: SXT(10); break;
-    }
-#undef SXT
+    const FusedForm f = form_of(A, rm, FusedUse::Step, pw != nullptr);
+    const PwTail tail = pw ? *pw : PwTail{};
+    return dispatch_bool(f.pw, [&](auto PW) -> int {
+        return dispatch_form(f, [&](auto NS, auto RARE) -> int {   // 3-D stencil: x staged in an LDS window per trip
+            return dispatch_bool(f.carry, [&](auto CARRY) -> int {
+                if constexpr (!decltype(RARE)::value && decltype(PW)::value && decltype(CARRY)::value) return no_such_form();
+                else return dispatch_nd<1, FND>(nd, [&](auto NDT) -> int {
+                    return launch_windowed<step_apply_tile_kernel<decltype(NS)::value, decltype(RARE)::value, decltype(NDT)::value, decltype(PW)::value,
+                                                                  decltype(CARRY)::value>>(grid, f.lds_bytes, m, x, y, d, A.nrow, g, rm, parts, sk.p,
+                                                                                           sk.it, tail);
+                });
+            });
+        }, [&](auto MODE, auto WT) -> int {
+            return dispatch_nd<1, FND>(nd, [&](auto NDT) -> int {
+                return launch(step_apply_kernel<decltype(MODE)::value, decltype(WT)::value, decltype(NDT)::value, decltype(PW)::value>, grid,
+                              RED_THREADS, f.lds_bytes, m, x, y, d, A.nrow, g, rm, parts, sk.p, sk.it, tail);
+            });
+        });
+    });
 }
 
 // 0: the residual update keeps its own launch; 1: latency regime (step_apply_xr_kernel); 2: windowed bandwidth regime
@@ -746,8 +655,8 @@ int csr_xr_fuse_kind(const CsrDev &A, const DistCsr *dist) {
     return tile_regime(A) ? 2 : 1;
 }
 bool csr_xr_fusable(const CsrDev &A, const DistCsr *dist) {
-    static const int64_t limit = getenv("MGCR_XR_FUSE_ROWS") ? atoll(getenv("MGCR_XR_FUSE_ROWS")) : ((int64_t)1 << 19);
-    if (!dist && tile_regime(A) && xr_tile_enabled() && csr_fusable(A, dist)) {
+    static const int64_t limit = env_int64("MGCR_XR_FUSE_ROWS", (int64_t)1 << 19);
+    if (!dist && fused_xr_windowed_regime(fused_operator(A), fused_setup()) && csr_fusable(A, dist)) {
         // the windowed form: real stencil coefficients, and the far slots one step of the banded row map away (gcr_fused_xr_tile.h)
         return !A.sten_rare && tile_carry(A, make_row_map(A.nrow, red_grid(A.nrow), A.reach));
     }
@@ -763,41 +672,25 @@ int csr_step_apply_xr(const CsrDev &A, const cplx *r_in, const cplx *ap, cplx *r
                       cplx *den_slot, int slot, LeanCoef *lc, const RowMap &rm) {
     MGCR_CHECK(r_in != r_out && r_out != y && r_in != y, MGCR_ERR_INVALID, "csr_step_apply_xr: operands must be distinct");
     MGCR_CHECK(nd >= 1 && nd <= FND, MGCR_ERR_INVALID, "csr_step_apply_xr: 1..10 vectors");
-    RowMat m = row_mat(A, shift, k);
-    DotVecs d;
-    for (int j = 0; j < FND; j++) d.v[j] = vecs[j < nd ? j : 0];
+    const RowMat m = row_mat(A, shift, k);
+    const DotVecs d = dot_vecs(vecs, nd);
     const int g = red_grid(A.nrow);
-    const unsigned grid = (unsigned)(g >= 64 ? (g + 7) / 8 * 8 : g);
-    const size_t lds_bytes = row_mat_lds_bytes(A);
-#define SXW(MODE)                                                                                                                          \
-    do {                                                                                                                                   \
-        if (A.W == 7) launch_xr_nd<MODE, 7>(nd, grid, lds_bytes, m, r_in, ap, r_out, y, d, A.nrow, g, rm, parts, partsR, st, it, partsA, nblkA, \
-                                            strideA, den_slot, slot, lc);                                                                  \
-        else launch_xr_nd<MODE, 0>(nd, grid, lds_bytes, m, r_in, ap, r_out, y, d, A.nrow, g, rm, parts, partsR, st, it, partsA, nblkA, strideA,  \
-                                   den_slot, slot, lc);                                                                                    \
-    } while (0)
-#define SXS(MODE, NS) launch_xr_nd<MODE, NS>(nd, grid, 0, m, r_in, ap, r_out, y, d, A.nrow, g, rm, parts, partsR, st, it, partsA, nblkA, strideA, \
-                                             den_slot, slot, lc)
-    if (tile_regime(A)) {
-        const size_t win = 2 * (size_t)(RED_THREADS + 2 * A.sten_halo_f) * sizeof(cplx);
-        // (APC instantiations take the newest direction's A p from the update's operands: it must be the last of the dot-product streams —
-        // it is, in a lean cycle of up to FND directions; beyond that the kernel requests its streams like any other)
-        MGCR_CHECK(!A.sten_rare && tile_carry(A, rm) && (nd > XR_TILE_APC_NDT || d.v[nd - 1] == ap), MGCR_ERR_INVALID,
-                   "csr_step_apply_xr: not the windowed form's case");
-        launch_xr_tile_nd<7, false>(nd, grid, win, m, r_in, ap, r_out, y, d, A.nrow, g, rm, parts, partsR, st, it, partsA, nblkA, strideA,
-                                         den_slot, slot, lc);
-    } else if (csr_stencil_active(A)) {
-        if (A.sten_rare) SXS(4, 9);
-        else if (sten_slots(A) == 7) SXS(3, 7);
-        else SXS(3, 9);
-    }
-    else if (A.pat_mode == 1) SXW(1);
-    else if (A.pat_mode == 2) SXW(2);
-    else SXW(0);
-#undef SXS
-#undef SXW
-    MGCR_HIP(hipGetLastError());
-    return MGCR_OK;
+    const unsigned grid = fused_grid(g);
+    // (APC instantiations take the newest direction's A p from the update's operands: it must be the last of the dot-product streams —
+    // it is, in a lean cycle of up to FND directions; beyond that the kernel requests its streams like any other)
+    const FusedForm f = form_of(A, rm, FusedUse::Xr, false, nd > XR_TILE_APC_NDT || d.v[nd - 1] == ap);
+    MGCR_CHECK(!f.error, MGCR_ERR_INVALID, "csr_step_apply_xr: %s", f.error);
+    return dispatch_nd<1, FND>(nd, [&](auto NDT) -> int {
+        constexpr int N = decltype(NDT)::value;
+        return dispatch_form(f, [&](auto NS, auto RARE) -> int {
+            if constexpr (decltype(RARE)::value) return no_such_form();
+            else return launch_windowed<step_apply_xr_tile_kernel<decltype(NS)::value, false, N, (N <= XR_TILE_APC_NDT)>>(
+                     grid, f.lds_bytes, m, r_in, ap, r_out, y, d, A.nrow, g, rm, parts, partsR, st, it, partsA, nblkA, strideA, den_slot, slot, lc);
+        }, [&](auto MODE, auto WT) -> int {
+            return launch(step_apply_xr_kernel<decltype(MODE)::value, decltype(WT)::value, N>, grid, RED_THREADS, f.lds_bytes, m, r_in, ap, r_out,
+                          y, d, A.nrow, g, rm, parts, partsR, st, it, partsA, nblkA, strideA, den_slot, slot, lc);
+        });
+    });
 }
 
 // aps0 = A r0 (or r0 - k A r0) + the partials of <r0,aps0>, <aps0,aps0> (partsA), |r0|^2 (partsR) and |b|^2 (partsN;
@@ -806,74 +699,37 @@ int csr_init_apply(const CsrDev &A, const cplx *r0, cplx *aps0, bool shift, cplx
                    double *partsN, DistCsr *dist, const RowMap &rm) {
     MGCR_CHECK(r0 != aps0, MGCR_ERR_INVALID, "SpMV cannot run in place");
     RowMat m = row_mat(A, shift, k);
-    if (dist) {
-        m.n_own = (int32_t)A.nrow;
-        MGCR_TRY(dist_halo_begin(dist, r0));
-        MGCR_TRY(dist_halo_end(dist));
-        m.xh = dist_halo_ptr(dist);
-    }
+    MGCR_TRY(dist_prologue(dist, A, r0, &m));
     const int g = red_grid(A.nrow);
-    const unsigned grid = (unsigned)(g >= 64 ? (g + 7) / 8 * 8 : g);
-    const size_t lds_bytes = row_mat_lds_bytes(A);
+    const unsigned grid = fused_grid(g);
     const SkipRef sk = get_apply_skip();
-#define IA(MODE, WT)                                                                                                            \
-    hipLaunchKernelGGL((init_apply_kernel<MODE, WT>), dim3(grid), dim3(RED_THREADS), lds_bytes, ctx().stream, m, r0, aps0, b, A.nrow, g, \
-                       rm, partsA, partsR, partsN, sk.p, sk.it)
-    if (csr_stencil_active(A) && A.sten_near_f == 0x3eu && A.sten_halo_f > 0 && (A.sten_rare || sten_slots(A) == 7) && fused_tile_enabled() &&
-        A.reach >= fused_tile_min_reach()) {
-        const size_t win = 2 * (size_t)(RED_THREADS + 2 * A.sten_halo_f) * sizeof(cplx);
-#define IAT(NS, RARE, CARRY)                                                                                                        \
-    do {                                                                                                                            \
-        static bool big_lds = false;                                                                                                \
-        if (!big_lds) {                                                                                                             \
-            hipFuncSetAttribute((const void *)init_apply_tile_kernel<NS, RARE, CARRY>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024); \
-            big_lds = true;                                                                                                         \
-        }                                                                                                                           \
-        hipLaunchKernelGGL((init_apply_tile_kernel<NS, RARE, CARRY>), dim3(grid), dim3(RED_THREADS), win, ctx().stream, m, r0, aps0, b, A.nrow, g, rm, \
-                           partsA, partsR, partsN, sk.p, sk.it);                                                                    \
-    } while (0)
-        if (A.sten_rare && tile_carry(A, rm)) IAT(9, true, true);
-        else if (A.sten_rare) IAT(9, true, false);
-        else if (tile_carry(A, rm)) IAT(7, false, true);
-        else IAT(7, false, false);
-#undef IAT
-    } else if (csr_stencil_active(A)) {
-#define IAS(MODE, NS) hipLaunchKernelGGL((init_apply_kernel<MODE, NS>), dim3(grid), dim3(RED_THREADS), 0, ctx().stream, m, r0, aps0, b, A.nrow, g, \
-                                         rm, partsA, partsR, partsN, sk.p, sk.it)
-        if (A.sten_rare) IAS(4, 9);
-        else if (sten_slots(A) == 7) IAS(3, 7);
-        else IAS(3, 9);
-#undef IAS
-    }
-    else if (A.pat_mode == 1) { if (A.W == 7) IA(1, 7); else IA(1, 0); }
-    else if (A.pat_mode == 2) { if (A.W == 7) IA(2, 7); else IA(2, 0); }
-    else { if (A.W == 7) IA(0, 7); else IA(0, 0); }
-#undef IA
-    MGCR_HIP(hipGetLastError());
-    return MGCR_OK;
+    const FusedForm f = form_of(A, rm, FusedUse::Init);
+    return dispatch_form(f, [&](auto NS, auto RARE) -> int {
+        return dispatch_bool(f.carry, [&](auto CARRY) -> int {
+            return launch_windowed<init_apply_tile_kernel<decltype(NS)::value, decltype(RARE)::value, decltype(CARRY)::value>>(
+                grid, f.lds_bytes, m, r0, aps0, b, A.nrow, g, rm, partsA, partsR, partsN, sk.p, sk.it);
+        });
+    }, [&](auto MODE, auto WT) -> int {
+        return launch(init_apply_kernel<decltype(MODE)::value, decltype(WT)::value>, grid, RED_THREADS, f.lds_bytes, m, r0, aps0, b, A.nrow, g, rm,
+                      partsA, partsR, partsN, sk.p, sk.it);
+    });
 }
 
 // y = A x / y = w - k A x in the carried-window form; false: not this kind of operator (the caller takes its own kernels)
 bool csr_apply_carry(const CsrDev &A, const cplx *x, cplx *y, bool shift, cplx k, const cplx *w) {
-    static const bool on = !(getenv("MGCR_APPLY_CARRY") && atoi(getenv("MGCR_APPLY_CARRY")) == 0);
     // (planes below 64 x 1024 sites — 192^3: x is small enough for the caches to serve spmv.hip's far gathers, 38.6 against 44.2 us)
-    if (!on || !tile_regime(A) || A.nrow != A.ncol || A.n_tail_rows || A.reach < 64 * RED_THREADS) return false;
+    if (!g_apply_carry.on() || !tile_regime(A) || A.nrow != A.ncol || A.n_tail_rows || A.reach < 64 * RED_THREADS) return false;
     const int g = red_grid(A.nrow);
     if (g < 64 || g % 8) return false;
     const RowMap rm = make_row_map(A.nrow, g, A.reach);
     if (A.sten_rare || !tile_carry(A, rm)) return false;
     const RowMat m = row_mat(A, shift, k);
-    const size_t win = 2 * (size_t)(RED_THREADS + 2 * A.sten_halo_f) * sizeof(cplx);
+    const size_t win = fused_window_bytes(RED_THREADS, A.sten_halo_f, sizeof(cplx));
     const SkipRef sk = get_apply_skip();
-    static bool big_lds = false;
-    if (!big_lds) {
-        (void)hipFuncSetAttribute((const void *)sten_apply_carry_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-        (void)hipFuncSetAttribute((const void *)sten_apply_carry_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-        big_lds = true;
-    }
-    if (shift) hipLaunchKernelGGL((sten_apply_carry_kernel<true>), dim3((unsigned)g), dim3(RED_THREADS), win, ctx().stream, m, x, y, w, A.nrow, g, rm, sk.p, sk.it);
-    else hipLaunchKernelGGL((sten_apply_carry_kernel<false>), dim3((unsigned)g), dim3(RED_THREADS), win, ctx().stream, m, x, y, (const cplx *)nullptr, A.nrow, g, rm, sk.p, sk.it);
-    return hipGetLastError() == hipSuccess;
+    return dispatch_bool(shift, [&](auto SHIFT) -> int {
+        return launch_windowed<sten_apply_carry_kernel<decltype(SHIFT)::value>>((unsigned)g, win, m, x, y, decltype(SHIFT)::value ? w : (const cplx *)nullptr,
+                                                                                A.nrow, g, rm, sk.p, sk.it);
+    }) == MGCR_OK;
 }
 
 }  // namespace mgcr

@@ -562,16 +562,8 @@ __global__ void __launch_bounds__(RED_THREADS / RPT, RED_THREADS / RPT / 256) gc
 // ------------------------------------------------------------------------------------------------
 static int64_t g_resident_solves = 0;
 int64_t resident_solve_count() { return g_resident_solves; }
-static int g_resident = -1;
-static bool resident_enabled() {
-    if (g_resident < 0) g_resident = !(getenv("MGCR_RESIDENT") && atoi(getenv("MGCR_RESIDENT")) == 0);
-    return g_resident != 0;
-}
-bool set_resident_enabled(bool on) {
-    bool prev = resident_enabled();
-    g_resident = on ? 1 : 0;
-    return prev;
-}
+static EnvSwitch g_resident("MGCR_RESIDENT"), g_resident_tile("MGCR_RESIDENT_TILE");
+bool set_resident_enabled(bool on) { return g_resident.set(on); }
 
 ExchangeShared &exchange_shared() {
     static ExchangeShared s;
@@ -630,7 +622,7 @@ int resident_check(bool internal) {
     }
     return MGCR_OK;
 }
-bool one_launch_paths_enabled() { return resident_enabled() || stepbuild_is_enabled(); }
+bool one_launch_paths_enabled() { return g_resident.on() || stepbuild_is_enabled(); }
 
 // which instantiation a solve launches, with how much dynamic LDS, on how many workgroups (shared by the eligibility test,
 // which asks the runtime whether that launch is co-resident, and the launch itself)
@@ -644,14 +636,13 @@ static ResidentPlan resident_plan(const CsrDev &M, int storage, int restart, int
     ResidentPlan pl{};
     const int64_t n = M.nrow;
     pl.g = red_grid(n);
-    pl.grid = (unsigned)(pl.g >= 64 ? (pl.g + 7) / 8 * 8 : pl.g);
-    static const bool tile_on = !(getenv("MGCR_RESIDENT_TILE") && atoi(getenv("MGCR_RESIDENT_TILE")) == 0);
-    const bool tile = tile_on && csr_stencil_active(M) && !M.sten_rare && sten_slots(M) == 7 && M.sten_near_f == 0x3eu && M.sten_halo_f > 0 &&
+    pl.grid = fused_grid(pl.g);
+    const bool tile = g_resident_tile.on() && csr_stencil_active(M) && !M.sten_rare && sten_slots(M) == 7 && M.sten_near_f == 0x3eu && M.sten_halo_f > 0 &&
                       M.sten_halo_f <= RES_TILE_HALO;
     pl.tile_h = tile ? M.sten_halo_f : 0;
     pl.lds_bytes = tile ? sizeof(cplx) * (size_t)(RED_THREADS + 2 * pl.tile_h) : csr_stencil_active(M) ? 0 : row_mat_lds_bytes(M);
     const int R = storage <= 5 && (restart == 5 || max_it < restart) ? 5 : 10;
-    static const int rpt_env = getenv("MGCR_RESIDENT_RPT") ? atoi(getenv("MGCR_RESIDENT_RPT")) : 0;
+    static const int rpt_env = (int)env_int64("MGCR_RESIDENT_RPT", 0);
     int rpt = rpt_env == 1 || rpt_env == 2 || rpt_env == 4 ? rpt_env : RES_RPT_DEFAULT;
 #define RES_K(MODE, NS, RR, RPT) ((const void *)gcr_resident_kernel<MODE, NS, RR, RPT>)
 #ifdef MGCR_RES_ALL_RPT   /* experiments: one and four rows per thread as well (build with EXTRA=-DMGCR_RES_ALL_RPT) */
@@ -674,7 +665,7 @@ static ResidentPlan resident_plan(const CsrDev &M, int storage, int restart, int
 }
 
 bool gcr_resident_eligible(const Op *A, const mgcr_gcr_param &p, int storage, int restart, int64_t n, bool lean, bool nested_handoff) {
-    if (!resident_enabled() || !lean || nested_handoff) return false;
+    if (!g_resident.on() || !lean || nested_handoff) return false;
     if (p.use_x0 || p.flexible || p.left_precond || p.right_precond || p.profile_spmv) return false;
     if (comm_live_count() > 0) return false;   // several processes may share this GPU: a launch that needs the whole chip could wait on another one
     const Op *b0 = A->kind == OP_DIRAC ? A->base : A;
@@ -721,8 +712,8 @@ int gcr_resident_run(Op *A, const mgcr_gcr_param &p, int storage, int restart, c
     a.alpha_only_last = alpha_only_last ? 1 : 0;
     const ResidentPlan pl = resident_plan(M, storage, restart, a.max_it);
     a.tile_h = pl.tile_h;
-    a.spin_limit = getenv("MGCR_TEST_RESIDENT_SPIN_LIMIT") ? atoi(getenv("MGCR_TEST_RESIDENT_SPIN_LIMIT")) : RES_SPIN_LIMIT;
-    a.test_stall = getenv("MGCR_TEST_RESIDENT_STALL") ? atoi(getenv("MGCR_TEST_RESIDENT_STALL")) : 0;
+    a.spin_limit = (int)env_int64("MGCR_TEST_RESIDENT_SPIN_LIMIT", RES_SPIN_LIMIT);
+    a.test_stall = (int)env_int64("MGCR_TEST_RESIDENT_STALL", 0);
     {   // how far a row's gathers go: exactly for the stencil view, CsrDev::reach otherwise (0 = unknown: every workgroup)
         int64_t reach = 0;
         if (csr_stencil_active(M)) for (int c = 0; c < M.sten_ns; c++) reach = std::max<int64_t>(reach, std::llabs((long long)M.sten_off[c]));
@@ -828,7 +819,7 @@ int coherence_selftest(int steps, int coherent, int64_t *rows_wrong) {
     ca.a = a; ca.b = b; ca.n = n; ca.shift = shift; ca.steps = steps; ca.coherent = coherent; ca.nblk = nblk;
     ca.slots = sh.slots; ca.abort_dev = sh.abort_dev; ca.abort_host = sh.abort_host;
     ca.gen0 = exchange_take_generations((unsigned)steps + 1u);
-    ca.spin_limit = getenv("MGCR_TEST_RESIDENT_SPIN_LIMIT") ? atoi(getenv("MGCR_TEST_RESIDENT_SPIN_LIMIT")) : RES_SPIN_LIMIT;
+    ca.spin_limit = (int)env_int64("MGCR_TEST_RESIDENT_SPIN_LIMIT", RES_SPIN_LIMIT);
     hipLaunchKernelGGL(coherence_selftest_kernel, dim3((unsigned)nblk), dim3(RED_THREADS), 0, ctx().stream, ca);
     MGCR_HIP(hipGetLastError());
     MGCR_HIP(hipMemcpyAsync(h.data(), (steps & 1) ? b : a, sizeof(cplx) * (size_t)n, hipMemcpyDeviceToHost, ctx().stream));

@@ -671,7 +671,7 @@ bool csr_step_build_eligible(const CsrDev &A, const DistCsr *dist, int lim) {
     const int g = red_grid(A.nrow);
     if (g < 64 || g % 8 != 0) return false;   // (smaller systems have the resident solver or the xr-fused kernels)
     if ((int64_t)g * RED_THREADS * SB_MAX_TRIPS < A.nrow) return false;
-    if (A.reach >= ((int64_t)1 << 15)) return false;   // rows that reach this far take the LDS-window kernels (gcr_fused.hip)
+    if (A.reach >= FUSED_TILE_REACH_DEFAULT) return false;   // rows that reach this far take the LDS-window kernels (gcr_fused.hip)
     if (exchange_shared_init() != MGCR_OK) return false;
     if (g > RES_BLK) return false;
     // every form the step may be launched in (with / without the next residual update, closing or not) must be co-resident

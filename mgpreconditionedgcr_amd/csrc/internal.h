@@ -206,6 +206,11 @@ struct EnvSwitch {
         return prev;
     }
 };
+// a numeric knob: the variable's value, `dflt` when it is unset (read whenever this is called: callers that read once keep the result)
+inline int64_t env_int64(const char *name, int64_t dflt) {
+    const char *s = getenv(name);
+    return s ? atoll(s) : dflt;
+}
 
 // a device buffer that is freed unless it is handed over (release): temporaries, and allocations on their way into a structure
 template <typename T>
@@ -241,6 +246,13 @@ static int dispatch_value(int v, F &&f) {
 }
 template <typename F>
 static int dispatch_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// one kernel launch on the library's stream
+template <typename... KA, typename... AA>
+static int launch(void (*kernel)(KA...), unsigned grid, int block, size_t lds, AA... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, ctx().stream, args...);
+    MGCR_HIP(hipGetLastError());
+    return MGCR_OK;
+}
 
 // ---- spmv_build.hip (formats) / spmv.hip (apply) ------------------------------------------------
 int csr_build_device(int64_t nrow, int64_t ncol, const int64_t *h_rowptr, const int64_t *h_col,

@@ -568,12 +568,6 @@ static SkipRef g_skip;  // consulted by apply kernels (set by the GCR driver aro
 void set_apply_skip(SkipRef s) { g_skip = s; }
 SkipRef get_apply_skip() { return g_skip; }
 
-template <typename... KA, typename... AA>
-static int launch(void (*kernel)(KA...), unsigned grid, int block, size_t lds, AA... args) {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, ctx().stream, args...);
-    MGCR_HIP(hipGetLastError());
-    return MGCR_OK;
-}
 // `rows` rows in tiles of `tile`: from 64 tiles on, the grid is padded to a multiple of 8 and every XCD takes one band (xcd_tile)
 struct Tiles { int64_t ntiles; bool xcd; unsigned grid; };
 static Tiles tiles_of(int64_t rows, int tile) {

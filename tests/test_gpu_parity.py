@@ -511,7 +511,7 @@ def test_lean_restart_cycles_match_classic(kind, restart, tol, sample, sample_or
     assert t1 <= max(2.0 * t0, 1.05 * tol)
 
 
-@pytest.mark.parametrize("fmt", ["pattern", "slab", "dirac-pattern", "slab-generic-width"])
+@pytest.mark.parametrize("fmt", ["pattern", "slab", "dirac-pattern", "slab-generic-width", "pattern-offsets-only"])
 @pytest.mark.parametrize("mode", [dict(restart=5), dict(restart=10), dict(truncation=3), dict()])
 def test_fused_apply_and_dots_same_bits(fmt, mode):
     """SpMV + beta dot products as one kernel (spmv.hip: spmv_multidot_kernel) against the two separate
@@ -520,6 +520,8 @@ def test_fused_apply_and_dots_same_bits(fmt, mode):
     n1 = 40 if "pattern" in fmt else 20
     n, ncol, rowptr, col, val = problems.poisson3d_csr(n1)
     val = val * (1.0 - 0.25j)
+    if fmt == "pattern-offsets-only":   # a value of its own per entry: the dictionary keeps the column offsets only (format 2)
+        val = val * (1.0 + 0.01 * np.random.default_rng(3).standard_normal(val.size))
     if fmt == "slab-generic-width":   # rows of up to 5 entries: the run-time-width code path
         keep = np.ones(val.size, bool)
         keep[rowptr[:-1]] = np.diff(rowptr) < 6
@@ -533,6 +535,7 @@ def test_fused_apply_and_dots_same_bits(fmt, mode):
     finally:
         mg.set_option("pattern_storage", prev)
     assert (A.storage_format()[0] != 0) == ("pattern" in fmt)
+    assert (A.storage_format()[0] == 2) == (fmt == "pattern-offsets-only")
     op = DiracOp(A, 0.05 + 0.02j) if fmt.startswith("dirac") else A
     b = Field((n,), problems.rhs_grid(n, 8))
     out = []
