@@ -26,15 +26,34 @@ __global__ void __launch_bounds__(256) dense_column_kernel(cplx *M, const cplx *
 }
 // pivot step k: the row p >= k with the largest |M[p][k]| (smallest p among equals: deterministic) is swapped into
 // row k and normalised; the column of multipliers is saved for the elimination kernel.  One workgroup.
+// Candidates are ranked by x^2 + y^2 of the column scaled by the power of two of its largest component: exact, so the
+// order and the ties are those of the unscaled squares wherever these neither overflow nor underflow, and 2^-600 A or
+// 2^+600 A pivots like A (unscaled, every candidate of the one squares to zero — "singular" — and of the other to infinity).
 __global__ void __launch_bounds__(1024) dense_pivot_kernel(cplx *M, int64_t n, int64_t k, cplx *colk, int *singular) {
     __shared__ double sbest[1024];
     __shared__ int64_t sidx[1024];
     const int t = threadIdx.x;
+    double big = 0.;
+    for (int64_t i = k + t; i < n; i += 1024) {
+        const cplx v = M[i * 2 * n + k];
+        big = fmax(big, fmax(fabs(v.x), fabs(v.y)));
+    }
+    sbest[t] = big;
+    __syncthreads();
+    for (int s = 512; s >= 1; s >>= 1) {
+        if (t < s) sbest[t] = fmax(sbest[t], sbest[t + s]);
+        __syncthreads();
+    }
+    big = sbest[0];
+    __syncthreads();
+    if (!(big > 0.)) { if (t == 0) *singular = 1; return; }
+    const int e = big <= 1.7976931348623157e308 ? ilogb(big) : 1023;
     double best = -1.;
     int64_t bi = k;
     for (int64_t i = k + t; i < n; i += 1024) {
         const cplx v = M[i * 2 * n + k];
-        const double a = v.x * v.x + v.y * v.y;
+        const double x = scalbn(v.x, -e), y = scalbn(v.y, -e);
+        const double a = x * x + y * y;
         if (a > best) { best = a; bi = i; }
     }
     sbest[t] = best; sidx[t] = bi;
