@@ -18,6 +18,10 @@
 // closing coefficients) IS the three-kernel path's: gcr_dev.h; the exchange scaffolding is exchange_dev.h's.
 // Up to 3 stored directions (the closing step with XR at 3 excepted) step_keep_kernel runs the step, reading r once; beyond
 // that, and as the reference side of tests/test_gpu_stepbuild_keep_all.py, step_build_kernel.
+// Neither reads from memory what it holds: step_keep_kernel's build takes its first Ap_0 rows from the registers of the pass-1
+// dots (sb_keep_rows), and the closing step_build_kernel at 4 and 5 directions loads a row's r once for the close pass and the
+// build, which are one loop there, the thread's last close row behind the exchange-2 publish (sb_close_merged;
+// tests/test_gpu_stepbuild_reuse.py: the same bits, tests/test_stepbuild_reuse_regs.py: the same registers class).
 //
 // Needs all workgroups co-resident (they wait for each other): 64 VGPRs and <= 80 KB of LDS each, at most 2 x #CU
 // workgroups, no other process on the device (no live communicator).  Up to 5 stored directions (beyond that the
@@ -40,6 +44,11 @@ namespace mgcr {
 constexpr int SB_MAX_TRIPS = 4;     // rows per thread whose Ar stays in LDS (4 x 1024 x 16 B = 64 KB per workgroup)
 constexpr int SB_MAX_ND = 5;
 constexpr int SB_KEEP_TB = 2;      // step_keep_kernel: trips whose streams are in registers at a time
+// step_keep_kernel: rows of Ap_0 that stay in registers from the pass-1 dots to the build (4 at 1 direction, 3 or 4 at 2 spill)
+template <int NDT> constexpr int sb_keep_rows() { return NDT == 1 ? 3 : 2; }
+// step_build_kernel<CLOSE>: the forms whose close pass and build are one loop over the rows — those it costs no scratch (at 3
+// directions the build's prefetched first row lives longer: 28 B; at 5 without the next residual update, a solve's last step: 12 B)
+template <int NDT, bool XR, bool CLOSE> constexpr bool sb_close_merged() { return CLOSE && (NDT == 4 || (NDT == 5 && XR)); }
 
 struct StepBuildArgs {
     RowMat m;
@@ -178,7 +187,33 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
     for (int j = 0; j < NDT; j++) beta[j] = to_sgpr(sbeta[j]);
     double v[4] = {0., 0., 0., 0.};
     int trip = 0;
-    if constexpr (CLOSE) {
+    // CLOSE with 4 or 5 directions: ONE loop over the rows — r of a row is loaded once for its close row and its build row — and
+    // the thread's last close row waits until the exchange-2 partials are on their way (sb_close_merged)
+    constexpr bool MERGED = sb_close_merged<NDT, XR, CLOSE>();
+    cplx mcp[MERGED ? NDT : 1], mcx[MERGED ? NDT : 1];
+    if constexpr (MERGED) {
+#pragma unroll
+        for (int j = 0; j < NDT; j++) {
+            mcp[j] = to_sgpr(scp[j]);
+            mcx[j] = to_sgpr(a.lc->cx[j]);   // (before this workgroup publishes: workgroup 0 rewrites lc->cx behind poll 2)
+        }
+    }
+    // x += sum_j cx_j p_j;  P0' = r - sum_j cp_j p_j for one row, as in the close pass below: p_out = ps[0] is read before it is
+    // written, and xr_out = ps[1] is read here before XR writes it (every close row precedes poll 2)
+    auto close_row = [&](int64_t i, cplx dv) {
+        cplx pj[NDT];
+#pragma unroll
+        for (int j = 0; j < NDT; j++) pj[j] = ld_stream<NTS>(a.ps[j] + i);
+        cplx xv = a.xvec[i];
+#pragma unroll
+        for (int j = 0; j < NDT; j++) xv = cadd(xv, cmul(mcx[MERGED ? j : 0], pj[j]));
+        a.xvec[i] = xv;
+        cplx pc = make_double2(0., 0.);
+#pragma unroll
+        for (int j = 0; j < NDT; j++) pc = csub(pc, cmul(mcp[MERGED ? j : 0], pj[j]));
+        st_stream<NTS>(a.p_out + i, cadd(dv, pc));
+    };
+    if constexpr (CLOSE && !MERGED) {
         // x += sum_j cx_j p_j;  P0' = dir - sum_j cp_j p_j  (p_0 = P0, p_m = D_m): a pass of its own over the p streams, so that they
         // and the Ap streams below are never in registers together (64 VGPRs: two workgroups per CU)
         cplx cp[NDT], cx[NDT];
@@ -205,11 +240,11 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
     }
     // (kept as a lambda that returns the row's r: written as the loop's body, the same statements change the registers of thirty
     // instantiations — profiles/scalar_stage_refactor_resource_usage.md)
-    auto build_row = [&](int64_t i, int trip) -> cplx {
+    auto build_row = [&](int64_t i, int trip, cplx r_have) -> cplx {   // r_have: the row's r, where the caller holds it (MERGED)
         cplx aj[NDT];
 #pragma unroll
         for (int j = 0; j < NDT; j++) aj[j] = (PRE && !CLOSE && i == i0) ? pre[j] : ld_stream<NTS>(a.aps[j] + i);
-        const cplx av = arL[trip * RED_THREADS + (int)threadIdx.x], rv = a.x[i];
+        const cplx av = arL[trip * RED_THREADS + (int)threadIdx.x], rv = MERGED ? r_have : a.x[i];
         cplx ac = make_double2(0., 0.);
 #pragma unroll
         for (int j = 0; j < NDT; j++) ac = csub(ac, cmul(beta[j], aj[j]));
@@ -222,9 +257,27 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
         v[2] += u.x; v[3] += u.y;
         return rv;
     };
-    for (int64_t i = i0; i < end; i += stride, trip++) (void)build_row(i, trip);
+    if constexpr (MERGED) {
+        for (int64_t i = i0; i < end; i += stride, trip++) {
+            const cplx rv = a.x[i];
+            if (!XR || i + stride < end) close_row(i, rv);   // (XR: the thread's last row waits for the publish below)
+            __builtin_amdgcn_sched_barrier(0);   // (the p streams and the Ap streams are never in registers together)
+            (void)build_row(i, trip, rv);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    } else {
+        for (int64_t i = i0; i < end; i += stride, trip++) (void)build_row(i, trip, make_double2(0., 0.));
+    }
     const double mine = block_sum_owner<4>(v, lds);
     if (threadIdx.x < 4) a.partsA[threadIdx.x * RED_MAX_BLOCKS + lb] = mine;
+    // MERGED with XR: the thread's last close row (its r loaded again: kept across the block sum it spills) behind the publish
+    auto close_last = [&]() {
+        if (trip > 0) {
+            const int64_t il = i0 + (int64_t)(trip - 1) * stride;
+            close_row(il, a.x[il]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
     if constexpr (XR) {
         // ---- the next step's residual update (gcr.hip xr_update_kernel<true, true>): alpha needs <r,Ap'>, <Ap',Ap'> over ALL
         // workgroups — a second exchange instead of a kernel boundary; r and Ap' of the thread's rows are on the chip ----
@@ -232,6 +285,7 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
             const v4i w4 = {__double2loint(mine), __double2hiint(mine), (int)sy.gen, 0};
             __builtin_amdgcn_raw_buffer_store_b128(w4, sy.slots, ((2 * RES_NV + (int)threadIdx.x) * RES_BLK + lb) * 16, 0, RES_SC1);
         }
+        if constexpr (MERGED) close_last();   // (streams while the exchange-2 partials travel)
         const cplx xr0 = i0 < end ? a.x[i0] : make_double2(0., 0.);   // (requested before the polls, like `pre` above)
         if (!res_collect<4>(sy, 2)) {
             res_abort(a.abort_dev, a.abort_host);
@@ -282,8 +336,10 @@ __device__ __forceinline__ double sb_block_owner_from_lds(double *lds) {
 // KEEP-ALL: step_build_kernel's step (in-cycle / closing, with / without XR) with r read ONCE per launch: the thread's residual
 // rows are loaded by the apply, next to the stencil gather (the same lines: a cache hit), and stay in registers (SB_MAX_TRIPS x
 // 16 B) for the shift epilogue, the build's <r,Ap'>, the close pass's P0' and XR; no later pass loads a.x.
-// Register use: the pass-1 dots walk one direction (all trips) at a time and hand its two sums to the wave trees as soon as they
-// are final (sb_wave_pair_to_lds: the bits of block_sum_owner<2 NDT>); the build and the close pass walk SB_KEEP_TB trips at a
+// Register use: the pass-1 dots walk one direction (all trips) at a time, the last direction first, and hand its two sums to the
+// wave trees as soon as they are final (sb_wave_pair_to_lds: the bits of block_sum_owner<2 NDT>, whatever the order of the
+// directions); the first sb_keep_rows rows of Ap_0, which the dots load last, stay in registers across exchange 1 for the build
+// (no stream is requested ahead of that exchange's polls any more); the build and the close pass walk SB_KEEP_TB trips at a
 // time, one direction after the other; every stream is addressed as scalar base + one 32-bit offset per trip.  Every element sees
 // the same operations in the same order as in step_build_kernel (ac -= beta_j Ap_j in j order, each per-thread accumulator adds
 // the rows in trip order): the same bits.  Only the forms that fit 64 VGPRs without scratch are launched (sb_keep_fits).
@@ -334,9 +390,15 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs
         __builtin_amdgcn_sched_barrier(0);   // (one trip's gathers in registers at a time)
     }
     // ---- <Ar, Ap_j>, one direction (all trips) at a time: its two sums go through the wave trees as soon as they are final ----
+    // The directions are walked LAST TO FIRST (every direction's pair of sums has its own LDS slots, so their order enters no
+    // sum): Ap_0 comes last and its first KT rows stay in registers for the build, which starts with Ap_0 — those rows are not
+    // read again (the streams are non-temporal and a vector is an XCD's whole L2: a re-read is a trip to memory).
+    constexpr int KT = sb_keep_rows<NDT>();
+    cplx pre[KT];
     {
 #pragma unroll
-        for (int j = 0; j < NDT; j++) {
+        for (int jj = 0; jj < NDT; jj++) {
+            const int j = NDT - 1 - jj;
             cplx b[SB_MAX_TRIPS];
 #pragma unroll
             for (int t = 0; t < SB_MAX_TRIPS; t++) b[t] = row(t) < end ? ld_stream<true>(at(a.aps[j], t)) : make_double2(0., 0.);
@@ -349,6 +411,10 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs
                     v[1] += tt.y;
                 }
             }
+            if (j == 0) {
+#pragma unroll
+                for (int u = 0; u < KT; u++) pre[u] = b[u];
+            }
             sb_wave_pair_to_lds(v, lds, 2 * j);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -358,10 +424,6 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs
             __builtin_amdgcn_raw_buffer_store_b128(w4, sy.slots, ((1 * RES_NV + tid) * RES_BLK + lb) * 16, 0, RES_SC1);
         }
     }
-    // the build's first streams are requested before the exchange is polled (they do not depend on beta)
-    cplx pre[SB_KEEP_TB];
-#pragma unroll
-    for (int u = 0; u < SB_KEEP_TB; u++) pre[u] = row(u) < end ? ld_stream<NTS>(at(a.aps[0], u)) : make_double2(0., 0.);
     if (!res_collect<2 * NDT>(sy, 1)) {
         res_abort(a.abort_dev, a.abort_host);
         for (int64_t i = i0; i < end; i += stride) a.ap_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
@@ -404,7 +466,9 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs
                 cplx aj[SB_KEEP_TB];
 #pragma unroll
                 for (int u = 0; u < SB_KEEP_TB; u++)
-                    aj[u] = (t0 == 0 && j == 0) ? pre[u] : row(t0 + u) < end ? ld_stream<NTS>(at(a.aps[j], t0 + u)) : make_double2(0., 0.);
+                    aj[u] = (j == 0 && t0 + u < KT) ? pre[t0 + u < KT ? t0 + u : 0]
+                            : row(t0 + u) < end   ? ld_stream<NTS>(at(a.aps[j], t0 + u))
+                                                  : make_double2(0., 0.);
 #pragma unroll
                 for (int u = 0; u < SB_KEEP_TB; u++) ac[u] = csub(ac[u], cmul(beta[j], aj[u]));
                 __builtin_amdgcn_sched_barrier(0);

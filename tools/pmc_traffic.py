@@ -40,7 +40,7 @@ def load(d, counter):
 def phase_of(name):
     if name.startswith("xr_update_kernel"):
         return "xr"
-    if name.startswith(("step_apply_kernel", "step_apply_tile_kernel", "step_apply_xr", "step_build_kernel", "multidot_kernel")):   # (step_build: apply + dots + build in one launch)
+    if name.startswith(("step_apply_kernel", "step_apply_tile_kernel", "step_apply_xr", "step_build_kernel", "step_keep_kernel", "multidot_kernel")):   # (step_build, step_keep: apply + dots + build in one launch)
         return "apply_dots"
     if name.startswith(("pat_spmv", "ell_spmv", "csr_tail", "sten_spmv")):
         return "spmv"   # stand-alone applies (set-up, bench.py's replay / cold-cache loops)
@@ -82,6 +82,12 @@ def main():
           # per kernel too: bench.py weights these by the mix of kernels its timed iterations launched (iteration k of a restart
           # cycle orthogonalises against k directions), so that `traffic` and `achieved` describe the same launches
           "kernel_hbm_bytes_per_launch": {name: b for name, calls, favg, wavg, b in rows if phase_of(name)}}
+    try:   # the other workloads' records (tools/pmc_workload.py) carry their own stamps: keep them
+        old = json.load(open(out_json))
+        if "workloads" in old:
+            js["workloads"] = old["workloads"]
+    except (OSError, ValueError):
+        pass
     json.dump(js, open(out_json, "w"), indent=1)
     print(json.dumps(js, indent=1))
 
