@@ -104,6 +104,23 @@ int mgcr_csr_create(int64_t nrow, int64_t ncol, const int64_t *rowptr, const int
  * borrows its Sparse*). */
 int mgcr_dirac_create(mgcr_op_t csr, const double k_ri[2], mgcr_op_t *out);
 int mgcr_dirac_set_k(mgcr_op_t dirac, const double k_ri[2]);       /* set_k src/Operator.h:116 */
+/* MultiDiracOp: 1 - k_j D on column j of a block of exactly k Fields (hopping-parameter scans: one D, one stream of the matrix,
+ * a ladder of k_j; no reference counterpart — test_kcritical, src/main.cpp:696-741, builds one DiracOp per value).  Borrows `csr`
+ * as mgcr_dirac_create does.  k_ri: [k][2], 1 <= k <= 16; a zero k_j, k outside 1 .. 16: MGCR_ERR_INVALID; a distributed
+ * Sparse: MGCR_ERR_UNSUPPORTED.  ONLY mgcr_op_apply_multi and mgcr_gcr_solve_multi take it, with blocks of exactly k columns
+ * (any other width: MGCR_ERR_INVALID); the entry points that work on one Field (mgcr_op_apply, mgcr_gcr_solve, mgcr_gcr_create,
+ * mgcr_gcr_set_operator, mgcr_mg_create, mgcr_bench_op_apply) answer MGCR_ERR_UNSUPPORTED.  The queries (mgcr_op_dim / nrow /
+ * nnz / stored_bytes / storage_format / ell_layout / xr_fuse_kind) answer for the Sparse, as for a DiracOp.
+ * Rule 1: column j of mgcr_op_apply_multi(MultiDiracOp(D, ks), X) is BIT-IDENTICAL to mgcr_op_apply of DiracOp(D, ks[j]) on
+ * column j of X.
+ * Rule 2: history, iteration count, convergence flag and x of column j of mgcr_gcr_solve_multi are BIT-IDENTICAL to
+ * mgcr_gcr_solve with DiracOp(D, ks[j]) on column j alone, under the conditions mgcr_gcr_solve_multi states (default options,
+ * mgcr_op_xr_fuse_kind 0 or 1, more rows than the small-solve limit).  The columns of a scan stop at different steps; a
+ * stopped column is frozen as in every batched solve.
+ * mgcr_dirac_multi_set_k replaces all k values (same count).  They travel in the kernel arguments of each launch: the new
+ * values hold for every later call and never for work already enqueued. */
+int mgcr_dirac_multi_create(mgcr_op_t csr, int32_t k, const double *k_ri /* [k][2] */, mgcr_op_t *out);
+int mgcr_dirac_multi_set_k(mgcr_op_t op, const double *k_ri /* [k][2] */);
 /* HierarchicalSparse<long,int> (block-CSR of dense bs x bs blocks, row-major inside a block,
  * src/HierarchicalSparse.h:22-48) from UNSORTED (block-row, block-col, block) triplets with the
  * constructor's semantics (:58-98): sorted by row*nbcol+col, duplicates of a pair kept and
@@ -124,7 +141,7 @@ int mgcr_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y);
  * mgcr_op_apply on column j: per column the kernels add a row's products in the order mgcr_op_ell_layout documents (block-CSR:
  * per block in column order, blocks in storage order), whichever storage form carries the matrix.  Supported: single-GPU
  * Sparse in every storage form (ELL slab + CSR tail with 1 .. 16 lanes per row, the LDS-window variant, both row-pattern
- * dictionary forms, the stencil view), DiracOp on top of any of them, HierarchicalSparse / Dense.  Distributed operators
+ * dictionary forms, the stencil view), DiracOp and MultiDiracOp on top of any of them, HierarchicalSparse / Dense.  Distributed operators
  * and GCR / MG objects: MGCR_ERR_UNSUPPORTED.  X == Y, mismatched n or k: MGCR_ERR_INVALID.
  * Block-CSR stages min(k, 64 / bs) (at least 1) columns of products and k columns of accumulators in LDS,
  * 16 (kg bs (bs + 1) + bs k) bytes: block sizes for which that exceeds 160 KiB (bs from about 95, depending on k) are

@@ -238,6 +238,74 @@ private:
 };
 
 // ------------------------------------------------------------------------------------------------
+// MultiField — a block of k Fields on one mesh (multi-RHS; the reference has no counterpart, include/mgcr.h
+// mgcr_mvec_*).  Lives on the device with the columns interleaved; columns go in and out as Fields.
+// ------------------------------------------------------------------------------------------------
+template <typename num_type>
+class MultiField {
+public:
+    MultiField(Mesh<num_type> m, int ncols) : mesh(std::move(m)), k(ncols) { alloc(); }
+    // k Fields of one size, packed on the device
+    explicit MultiField(const std::vector<const Field<num_type> *> &fields) : mesh(first(fields)->get_mesh()), k((int)fields.size()) {
+        alloc();
+        for (int j = 0; j < k; j++) set_column(j, *fields[(size_t)j]);
+    }
+    explicit MultiField(const std::vector<Field<num_type>> &fields) : MultiField(pointers(fields)) {}
+    MultiField(MultiField const &o) : mesh(o.mesh), k(o.k) { alloc(); for (int j = 0; j < k; j++) set_column(j, o.column(j)); }
+    MultiField &operator=(MultiField const &) = delete;
+    ~MultiField() { if (h) mgcr_mvec_destroy(h); }
+
+    int ncols() const { return k; }
+    num_type field_size() const { return mesh.get_size(); }
+    Mesh<num_type> get_mesh() const { return mesh; }
+    Field<num_type> column(int j) const {
+        Field<num_type> out(mesh);
+        mgcr_detail::ok(mgcr_mvec_get_column(h, j, out.device()), "MultiField::column");
+        out.device_written();
+        return out;
+    }
+    void set_column(int j, const Field<num_type> &f) {
+        if (f.field_size() != field_size()) { std::fprintf(stderr, "Lengths of two fields do not match!\n"); std::abort(); }
+        mgcr_detail::ok(mgcr_mvec_set_column(h, j, f.device()), "MultiField::set_column");
+    }
+    void set_zero() { mgcr_detail::ok(mgcr_mvec_zero(h), "MultiField::set_zero"); }
+    // <this_j, f_j> (conj on *this) and |this_j|^2 for every column, in one pass each
+    std::vector<std::complex<double>> dot(const MultiField &f) const {
+        std::vector<double> o((size_t)2 * k);
+        mgcr_detail::ok(mgcr_mvec_dot(h, f.h, o.data()), "MultiField::dot");
+        std::vector<std::complex<double>> r((size_t)k);
+        for (int j = 0; j < k; j++) r[(size_t)j] = std::complex<double>(o[(size_t)2 * j], o[(size_t)2 * j + 1]);
+        return r;
+    }
+    std::vector<double> squarednorm() const {
+        std::vector<double> o((size_t)k);
+        mgcr_detail::ok(mgcr_mvec_norm2(h, o.data()), "MultiField::squarednorm");
+        return o;
+    }
+    // this_j += alpha_j x_j
+    void axpy(const std::vector<std::complex<double>> &alpha, const MultiField &x) {
+        if ((int)alpha.size() != k) { std::fprintf(stderr, "MultiField::axpy: one coefficient per column\n"); std::abort(); }
+        mgcr_detail::ok(mgcr_mvec_axpy(reinterpret_cast<const double *>(alpha.data()), x.h, h), "MultiField::axpy");
+    }
+    mgcr_mvec_t device() const { return h; }
+
+private:
+    static const Field<num_type> *first(const std::vector<const Field<num_type> *> &fields) {
+        if (fields.empty()) { std::fprintf(stderr, "MultiField: no Fields\n"); std::abort(); }
+        return fields[0];
+    }
+    static std::vector<const Field<num_type> *> pointers(const std::vector<Field<num_type>> &fields) {
+        std::vector<const Field<num_type> *> p;
+        for (const Field<num_type> &f : fields) p.push_back(&f);
+        return p;
+    }
+    void alloc() { mgcr_detail::ensure_init(); mgcr_detail::ok(mgcr_mvec_create((int64_t)mesh.get_size(), k, &h), "MultiField alloc"); }
+    Mesh<num_type> mesh;
+    int k = 0;
+    mgcr_mvec_t h = nullptr;
+};
+
+// ------------------------------------------------------------------------------------------------
 // Operator — src/Operator.h:16-29
 // ------------------------------------------------------------------------------------------------
 template <typename num_type>
@@ -251,6 +319,16 @@ public:
     virtual ~Operator() = default;
     // device handle of this operator (built on demand); nullptr for purely host-defined operators
     virtual mgcr_op_t handle() { return nullptr; }
+    // Y = op(X) for a block of Fields: the matrix is streamed once for all columns, column j has the bits of op(X.column(j))
+    // (extension, mgcr_op_apply_multi: Sparse, DiracOp, MultiDiracOp, HierarchicalSparse / Dense)
+    MultiField<num_type> apply_multi(const MultiField<num_type> &X) {
+        mgcr_op_t op = handle();
+        if (!op) { std::fprintf(stderr, "Operator has no device representation\n"); std::abort(); }
+        num_type rows = (num_type)mgcr_op_nrow(op);
+        MultiField<num_type> out(rows == X.field_size() ? X.get_mesh() : Mesh<num_type>(&rows, 1), X.ncols());
+        mgcr_detail::ok(mgcr_op_apply_multi(op, X.device(), out.device()), "Operator apply_multi");
+        return out;
+    }
 
 protected:
     Field<num_type> apply_handle(const Field<num_type> &f, mgcr_op_t op, num_type out_rows) {
@@ -401,6 +479,44 @@ public:
 
 private:
     std::complex<double> k = 0.;
+    Sparse<num_type> *D;
+    mgcr_op_t op = nullptr, base_seen = nullptr;
+};
+
+// MultiDiracOp: Id - ks[j]*D on column j of a block of ks.size() Fields — a hopping-parameter scan (the ladder of
+// test_kcritical, src/main.cpp:696-741) as ONE operator (extension, mgcr_dirac_multi_create).  Borrows the Sparse.  Only
+// apply_multi and GCR::solve_multi take it; column j has the bits of DiracOp(D, ks[j]) on that column alone.
+template <typename num_type>
+class MultiDiracOp : public Operator<num_type> {
+public:
+    MultiDiracOp(Sparse<num_type> *mat, std::vector<std::complex<double>> k_factors) : ks(std::move(k_factors)), D(mat) { this->dim = D->get_dim(); }
+    MultiDiracOp(MultiDiracOp const &o) : ks(o.ks), D(o.D) { this->dim = D->get_dim(); }
+    ~MultiDiracOp() override { if (op) mgcr_op_destroy(op); }
+    int ncols() const { return (int)ks.size(); }
+    std::complex<double> val_at(num_type, num_type) const override { return no_single("val_at"); }
+    std::complex<double> val_at(num_type) const override { return no_single("val_at"); }
+    Field<num_type> operator()(Field<num_type> const &f) override { no_single("operator()"); return f; }
+    void set_k(std::vector<std::complex<double>> new_ks) {   // same count; holds for every later apply / solve
+        if (new_ks.size() != ks.size()) { std::fprintf(stderr, "MultiDiracOp::set_k: %zu values for %zu columns\n", new_ks.size(), ks.size()); std::abort(); }
+        ks = std::move(new_ks);
+        if (op) mgcr_detail::ok(mgcr_dirac_multi_set_k(op, reinterpret_cast<const double *>(ks.data())), "MultiDiracOp::set_k");
+    }
+    mgcr_op_t handle() override {
+        mgcr_op_t base = D->handle();
+        if (!op || base != base_seen) {
+            if (op) mgcr_op_destroy(op);
+            mgcr_detail::ok(mgcr_dirac_multi_create(base, (int32_t)ks.size(), reinterpret_cast<const double *>(ks.data()), &op), "MultiDiracOp");
+            base_seen = base;
+        }
+        return op;
+    }
+
+private:
+    static std::complex<double> no_single(const char *what) {
+        std::fprintf(stderr, "MultiDiracOp::%s: one hopping parameter per column of a block; use apply_multi / GCR::solve_multi\n", what);
+        std::abort();
+    }
+    std::vector<std::complex<double>> ks;
     Sparse<num_type> *D;
     mgcr_op_t op = nullptr, base_seen = nullptr;
 };
@@ -644,6 +760,31 @@ public:
         std::ofstream file("../../data/out_data/convergence.txt");  // :168 (silently a no-op when the directory is absent)
         for (int i = 0; i <= it; i++) file << i << "\t" << history[(size_t)i] << "\n";
     }
+    // k independent solves A x_j = rhs_j in lockstep (extension, mgcr_gcr_solve_multi: restart mode, unpreconditioned; the
+    // operator a matrix, a DiracOp or a MultiDiracOp).  X is updated in place; per column: last_history[j][i] = the value
+    // solve() would print at step i, last_iterations[j], last_converged[j] — the bits of solve() on that column alone.
+    void solve_multi(const MultiField<num_type> &rhs, MultiField<num_type> &x) {
+        if (!A_operator) { std::fprintf(stderr, "GCR has no operator (call initialise first)\n"); std::abort(); }
+        if (rhs.field_size() != this->dim) { std::fprintf(stderr, "Field dimension does not match with Operator!\n"); std::abort(); }
+        if (x.field_size() != this->dim) { std::fprintf(stderr, "x dimension does not match with Operator!\n"); std::abort(); }
+        mgcr_gcr_param p = cparam();
+        const int k = rhs.ncols(), cap = (param->max_iter > 0 ? param->max_iter : 1) + 1;
+        std::vector<double> hist((size_t)k * cap, 0.);
+        std::vector<int32_t> it((size_t)k, 0), conv((size_t)k, 0);
+        mgcr_detail::ok(mgcr_gcr_solve_multi(need_handle(A_operator), &p, rhs.device(), x.device(), hist.data(), cap, it.data(), conv.data()),
+                        "GCR::solve_multi");
+        last_history.assign((size_t)k, std::vector<double>());
+        last_iterations.assign(it.begin(), it.end());
+        last_converged.assign((size_t)k, false);
+        for (int j = 0; j < k; j++) {
+            last_history[(size_t)j].assign(hist.begin() + (size_t)j * cap, hist.begin() + (size_t)j * cap + it[(size_t)j] + 1);
+            last_converged[(size_t)j] = conv[(size_t)j] != 0;
+        }
+    }
+    std::vector<std::vector<double>> last_history;
+    std::vector<int> last_iterations;
+    std::vector<bool> last_converged;
+
     std::complex<double> val_at(num_type row, num_type col) const override { return A_operator->val_at(row, col); }
     std::complex<double> val_at(num_type location) const override { return A_operator->val_at(location); }
     Field<num_type> operator()(Field<num_type> const &f) override {  // :62-68: x = init_rand(2); solve(f, x)

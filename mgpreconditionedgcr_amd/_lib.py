@@ -72,6 +72,8 @@ _SIGS = {
     "mgcr_csr_create": (C.c_int, [C.c_int64, C.c_int64, _vp, _vp, _vp, C.POINTER(_vp)]),
     "mgcr_dirac_create": (C.c_int, [_vp, _dp, C.POINTER(_vp)]),
     "mgcr_dirac_set_k": (C.c_int, [_vp, _dp]),
+    "mgcr_dirac_multi_create": (C.c_int, [_vp, C.c_int32, _dp, C.POINTER(_vp)]),
+    "mgcr_dirac_multi_set_k": (C.c_int, [_vp, _dp]),
     "mgcr_bcsr_create_from_triplets": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.POINTER(_vp)]),
     "mgcr_bcsr_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.POINTER(_vp)]),
     "mgcr_op_destroy": (C.c_int, [_vp]),

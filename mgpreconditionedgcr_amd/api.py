@@ -398,6 +398,33 @@ class DiracOp(Operator):
         check(_lib.lib().mgcr_dirac_set_k(self.h, _ri(new_k)))
 
 
+class MultiDiracOp(Operator):
+    """Id - ks[j]*D on column j of a block of len(ks) Fields: a hopping-parameter scan as ONE operator (mgcr_dirac_multi_create;
+    no reference counterpart).  Borrows the Sparse.  Only apply_multi and GCR(...).solve_multi take it, with blocks of exactly
+    ncols columns; column j has the bits of DiracOp(mat, ks[j]) on that column alone."""
+
+    def __init__(self, mat, ks):
+        super().__init__()
+        kv = self._values(ks)
+        h = C.c_void_p()
+        check(_lib.lib().mgcr_dirac_multi_create(mat.h, kv.shape[0], kv.ctypes.data_as(C.POINTER(C.c_double)), C.byref(h)))
+        self.h = h
+        self.ncols = int(kv.shape[0])
+        self._keep.append(mat)
+
+    @staticmethod
+    def _values(ks):
+        kv = np.atleast_1d(np.asarray(ks, c128)).reshape(-1)
+        return np.ascontiguousarray(kv.view(np.float64).reshape(-1, 2))
+
+    def set_k(self, ks):
+        """Replace all ncols values; takes effect for every later apply / solve, never for work already enqueued."""
+        kv = self._values(ks)
+        if kv.shape[0] != self.ncols:
+            raise MgcrError(1, "MultiDiracOp.set_k: %d values for %d columns" % (kv.shape[0], self.ncols))
+        check(_lib.lib().mgcr_dirac_multi_set_k(self.h, kv.ctypes.data_as(C.POINTER(C.c_double))))
+
+
 class HierarchicalSparse(Operator):
     """HierarchicalSparse<long,int> (src/HierarchicalSparse.h:22-48) from unsorted
     (block_row, block_col, dense block) triplets, duplicates kept (ctor :58-98)."""
@@ -478,7 +505,10 @@ class GCR(Operator):
         self.A = M
         h = C.c_void_p()
         pc = gcr_param._c()
-        check(_lib.lib().mgcr_gcr_create(M.h if M is not None else None, C.byref(pc), x0_mode, C.byref(h)))
+        # (a MultiDiracOp serves solve_multi only, which takes the operator from self.A: the single-Field solver object is made
+        # without one, and solve / operator() answer as the C entry points do)
+        single = M is not None and not isinstance(M, MultiDiracOp)
+        check(_lib.lib().mgcr_gcr_create(M.h if single else None, C.byref(pc), x0_mode, C.byref(h)))
         self.h = h
         self._keep += [M, gcr_param, gcr_param.left_precond, gcr_param.right_precond]
         self.last_history = None
@@ -488,7 +518,16 @@ class GCR(Operator):
     def initialise(self, M):  # src/GCR.h:31
         self.A = M
         self._keep.append(M)
-        check(_lib.lib().mgcr_gcr_set_operator(self.h, M.h))
+        if not isinstance(M, MultiDiracOp):
+            check(_lib.lib().mgcr_gcr_set_operator(self.h, M.h))
+
+    def _single_field_only(self, who):
+        if isinstance(self.A, MultiDiracOp):
+            raise MgcrError(7, "%s: a MultiDiracOp has one hopping parameter per column of a block; use solve_multi" % who)
+
+    def __call__(self, f, out=None):
+        self._single_field_only("GCR as an operator")
+        return super().__call__(f, out)
 
     def set_x0(self, x0):
         check(_lib.lib().mgcr_gcr_set_x0(self.h, x0.h if x0 is not None else None))
@@ -496,6 +535,7 @@ class GCR(Operator):
     def solve(self, rhs, x):
         """void solve(const Field& rhs, Field& x) (src/GCR.h:158-302). x is updated in place;
         the residual history / iteration count are kept in last_history / last_iterations."""
+        self._single_field_only("GCR.solve")
         cap = max(self.param.max_iter, 1) + 1
         hist = np.zeros(cap, np.float64)
         it, conv = C.c_int32(), C.c_int32()

@@ -68,6 +68,45 @@ int mgcr_dirac_set_k(mgcr_op_t dirac, const double k_ri[2]) {
     return MGCR_OK;
 }
 
+static int dirac_multi_values(const double *k_ri, int32_t k, cplx *out, const char *who) {
+    for (int32_t j = 0; j < k; j++) {
+        MGCR_CHECK(k_ri[2 * j] != 0. || k_ri[2 * j + 1] != 0., MGCR_ERR_INVALID, "%s: k[%d] is zero (No k value supplied for Dirac Operator!)", who, (int)j);
+        out[j] = make_double2(k_ri[2 * j], k_ri[2 * j + 1]);
+    }
+    return MGCR_OK;
+}
+
+int mgcr_dirac_multi_create(mgcr_op_t csr, int32_t k, const double *k_ri, mgcr_op_t *out) {
+    MGCR_TRY(require_ctx());
+    MGCR_CHECK(csr && k_ri && out, MGCR_ERR_INVALID, "mgcr_dirac_multi_create: null argument");
+    MGCR_CHECK(csr->kind == OP_CSR, MGCR_ERR_INVALID, "mgcr_dirac_multi_create: MultiDiracOp wraps a Sparse (CSR) operator");
+    MGCR_CHECK(!csr->dist && !csr->comm, MGCR_ERR_UNSUPPORTED, "mgcr_dirac_multi_create: distributed operators are not supported");
+    MGCR_CHECK(csr->csr.nrow == csr->csr.ncol, MGCR_ERR_INVALID, "mgcr_dirac_multi_create: matrix must be square");
+    MGCR_CHECK(k >= 1 && k <= MV_MAX_K, MGCR_ERR_INVALID, "mgcr_dirac_multi_create: k = %d hopping parameters, 1 .. %d are supported", (int)k, MV_MAX_K);
+    cplx ks[MV_MAX_K] = {};
+    MGCR_TRY(dirac_multi_values(k_ri, k, ks, "mgcr_dirac_multi_create"));
+    LOCK();
+    mgcr_op_s *op = new mgcr_op_s();
+    op->kind = OP_DIRAC_MULTI;
+    op->dim = csr->dim;
+    op->nrow = csr->nrow;
+    op->base = csr;
+    op->nk = k;
+    std::copy(ks, ks + MV_MAX_K, op->ks);
+    *out = op;
+    return MGCR_OK;
+}
+
+// The values travel in the kernel arguments of every launch (KCols, multi_dev.h): what is already enqueued keeps the old ones.
+int mgcr_dirac_multi_set_k(mgcr_op_t op, const double *k_ri) {
+    MGCR_CHECK(op && k_ri && op->kind == OP_DIRAC_MULTI, MGCR_ERR_INVALID, "mgcr_dirac_multi_set_k: not a MultiDiracOp");
+    cplx ks[MV_MAX_K] = {};
+    MGCR_TRY(dirac_multi_values(k_ri, op->nk, ks, "mgcr_dirac_multi_set_k"));
+    LOCK();
+    std::copy(ks, ks + MV_MAX_K, op->ks);
+    return MGCR_OK;
+}
+
 int mgcr_bcsr_create(int32_t nbrow, int32_t nbcol, int32_t bs, const int32_t *browptr, const int32_t *bcol,
                      const double *blocks_ri, mgcr_op_t *out) {
     MGCR_TRY(require_ctx());
@@ -121,7 +160,7 @@ int mgcr_op_destroy(mgcr_op_t op) {
         case OP_BCSR: bcsr_free(&op->bcsr); dist_free(op->dist); break;
         case OP_GCR: gcr_state_destroy(op->gcr); break;
         case OP_MG: mg_destroy(op->mg); break;
-        default: break;  // OP_DIRAC borrows its Sparse (src/Operator.h:117,555-560)
+        default: break;  // OP_DIRAC and OP_DIRAC_MULTI borrow their Sparse (src/Operator.h:117,555-560)
     }
     delete op;
     return MGCR_OK;
@@ -133,7 +172,8 @@ int64_t mgcr_op_nnz(mgcr_op_t op) {
     if (!op) return -1;
     switch (op->kind) {
         case OP_CSR: return op->csr.nnz;
-        case OP_DIRAC: return op->base->csr.nnz;
+        case OP_DIRAC:
+        case OP_DIRAC_MULTI: return op->base->csr.nnz;
         case OP_BCSR: return (int64_t)op->bcsr.nblocks * op->bcsr.bs * op->bcsr.bs;  // src/HierarchicalSparse.h:31
         default: return -1;
     }
@@ -141,7 +181,7 @@ int64_t mgcr_op_nnz(mgcr_op_t op) {
 
 int mgcr_op_storage_format(mgcr_op_t op, int32_t *format, int32_t *n_patterns) {
     MGCR_CHECK(op, MGCR_ERR_INVALID, "null operator");
-    const Op *o = op->kind == OP_DIRAC ? op->base : op;
+    const Op *o = op_matrix(op);
     MGCR_CHECK(o->kind == OP_CSR, MGCR_ERR_UNSUPPORTED, "mgcr_op_storage_format: not a Sparse");
     if (format) *format = csr_stencil_active(o->csr) ? 3 : o->csr.pat_mode;
     if (n_patterns) *n_patterns = csr_stencil_active(o->csr) ? o->csr.sten_ns : o->csr.npat;
@@ -151,7 +191,7 @@ int mgcr_op_storage_format(mgcr_op_t op, int32_t *format, int32_t *n_patterns) {
 int mgcr_op_ell_layout(mgcr_op_t op, int32_t *ell_width, int32_t *lanes, int64_t *tail_rows, int64_t *reach, int32_t *tail_chunk_cap,
                        int32_t *x_window) {
     MGCR_CHECK(op, MGCR_ERR_INVALID, "null operator");
-    const Op *o = op->kind == OP_DIRAC ? op->base : op;
+    const Op *o = op_matrix(op);
     MGCR_CHECK(o->kind == OP_CSR, MGCR_ERR_UNSUPPORTED, "mgcr_op_ell_layout: not a Sparse");
     if (ell_width) *ell_width = o->csr.W;
     if (lanes) *lanes = o->csr.L;
@@ -164,7 +204,7 @@ int mgcr_op_ell_layout(mgcr_op_t op, int32_t *ell_width, int32_t *lanes, int64_t
 
 int mgcr_op_xr_fuse_kind(mgcr_op_t op, int32_t *kind) {
     MGCR_CHECK(op && kind, MGCR_ERR_INVALID, "mgcr_op_xr_fuse_kind: null argument");
-    const Op *o = op->kind == OP_DIRAC ? op->base : op;
+    const Op *o = op_matrix(op);
     MGCR_CHECK(o->kind == OP_CSR, MGCR_ERR_UNSUPPORTED, "mgcr_op_xr_fuse_kind: not a Sparse");
     *kind = csr_fusable(o->csr, o->dist) ? csr_xr_fuse_kind(o->csr, o->dist) : 0;
     return MGCR_OK;
@@ -172,7 +212,7 @@ int mgcr_op_xr_fuse_kind(mgcr_op_t op, int32_t *kind) {
 
 int mgcr_op_halo_kind(mgcr_op_t op, int32_t *kind) {
     MGCR_CHECK(op && kind, MGCR_ERR_INVALID, "mgcr_op_halo_kind: null argument");
-    const Op *o = op->kind == OP_DIRAC ? op->base : op;
+    const Op *o = op_matrix(op);
     MGCR_CHECK(o->dist, MGCR_ERR_UNSUPPORTED, "mgcr_op_halo_kind: not a distributed Sparse");
     *kind = dist_halo_kind(o->dist);
     return MGCR_OK;
@@ -229,7 +269,7 @@ int mgcr_selftest_coherence(int32_t steps, int32_t coherent, int64_t *rows_wrong
 
 int mgcr_op_stored_bytes(mgcr_op_t op, int64_t *matrix_bytes, int32_t *ell_width, int64_t *tail_nnz) {
     MGCR_CHECK(op, MGCR_ERR_INVALID, "null operator");
-    const Op *o = op->kind == OP_DIRAC ? op->base : op;
+    const Op *o = op_matrix(op);
     if (o->kind == OP_CSR) {
         const CsrDev &A = o->csr;
         int64_t slab = (int64_t)A.nchunk * A.npad * A.L;
@@ -256,6 +296,7 @@ int mgcr_op_stored_bytes(mgcr_op_t op, int64_t *matrix_bytes, int32_t *ell_width
 int mgcr_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y) {
     MGCR_TRY(require_ctx());
     MGCR_CHECK(op && x && y, MGCR_ERR_INVALID, "mgcr_op_apply: null argument");
+    MGCR_REFUSE_MULTI_DIRAC(op, "mgcr_op_apply");
     MGCR_CHECK(x->n == op->dim, MGCR_ERR_INVALID, "Sparse matrix dimension does not match Field dimension!");
     int64_t nrow = op->nrow ? op->nrow : op->dim;
     MGCR_CHECK(y->n == nrow, MGCR_ERR_INVALID, "output Field has %lld entries, operator has %lld rows", (long long)y->n, (long long)nrow);
@@ -270,6 +311,7 @@ int mgcr_gcr_solve(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_vec_t rhs, mgc
                    int32_t *n_iter, int32_t *converged) {
     MGCR_TRY(require_ctx());
     MGCR_CHECK(A && param && rhs && x, MGCR_ERR_INVALID, "mgcr_gcr_solve: null argument");
+    MGCR_REFUSE_MULTI_DIRAC(A, "mgcr_gcr_solve");
     // assertm(rhs.field_size() == this->dim, ...) src/GCR.h:160-161
     MGCR_CHECK(rhs->n == A->dim, MGCR_ERR_INVALID, "Field dimension does not match with Operator!");
     MGCR_CHECK(x->n == A->dim, MGCR_ERR_INVALID, "x dimension does not match with Operator!");
@@ -289,6 +331,7 @@ int mgcr_gcr_solve(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_vec_t rhs, mgc
 int mgcr_gcr_create(mgcr_op_t A, const mgcr_gcr_param *param, int32_t x0_mode, mgcr_op_t *out) {
     MGCR_TRY(require_ctx());
     MGCR_CHECK(param && out, MGCR_ERR_INVALID, "mgcr_gcr_create: null argument");
+    MGCR_REFUSE_MULTI_DIRAC(A, "mgcr_gcr_create");
     LOCK();
     mgcr_op_s *op = new mgcr_op_s();
     op->kind = OP_GCR;
@@ -302,6 +345,7 @@ int mgcr_gcr_create(mgcr_op_t A, const mgcr_gcr_param *param, int32_t x0_mode, m
 
 int mgcr_gcr_set_operator(mgcr_op_t gcr, mgcr_op_t A) {
     MGCR_CHECK(gcr && A && gcr->kind == OP_GCR, MGCR_ERR_INVALID, "mgcr_gcr_set_operator: not a GCR operator");
+    MGCR_REFUSE_MULTI_DIRAC(A, "mgcr_gcr_set_operator");
     LOCK();
     gcr->dim = A->dim;  // GCR::initialise src/GCR.h:31
     gcr->nrow = A->dim;
@@ -355,6 +399,7 @@ int mgcr_gcr_last_profile(double *phase_ms_total, int32_t *n_iter, int32_t *fuse
 int mgcr_bench_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y, int32_t reps, double *ms_avg) {
     MGCR_TRY(require_ctx());
     MGCR_CHECK(op && x && y && reps > 0 && ms_avg, MGCR_ERR_INVALID, "mgcr_bench_op_apply: bad argument");
+    MGCR_REFUSE_MULTI_DIRAC(op, "mgcr_bench_op_apply");
     LOCK();
     Context &c = ctx();
     MGCR_TRY(mgcr_op_apply(op, x, y));  // warm-up (and argument checks)
@@ -372,12 +417,14 @@ int mgcr_bench_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y, int32_t reps, 
 static int apply_multi_checks(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y, const char *who) {
     MGCR_CHECK(op && x && y, MGCR_ERR_INVALID, "%s: null argument", who);
     MGCR_CHECK(op->kind != OP_GCR && op->kind != OP_MG, MGCR_ERR_UNSUPPORTED, "%s: GCR and MG objects cannot be applied to a block of Fields", who);
-    const Op *b0 = op->kind == OP_DIRAC ? op->base : op;
+    const Op *b0 = op_matrix(op);
     MGCR_CHECK(!op->dist && !op->comm && !b0->dist && !b0->comm, MGCR_ERR_UNSUPPORTED, "%s: distributed operators are not supported", who);
     MGCR_CHECK(x->n == op->dim, MGCR_ERR_INVALID, "Sparse matrix dimension does not match Field dimension!");
     const int64_t nrow = op->nrow ? op->nrow : op->dim;
     MGCR_CHECK(y->n == nrow, MGCR_ERR_INVALID, "output block has %lld rows, operator has %lld", (long long)y->n, (long long)nrow);
     MGCR_CHECK(x->k == y->k, MGCR_ERR_INVALID, "%s: input has %d columns, output has %d", who, (int)x->k, (int)y->k);
+    MGCR_CHECK(op->kind != OP_DIRAC_MULTI || x->k == op->nk, MGCR_ERR_INVALID, "%s: the MultiDiracOp carries %d hopping parameters, the block has %d columns",
+               who, op->nk, (int)x->k);
     MGCR_CHECK(x != y && (x->d != y->d || !x->d), MGCR_ERR_INVALID, "%s: input and output must be different blocks", who);
     return MGCR_OK;
 }
@@ -417,7 +464,7 @@ int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t r
     MGCR_CHECK(!param->flexible && !param->profile_spmv, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: flexible / profile_spmv are not supported");
     MGCR_CHECK(A->kind != OP_GCR && A->kind != OP_MG, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: the operator must be a matrix");
     {
-        const Op *b0 = A->kind == OP_DIRAC ? A->base : A;
+        const Op *b0 = op_matrix(A);
         MGCR_CHECK(!A->dist && !A->comm && !b0->dist && !b0->comm, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: distributed operators are not supported");
     }
     MGCR_CHECK(rhs->n == A->dim, MGCR_ERR_INVALID, "Field dimension does not match with Operator!");
@@ -425,6 +472,8 @@ int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t r
     MGCR_CHECK((A->nrow ? A->nrow : A->dim) == A->dim, MGCR_ERR_INVALID, "mgcr_gcr_solve_multi: the operator must be square");
     MGCR_CHECK(rhs->k == x->k, MGCR_ERR_INVALID, "mgcr_gcr_solve_multi: rhs has %d columns, x has %d", (int)rhs->k, (int)x->k);
     MGCR_CHECK(rhs != x && (rhs->d != x->d || !x->d), MGCR_ERR_INVALID, "rhs and x must be different blocks");
+    MGCR_CHECK(A->kind != OP_DIRAC_MULTI || x->k == A->nk, MGCR_ERR_INVALID,
+               "mgcr_gcr_solve_multi: the MultiDiracOp carries %d hopping parameters, the blocks have %d columns", A->nk, (int)x->k);
     LOCK();
     return gcr_multi_run(A, *param, rhs->d, x->d, x->n, x->k, hist, hist_cap, n_iter, converged);
 }

@@ -707,6 +707,9 @@ int op_apply_raw(Op *op, const cplx *x, cplx *y, int64_t n) {
             return gcr_apply_as_operator(op->gcr, x, y);
         case OP_MG:
             return mg_apply(op->mg, x, y);
+        case OP_DIRAC_MULTI:   // (reached through a preconditioner slot; the entry points refuse it themselves)
+            set_error("a MultiDiracOp has one hopping parameter per column of a block and cannot be applied to a single Field");
+            return MGCR_ERR_UNSUPPORTED;
         default:
             set_error("operator kind %d cannot be applied", (int)op->kind);
             return MGCR_ERR_UNSUPPORTED;

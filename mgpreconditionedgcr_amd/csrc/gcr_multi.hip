@@ -479,13 +479,14 @@ int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int6
     for (int j = 0; j < LND; j++) { d.ps[j] = ps[(size_t)(j < storage ? j : 0)]; d.aps[j] = aps[(size_t)(j < storage ? j : 0)]; }
     int64_t reach = 0;
     {
-        const Op *b0 = A->kind == OP_DIRAC ? A->base : A;
+        const Op *b0 = op_matrix(A);   // (a MultiDiracOp deals its rows as the DiracOps of its columns do)
         if (b0 && b0->kind == OP_CSR) reach = b0->csr.reach;
     }
     const RowMap rmap = make_row_map(n, g, reach);
 
     MK(m_reset_kernel, dim3(1), MV_MAX_K, st, p.tol * p.tol, k);
-    // r0 = b, or b - A x0 formed as the single solve forms it (op_residual_raw)
+    // r0 = b, or b - A x0 formed as the single solve forms it (op_residual_raw: one pass for a plain Sparse, apply then b - r for
+    // a DiracOp and for a MultiDiracOp)
     if (p.use_x0) {
         if (A->kind == OP_CSR && A->csr.nrow == n && A->csr.ncol == n) {
             MGCR_TRY(op_apply_multi_raw(A, x, r, n, k, rhs));

@@ -83,7 +83,7 @@ struct MVec {
 };
 constexpr int MV_MAX_K = 16;
 
-enum OpKind { OP_CSR = 1, OP_DIRAC = 2, OP_BCSR = 3, OP_GCR = 4, OP_MG = 5 };
+enum OpKind { OP_CSR = 1, OP_DIRAC = 2, OP_BCSR = 3, OP_GCR = 4, OP_MG = 5, OP_DIRAC_MULTI = 6 };
 
 // ELL slab + CSR tail (int32 indices).
 //   ELL: W = nchunk*L entries per row, L lanes co-operate on a row.
@@ -164,14 +164,23 @@ struct Op {
     OpKind kind;
     int64_t dim = 0, nrow = 0;
     CsrDev csr;          // OP_CSR
-    Op *base = nullptr;  // OP_DIRAC: borrowed CSR
+    Op *base = nullptr;  // OP_DIRAC / OP_DIRAC_MULTI: borrowed CSR
     cplx k = {0., 0.};   // OP_DIRAC
+    int nk = 0;          // OP_DIRAC_MULTI: 1 - ks[j] D on column j of a block of exactly nk columns (block entry points only)
+    cplx ks[MV_MAX_K] = {};
     BcsrDev bcsr;        // OP_BCSR
     GcrState *gcr = nullptr;  // OP_GCR
     MgState *mg = nullptr;    // OP_MG
     DistCsr *dist = nullptr;  // OP_CSR / OP_BCSR row block of a distributed matrix (halo.hip; owned)
     Comm *comm = nullptr;     // communicator the operator's Fields are distributed over (borrowed)
 };
+
+// the Sparse an operator reads: its own, or the one a DiracOp / MultiDiracOp borrows
+inline const Op *op_matrix(const Op *op) { return op && (op->kind == OP_DIRAC || op->kind == OP_DIRAC_MULTI) ? op->base : op; }
+// the single-Field entry points' answer to a MultiDiracOp
+#define MGCR_REFUSE_MULTI_DIRAC(op, who)                                                                                              \
+    MGCR_CHECK(!(op) || (op)->kind != OP_DIRAC_MULTI, MGCR_ERR_UNSUPPORTED,                                                           \
+               "%s: a MultiDiracOp has one hopping parameter per column of a block; only mgcr_op_apply_multi and mgcr_gcr_solve_multi take it", who)
 
 // ---- blas1.hip -------------------------------------------------------------------------------
 int red_grid(int64_t n);

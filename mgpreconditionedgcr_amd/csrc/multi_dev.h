@@ -15,6 +15,18 @@ namespace mgcr {
 #define MV_GRID_STRIDE(i, n) \
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (int64_t)gridDim.x * blockDim.x)
 
+// The shift of the k-wide apply (spmm.hip): one k for all columns, or one k per column.  KCols is passed BY VALUE in the kernel
+// arguments: a launch keeps the values it was enqueued with whatever mgcr_dirac_multi_set_k does afterwards, and a thread reads
+// them as scalars.
+struct KUniform {
+    cplx k;
+    __device__ __forceinline__ cplx at(int) const { return k; }
+};
+struct KCols {
+    cplx v[MV_MAX_K];
+    __device__ __forceinline__ cplx at(int q) const { return v[q]; }
+};
+
 // columns per thread of the streaming kernels
 inline int mv_group(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : 4; }
 

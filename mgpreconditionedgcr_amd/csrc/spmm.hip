@@ -7,6 +7,13 @@
 // (chunk rows), 64 lanes striding + wave tree (rows longer than a chunk); block-CSR: a block's products of a row in column
 // order, blocks in storage order; dictionary / stencil view: row_product / sten_row_product of spmv_dev.h called per column.
 // No fused multiply-adds (-ffp-contract=off), no MFMA.
+//
+// The shift y = w - k (A x) comes in two forms (multi_dev.h): KUniform, one k for every column (Sparse residual form, DiracOp), and
+// KCols, one k PER COLUMN (MultiDiracOp: 16 values in the kernel arguments, so a launch carries the values of the moment it was
+// enqueued).  Every Sparse kernel below is a body templated on that type and two __global__ entries: NAME<...> with the uniform k —
+// the kernels as they were, name and arguments — and NAME_kcol<...> with the per-column values (256 bytes more of kernel
+// arguments, which the small operators' launch-bound applies would pay for: measured).  The expression per
+// column is the single kernels' csub(w, cmul(k_j, sum)) either way.
 #include "internal.h"
 #include "reduce.h"
 #include "spmv_dev.h"
@@ -19,10 +26,10 @@ namespace mgcr {
 // (non-temporally: the slab is touched once per apply), the k values of X's row `col` are one contiguous 16 k-byte piece, and
 // the thread keeps K >= k accumulators.  MASK: k < K, the columns beyond k are neither loaded nor stored.
 // ------------------------------------------------------------------------------------------------
-template <int K, bool MASK, bool REALV>
-__global__ void __launch_bounds__(256) ell_multi_kernel(int64_t nrow, int64_t npad, int32_t nchunk, int lshift, const void *__restrict__ val,
-                                                        const int32_t *__restrict__ col, const cplx *__restrict__ x, cplx *__restrict__ y,
-                                                        int k, int shift, cplx kk, const cplx *__restrict__ w) {
+template <int K, bool MASK, bool REALV, typename KS>
+__device__ __forceinline__ void ell_multi_body(int64_t nrow, int64_t npad, int32_t nchunk, int lshift, const void *__restrict__ val,
+                                               const int32_t *__restrict__ col, const cplx *__restrict__ x, cplx *__restrict__ y,
+                                               int k, int shift, const KS ks, const cplx *__restrict__ w) {
     const int L = 1 << lshift;
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t row = t >> lshift;
@@ -62,8 +69,20 @@ __global__ void __launch_bounds__(256) ell_multi_kernel(int64_t nrow, int64_t np
         const cplx *wr = (w ? w : x) + row * k;
 #pragma unroll
         for (int q = 0; q < K; q++)
-            if (!MASK || q < k) y[row * k + q] = shift ? csub(wr[q], cmul(kk, sum[q])) : sum[q];
+            if (!MASK || q < k) y[row * k + q] = shift ? csub(wr[q], cmul(ks.at(q), sum[q])) : sum[q];
     }
+}
+template <int K, bool MASK, bool REALV>
+__global__ void __launch_bounds__(256) ell_multi_kernel(int64_t nrow, int64_t npad, int32_t nchunk, int lshift, const void *__restrict__ val,
+                                                        const int32_t *__restrict__ col, const cplx *__restrict__ x, cplx *__restrict__ y,
+                                                        int k, int shift, cplx kk, const cplx *__restrict__ w) {
+    ell_multi_body<K, MASK, REALV>(nrow, npad, nchunk, lshift, val, col, x, y, k, shift, KUniform{kk}, w);
+}
+template <int K, bool MASK, bool REALV>
+__global__ void __launch_bounds__(256) ell_multi_kernel_kcol(int64_t nrow, int64_t npad, int32_t nchunk, int lshift, const void *__restrict__ val,
+                                                             const int32_t *__restrict__ col, const cplx *__restrict__ x, cplx *__restrict__ y,
+                                                             int k, int shift, KCols ks, const cplx *__restrict__ w) {
+    ell_multi_body<K, MASK, REALV>(nrow, npad, nchunk, lshift, val, col, x, y, k, shift, ks, w);
 }
 
 // CSR tail, the rows of a chunk: the k-wide form of csr_tail_chunk_kernel.  One workgroup per chunk (a run of consecutive tail
@@ -72,12 +91,13 @@ __global__ void __launch_bounds__(256) ell_multi_kernel(int64_t nrow, int64_t np
 // are requested before this trip's products are formed), every thread gathers the k contiguous values of X's row `col` and
 // stages its k products in LDS, prod[K][TAIL_THREADS]; thread t then adds the trip's products of ITS row, per column, in CSR
 // order onto the row's tail sum, which is added to the row's ELL sum at the end — csr_tail_chunk_kernel's order, same bits.
-template <int K>
-__global__ void __launch_bounds__(TAIL_THREADS) tail_chunk_multi_kernel(const int4 *__restrict__ chunks, const int32_t *__restrict__ tail_rows,
-                                                                        const int32_t *__restrict__ tail_ptr, const int32_t *__restrict__ tail_col,
-                                                                        const cplx *__restrict__ tail_val, const cplx *__restrict__ x,
-                                                                        cplx *__restrict__ y, int k, int shift, cplx kk, int c0, int kw) {
-    // (columns [c0, c0 + kw) of the k, kw <= K: 12 columns run as 8 + 4 — the 16-wide form's 64 KB of products and 210 registers
+template <int K, typename KS>
+__device__ __forceinline__ void tail_chunk_multi_body(const int4 *__restrict__ chunks, const int32_t *__restrict__ tail_rows,
+                                                      const int32_t *__restrict__ tail_ptr, const int32_t *__restrict__ tail_col,
+                                                      const cplx *__restrict__ tail_val, const cplx *__restrict__ x,
+                                                      cplx *__restrict__ y, int k, int shift, const KS ks, int c0, int kw) {
+    // (columns [c0, c0 + kw) of the k, kw <= K; ks.at(q) is the shift of column c0 + q — the host passes the window's values, so
+    // that every index into the kernel arguments is a constant: 12 columns run as 8 + 4 — the 16-wide form's 64 KB of products and 210 registers
     // leave 2 waves per SIMD and measured slower than streaming the tail twice)
     __shared__ cplx prod[K * TAIL_THREADS];
     const int t = threadIdx.x;
@@ -129,17 +149,31 @@ __global__ void __launch_bounds__(TAIL_THREADS) tail_chunk_multi_kernel(const in
         for (int q = 0; q < K; q++)
             if (q < kw) {
                 const cplx y0 = y[row * k + c0 + q];
-                y[row * k + c0 + q] = shift ? csub(y0, cmul(kk, sum[q])) : cadd(y0, sum[q]);
+                y[row * k + c0 + q] = shift ? csub(y0, cmul(ks.at(q), sum[q])) : cadd(y0, sum[q]);
             }
     }
 }
+template <int K>
+__global__ void __launch_bounds__(TAIL_THREADS) tail_chunk_multi_kernel(const int4 *__restrict__ chunks, const int32_t *__restrict__ tail_rows,
+                                                                        const int32_t *__restrict__ tail_ptr, const int32_t *__restrict__ tail_col,
+                                                                        const cplx *__restrict__ tail_val, const cplx *__restrict__ x,
+                                                                        cplx *__restrict__ y, int k, int shift, cplx kk, int c0, int kw) {
+    tail_chunk_multi_body<K>(chunks, tail_rows, tail_ptr, tail_col, tail_val, x, y, k, shift, KUniform{kk}, c0, kw);
+}
+template <int K>
+__global__ void __launch_bounds__(TAIL_THREADS) tail_chunk_multi_kernel_kcol(const int4 *__restrict__ chunks, const int32_t *__restrict__ tail_rows,
+                                                                             const int32_t *__restrict__ tail_ptr, const int32_t *__restrict__ tail_col,
+                                                                             const cplx *__restrict__ tail_val, const cplx *__restrict__ x,
+                                                                             cplx *__restrict__ y, int k, int shift, KCols ks, int c0, int kw) {
+    tail_chunk_multi_body<K>(chunks, tail_rows, tail_ptr, tail_col, tail_val, x, y, k, shift, ks, c0, kw);
+}
 
 // CSR tail, rows longer than a chunk (csr_tail_kernel's): one wave per row, lanes stride the entries, wave tree per column
-template <int K>
-__global__ void __launch_bounds__(256) tail_long_multi_kernel(int64_t n_long, const int32_t *__restrict__ tail_long, const int32_t *__restrict__ tail_rows,
-                                                              const int32_t *__restrict__ tail_ptr, const int32_t *__restrict__ tail_col,
-                                                              const cplx *__restrict__ tail_val, const cplx *__restrict__ x, cplx *__restrict__ y,
-                                                              int k, int shift, cplx kk) {
+template <int K, typename KS>
+__device__ __forceinline__ void tail_long_multi_body(int64_t n_long, const int32_t *__restrict__ tail_long, const int32_t *__restrict__ tail_rows,
+                                                     const int32_t *__restrict__ tail_ptr, const int32_t *__restrict__ tail_col,
+                                                     const cplx *__restrict__ tail_val, const cplx *__restrict__ x, cplx *__restrict__ y,
+                                                     int k, int shift, const KS ks) {
     const int64_t wave = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (wave >= n_long) return;
@@ -166,17 +200,31 @@ __global__ void __launch_bounds__(256) tail_long_multi_kernel(int64_t n_long, co
         for (int q = 0; q < K; q++)
             if (q < k) {
                 const cplx y0 = y[row * k + q];
-                y[row * k + q] = shift ? csub(y0, cmul(kk, sum[q])) : cadd(y0, sum[q]);
+                y[row * k + q] = shift ? csub(y0, cmul(ks.at(q), sum[q])) : cadd(y0, sum[q]);
             }
     }
+}
+template <int K>
+__global__ void __launch_bounds__(256) tail_long_multi_kernel(int64_t n_long, const int32_t *__restrict__ tail_long, const int32_t *__restrict__ tail_rows,
+                                                              const int32_t *__restrict__ tail_ptr, const int32_t *__restrict__ tail_col,
+                                                              const cplx *__restrict__ tail_val, const cplx *__restrict__ x, cplx *__restrict__ y,
+                                                              int k, int shift, cplx kk) {
+    tail_long_multi_body<K>(n_long, tail_long, tail_rows, tail_ptr, tail_col, tail_val, x, y, k, shift, KUniform{kk});
+}
+template <int K>
+__global__ void __launch_bounds__(256) tail_long_multi_kernel_kcol(int64_t n_long, const int32_t *__restrict__ tail_long, const int32_t *__restrict__ tail_rows,
+                                                                   const int32_t *__restrict__ tail_ptr, const int32_t *__restrict__ tail_col,
+                                                                   const cplx *__restrict__ tail_val, const cplx *__restrict__ x, cplx *__restrict__ y,
+                                                                   int k, int shift, KCols ks) {
+    tail_long_multi_body<K>(n_long, tail_long, tail_rows, tail_ptr, tail_col, tail_val, x, y, k, shift, ks);
 }
 
 // Row-pattern dictionary (MODE 1: offsets and values in the table, 2: offsets only) and stencil view (MODE 3; RARE: the
 // rare-tail layout): ONE generic row-thread kernel, the single kernels' row product (spmv_dev.h) called once per column
 // through its x hook.  Correct and bit-exact; not tuned (the table / presence words are re-read per column, from cache).
-template <int MODE, int NS, bool RARE>
-__global__ void __launch_bounds__(256) rowgen_multi_kernel(RowMat m, int64_t nrow, const cplx *__restrict__ x, cplx *__restrict__ y, int k,
-                                                           const cplx *__restrict__ w) {
+template <int MODE, int NS, bool RARE, typename KS>
+__device__ __forceinline__ void rowgen_multi_body(const RowMat &m, int64_t nrow, const cplx *__restrict__ x, cplx *__restrict__ y, int k,
+                                                  const KS ks, const cplx *__restrict__ w) {
     const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if ((row & ~(int64_t)63) >= nrow) return;   // the whole wave lies outside
     const bool live = row < nrow;
@@ -189,20 +237,36 @@ __global__ void __launch_bounds__(256) rowgen_multi_kernel(RowMat m, int64_t nro
         cplx sum;
         if constexpr (MODE == 3) sum = sten_row_product<NS, RARE>(m, row, xf);   // (a wave holds 64 consecutive rows from a multiple of 64)
         else sum = row_product<MODE, 0>(m, r, t0, pl, xf);
-        if (live) y[row * k + q] = m.shift ? csub((w ? w : x)[row * k + q], cmul(m.k, sum)) : sum;
+        if (live) y[row * k + q] = m.shift ? csub((w ? w : x)[row * k + q], cmul(ks.at(q), sum)) : sum;
     }
+}
+template <int MODE, int NS, bool RARE>
+__global__ void __launch_bounds__(256) rowgen_multi_kernel(RowMat m, int64_t nrow, const cplx *__restrict__ x, cplx *__restrict__ y, int k,
+                                                           const cplx *__restrict__ w) {
+    rowgen_multi_body<MODE, NS, RARE>(m, nrow, x, y, k, KUniform{m.k}, w);
+}
+template <int MODE, int NS, bool RARE>
+__global__ void __launch_bounds__(256) rowgen_multi_kernel_kcol(RowMat m, int64_t nrow, const cplx *__restrict__ x, cplx *__restrict__ y, int k,
+                                                                KCols ks, const cplx *__restrict__ w) {
+    rowgen_multi_body<MODE, NS, RARE>(m, nrow, x, y, k, ks, w);
 }
 
 template <bool REALV>
-static int launch_ell_multi(const CsrDev &A, const cplx *x, cplx *y, int k, int shift, cplx kk, const cplx *w) {
+static int launch_ell_multi(const CsrDev &A, const cplx *x, cplx *y, int k, int shift, cplx kk, const KCols *kc, const cplx *w) {
     int lshift = 0;
     while ((1 << lshift) < A.L) lshift++;
     const int64_t threads = A.nrow << lshift;
     const unsigned grid = (unsigned)((threads + 255) / 256);
     const void *vals = A.ell_val_re ? (const void *)A.ell_val_re : (const void *)A.ell_val;
 #define EM(KK, MM)                                                                                                                  \
-    hipLaunchKernelGGL((ell_multi_kernel<KK, MM, REALV>), dim3(grid), dim3(256), 0, ctx().stream, A.nrow, A.npad, A.nchunk, lshift, vals, \
-                       (const int32_t *)A.ell_col, x, y, k, shift, kk, w)
+    do {                                                                                                                            \
+        if (kc)                                                                                                                     \
+            hipLaunchKernelGGL((ell_multi_kernel_kcol<KK, MM, REALV>), dim3(grid), dim3(256), 0, ctx().stream, A.nrow, A.npad, A.nchunk, lshift, \
+                               vals, (const int32_t *)A.ell_col, x, y, k, shift, *kc, w);                                           \
+        else                                                                                                                        \
+            hipLaunchKernelGGL((ell_multi_kernel<KK, MM, REALV>), dim3(grid), dim3(256), 0, ctx().stream, A.nrow, A.npad, A.nchunk, lshift, \
+                               vals, (const int32_t *)A.ell_col, x, y, k, shift, kk, w);                                            \
+    } while (0)
     switch (k) {
         case 1: EM(1, false); break;
         case 2: EM(2, false); break;
@@ -215,19 +279,32 @@ static int launch_ell_multi(const CsrDev &A, const cplx *x, cplx *y, int k, int 
             if (k < 8) EM(8, true);
             else if (k < 12) EM(12, true);
             else EM(16, true);
+            break;
     }
 #undef EM
     MGCR_HIP(hipGetLastError());
     return MGCR_OK;
 }
 
-static int csr_apply_multi(const CsrDev &A, const cplx *x, cplx *y, int k, bool shift, cplx kk, const cplx *w) {
+// entry q = the shift of column c0 + q (entries past column 15 repeat the last one; no kernel reads them)
+static KCols kcols_window(const KCols &ks, int c0) {
+    KCols w;
+    for (int q = 0; q < MV_MAX_K; q++) w.v[q] = ks.v[c0 + q < MV_MAX_K ? c0 + q : MV_MAX_K - 1];
+    return w;
+}
+
+// kc == nullptr: the uniform shift kk; else the shift per column (kk unused)
+static int csr_apply_multi(const CsrDev &A, const cplx *x, cplx *y, int k, bool shift, cplx kk, const KCols *kc, const cplx *w) {
     Context &c = ctx();
     if (A.nrow == 0) return MGCR_OK;
     const unsigned rgrid = (unsigned)((A.nrow + 255) / 256);
     if (csr_stencil_active(A) || A.pat_mode) {
-        const RowMat m = row_mat(A, shift, kk);
-#define RG(MODE, NS, RARE) hipLaunchKernelGGL((rowgen_multi_kernel<MODE, NS, RARE>), dim3(rgrid), dim3(256), 0, c.stream, m, A.nrow, x, y, k, w)
+        const RowMat m = row_mat(A, shift, kk);   // (the per-column kernel takes its shifts from *kc, not from m.k)
+#define RG(MODE, NS, RARE)                                                                                                                   \
+    do {                                                                                                                                     \
+        if (kc) hipLaunchKernelGGL((rowgen_multi_kernel_kcol<MODE, NS, RARE>), dim3(rgrid), dim3(256), 0, c.stream, m, A.nrow, x, y, k, *kc, w); \
+        else hipLaunchKernelGGL((rowgen_multi_kernel<MODE, NS, RARE>), dim3(rgrid), dim3(256), 0, c.stream, m, A.nrow, x, y, k, w);           \
+    } while (0)
         if (csr_stencil_active(A)) {
             if (A.sten_rare) RG(3, 9, true);
             else if (sten_slots(A) == 7) RG(3, 7, false);
@@ -237,15 +314,22 @@ static int csr_apply_multi(const CsrDev &A, const cplx *x, cplx *y, int k, bool 
 #undef RG
         MGCR_HIP(hipGetLastError());
     } else if (A.ell_val_re) {
-        MGCR_TRY(launch_ell_multi<true>(A, x, y, k, shift ? 1 : 0, kk, w));
+        MGCR_TRY(launch_ell_multi<true>(A, x, y, k, shift ? 1 : 0, kk, kc, w));
     } else {
-        MGCR_TRY(launch_ell_multi<false>(A, x, y, k, shift ? 1 : 0, kk, w));
+        MGCR_TRY(launch_ell_multi<false>(A, x, y, k, shift ? 1 : 0, kk, kc, w));
     }
     if (A.n_tail_rows) {
 #define TCH(KK, C0, KW)                                                                                                                 \
-    hipLaunchKernelGGL((tail_chunk_multi_kernel<KK>), dim3((unsigned)A.n_tail_chunks), dim3(TAIL_THREADS), 0, c.stream,                 \
-                       (const int4 *)A.tail_chunk, (const int32_t *)A.tail_rows, (const int32_t *)A.tail_ptr,                           \
-                       (const int32_t *)A.tail_col, (const cplx *)A.tail_val, x, y, k, shift ? 1 : 0, kk, C0, KW)
+    do {                                                                                                                                \
+        if (kc)                                                                                                                         \
+            hipLaunchKernelGGL((tail_chunk_multi_kernel_kcol<KK>), dim3((unsigned)A.n_tail_chunks), dim3(TAIL_THREADS), 0, c.stream,    \
+                               (const int4 *)A.tail_chunk, (const int32_t *)A.tail_rows, (const int32_t *)A.tail_ptr,                   \
+                               (const int32_t *)A.tail_col, (const cplx *)A.tail_val, x, y, k, shift ? 1 : 0, kcols_window(*kc, C0), C0, KW); \
+        else                                                                                                                            \
+            hipLaunchKernelGGL((tail_chunk_multi_kernel<KK>), dim3((unsigned)A.n_tail_chunks), dim3(TAIL_THREADS), 0, c.stream,         \
+                               (const int4 *)A.tail_chunk, (const int32_t *)A.tail_rows, (const int32_t *)A.tail_ptr,                   \
+                               (const int32_t *)A.tail_col, (const cplx *)A.tail_val, x, y, k, shift ? 1 : 0, kk, C0, KW);              \
+    } while (0)
         if (A.n_tail_chunks) {
             if (k <= 2) TCH(2, 0, k);
             else if (k <= 4) TCH(4, 0, k);
@@ -260,7 +344,11 @@ static int csr_apply_multi(const CsrDev &A, const cplx *x, cplx *y, int k, bool 
 #undef TCH
 #define TK(KK)                                                                                                                              \
     do {                                                                                                                                    \
-        if (A.n_tail_long)                                                                                                                  \
+        if (A.n_tail_long && kc)                                                                                                            \
+            hipLaunchKernelGGL((tail_long_multi_kernel_kcol<KK>), dim3((unsigned)(((int64_t)A.n_tail_long * 64 + 255) / 256)), dim3(256), 0, \
+                               c.stream, (int64_t)A.n_tail_long, (const int32_t *)A.tail_long, (const int32_t *)A.tail_rows,                \
+                               (const int32_t *)A.tail_ptr, (const int32_t *)A.tail_col, (const cplx *)A.tail_val, x, y, k, shift ? 1 : 0, *kc); \
+        else if (A.n_tail_long)                                                                                                             \
             hipLaunchKernelGGL((tail_long_multi_kernel<KK>), dim3((unsigned)(((int64_t)A.n_tail_long * 64 + 255) / 256)), dim3(256), 0,     \
                                c.stream, (int64_t)A.n_tail_long, (const int32_t *)A.tail_long, (const int32_t *)A.tail_rows,                \
                                (const int32_t *)A.tail_ptr, (const int32_t *)A.tail_col, (const cplx *)A.tail_val, x, y, k, shift ? 1 : 0, kk); \
@@ -386,27 +474,36 @@ int op_apply_multi_raw(Op *op, const cplx *x, cplx *y, int64_t n, int k, const c
     MGCR_CHECK(k >= 1 && k <= MV_MAX_K, MGCR_ERR_INVALID, "k = %d columns, 1 .. %d are supported", k, MV_MAX_K);
     if (n == 0) return MGCR_OK;
     MGCR_CHECK(x != y, MGCR_ERR_INVALID, "the k-wide apply cannot run in place");
-    const Op *b0 = op->kind == OP_DIRAC ? op->base : op;
+    const Op *b0 = op->kind == OP_DIRAC || op->kind == OP_DIRAC_MULTI ? op->base : op;
     MGCR_CHECK(!op->dist && !op->comm && !(b0 && (b0->dist || b0->comm)), MGCR_ERR_UNSUPPORTED,
                "the k-wide apply does not support distributed operators");
     switch (op->kind) {
         case OP_CSR:
             MGCR_CHECK(op->csr.ncol == n, MGCR_ERR_INVALID, "Sparse matrix dimension does not match Field dimension!");
             MGCR_CHECK(!w || op->csr.nrow == n, MGCR_ERR_INVALID, "residual form needs a square matrix");
-            return w ? csr_apply_multi(op->csr, x, y, k, true, make_double2(1., 0.), w)
-                     : csr_apply_multi(op->csr, x, y, k, false, make_double2(0., 0.), nullptr);
+            return w ? csr_apply_multi(op->csr, x, y, k, true, make_double2(1., 0.), nullptr, w)
+                     : csr_apply_multi(op->csr, x, y, k, false, make_double2(0., 0.), nullptr, nullptr);
         case OP_DIRAC:
             MGCR_CHECK(!w, MGCR_ERR_INVALID, "residual form: plain Sparse only");
             MGCR_CHECK(b0->kind == OP_CSR && b0->csr.nrow == n && b0->csr.ncol == n, MGCR_ERR_INVALID,
                        "DiracOp needs a square matrix matching the Field dimension");
             MGCR_CHECK(op->k.x != 0. || op->k.y != 0., MGCR_ERR_INVALID, "No k value supplied for Dirac Operator!");
-            return csr_apply_multi(b0->csr, x, y, k, true, op->k, nullptr);
+            return csr_apply_multi(b0->csr, x, y, k, true, op->k, nullptr, nullptr);
+        case OP_DIRAC_MULTI: {
+            MGCR_CHECK(!w, MGCR_ERR_INVALID, "residual form: plain Sparse only");
+            MGCR_CHECK(b0->kind == OP_CSR && b0->csr.nrow == n && b0->csr.ncol == n, MGCR_ERR_INVALID,
+                       "MultiDiracOp needs a square matrix matching the Field dimension");
+            MGCR_CHECK(k == op->nk, MGCR_ERR_INVALID, "MultiDiracOp carries %d hopping parameters, the block has %d columns", op->nk, k);
+            KCols ks;
+            for (int q = 0; q < MV_MAX_K; q++) ks.v[q] = op->ks[q];   // (entries from k on are 0 and are not read)
+            return csr_apply_multi(b0->csr, x, y, k, true, op->ks[0], &ks, nullptr);
+        }
         case OP_BCSR:
             MGCR_CHECK(!w, MGCR_ERR_INVALID, "residual form: plain Sparse only");
             MGCR_CHECK((int64_t)op->bcsr.nbcol * op->bcsr.bs == n, MGCR_ERR_INVALID, "Sparse matrix dimension does not match Field dimension!");
             return bcsr_apply_multi(op->bcsr, x, y, k);
         default:
-            set_error("the k-wide apply supports Sparse, DiracOp and HierarchicalSparse / Dense operators (not GCR or MG objects)");
+            set_error("the k-wide apply supports Sparse, DiracOp, MultiDiracOp and HierarchicalSparse / Dense operators (not GCR or MG objects)");
             return MGCR_ERR_UNSUPPORTED;
     }
 }

@@ -3,6 +3,7 @@ either side of the hot path — plus the MatrixMarket 
 (rank 2).  Each function returns its numbers (and prints what the reference prints).
 
     python -m mgpreconditionedgcr_amd.experiments kcritical  --dir data/sample_matrix
+    python -m mgpreconditionedgcr_amd.experiments kcritical  --dir data/sample_matrix --batched
     python -m mgpreconditionedgcr_amd.experiments mg_property --dir data/sample_matrix
     python -m mgpreconditionedgcr_amd.experiments hermiticity --dir data/sample_matrix
     python -m mgpreconditionedgcr_amd.experiments parse  conf.mtx parsed.txt
@@ -12,7 +13,7 @@ import os
 
 import numpy as np
 
-from .api import DiracOp, Field, GCR, GCR_Param, MG, MG_Param, Mesh, Sparse, read_data
+from .api import DiracOp, Field, GCR, GCR_Param, MG, MG_Param, Mesh, MultiDiracOp, MultiField, Sparse, read_data
 
 DIMS_4x4 = (4, 4, 4, 4, 4, 3)
 K_CRITICAL = {"4x4parsed.txt": 0.20611, "8x8parsed.txt": 0.17865}  # src/main.cpp:699,722,845
@@ -78,6 +79,28 @@ def test_kcritical(D, dims, k_c, k_start, steps=5, restart=10, max_iter=50000, t
     return out
 
 
+def test_kcritical_batched(D, dims, k_c, k_start, steps=5, restart=10, max_iter=50000, tol=1e-13, seed=42):
+    """test_kcritical as ONE batched solve: the ladder of k is the shift per column of a MultiDiracOp, the right-hand side is the
+    same in every column, D is streamed once per step for all of them.  Prints the same lines and returns the same tuples (column j
+    has the bits of the single solve with DiracOp(D, k_j)); a column that has converged is frozen while the others go on, so the
+    scan takes as many steps as its slowest column."""
+    if not 1 <= steps <= 16:
+        raise ValueError("the batched scan takes 1 .. 16 values of k, got %d" % steps)
+    field = Field(dims).fill_rhs(seed)
+    step = (k_c - k_start) / steps
+    ks = [k_start + step * i for i in range(steps)]
+    rhs = MultiField.from_fields([field] * steps)
+    sol = MultiField(dims, steps).set_zero()
+    gcr = GCR(MultiDiracOp(D, ks), GCR_Param(0, restart, max_iter, tol, False, check_every=50))
+    gcr.solve_multi(rhs, sol)
+    out = []
+    for j, k in enumerate(ks):
+        print("k = %f: %s after %d steps, residual %.10e" % (k, "converged" if gcr.last_converged[j] else "did not converge",
+                                                             gcr.last_iterations[j], gcr.last_history[j][-1]))
+        out.append((k, gcr.last_iterations[j], gcr.last_converged[j], float(gcr.last_history[j][-1])))
+    return out
+
+
 def test_MG_property(Dirac, dims, subblock=2, n_eigen=2, null_vectors=None, seed=42):
     """src/main.cpp:877-918 and MG::test_MG (src/MG.h:432-512): projector identities
     (R P R = R, P R P R = P R) and coarse-operator consistency P R A v = P A_c R v on span(P)."""
@@ -109,6 +132,7 @@ def main():
     ap.add_argument("args", nargs="*")
     ap.add_argument("--dir", default="../../data/sample_matrix/")
     ap.add_argument("--file", default="4x4parsed.txt")
+    ap.add_argument("--batched", action="store_true", help="kcritical: every k as one column of ONE batched solve")
     a = ap.parse_args()
     if a.what == "parse":
         parse_data(a.args[0], a.args[1])
@@ -119,7 +143,7 @@ def main():
         test_hermiticity(D, dims)
     elif a.what == "kcritical":
         kc = K_CRITICAL.get(a.file, 0.20611)
-        test_kcritical(D, dims, kc, kc - 0.00611 if a.file.startswith("4x4") else 0.174)
+        (test_kcritical_batched if a.batched else test_kcritical)(D, dims, kc, kc - 0.00611 if a.file.startswith("4x4") else 0.174)
     else:
         test_MG_property(DiracOp(D, 0.1), dims)
 

@@ -1,0 +1,47 @@
+"""The block classes of the C++ mirror (include/mgcr/mgcr_dropin.hpp: MultiField, Operator::apply_multi, GCR::solve_multi,
+MultiDiracOp) through examples/k_critical_batched.cpp: it compiles with g++, and on the GPU the lines it prints for a
+three-value hopping-parameter scan of the sample are, digit for digit, those of the Python batched solve with the same
+parameters (rhs init_rand(0) in the g++ evaluation order = the golden `gcr_rhs`, x0 = 0, GCR(5), 400 steps, 1e-10)."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "examples", "build", "k_critical_batched")
+KS = [0.05, 0.15, 0.18]
+
+
+def test_example_compiles_with_gxx():
+    p = subprocess.run(["make", "-C", os.path.join(ROOT, "examples")], capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert os.path.exists(EXE)
+
+
+def test_example_wants_at_least_one_k():
+    assert os.path.exists(EXE), "run __graft_entry__.build() first"
+    p = subprocess.run([EXE], capture_output=True, text=True, timeout=60)     # (returns before anything touches the device)
+    assert p.returncode == 2 and "usage" in p.stderr
+
+
+@pytest.mark.gpu
+def test_scan_lines_equal_the_python_batched_solve(sample_matrix_path, sample_gold):
+    assert os.path.exists(EXE), "run __graft_entry__.build() first"
+    d = os.path.dirname(sample_matrix_path)
+    p = subprocess.run([EXE, os.path.basename(sample_matrix_path)] + ["%r" % k for k in KS], capture_output=True, text=True,
+                       env=dict(os.environ, MGCR_SAMPLE_DIR=d), timeout=300, cwd=d)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    from mgpreconditionedgcr_amd import Field, GCR, GCR_Param, MultiDiracOp, MultiField, read_data
+    D = read_data(os.path.basename(sample_matrix_path), directory=d)
+    n = D.get_dim()
+    g = GCR(MultiDiracOp(D, KS), GCR_Param(0, 5, 400, 1e-10, False))
+    b = Field((n,), sample_gold["gcr_rhs"])
+    g.solve_multi(MultiField.from_fields([b] * len(KS)), MultiField((n,), len(KS)).set_zero())
+    want = ["[%d] Step %d residual norm = %.10e" % (j, i, h) for j in range(len(KS)) for i, h in enumerate(g.last_history[j])]
+    printed = re.findall(r"^\[\d+\] Step \d+ residual norm = \S+$", p.stdout, re.M)
+    assert printed == want, "first differing line: %s" % (next((a, b_) for a, b_ in zip(printed + [None], want + [None]) if a != b_),)
+    steps = [int(m) for m in re.findall(r"^k = \S+: converged after (\d+) steps$", p.stdout, re.M)]
+    assert steps == g.last_iterations and all(g.last_converged), (steps, g.last_iterations)
+    assert len(set(steps)) == len(KS)                                      # three different stopping steps
+    assert re.findall(r"^k = (\S+):", p.stdout, re.M) == ["0.05", "0.15", "0.18"]

@@ -6,7 +6,15 @@ One JSON line to stdout (--out FILE writes it too).  For k in --ks (default 1 2 
   2. irregular CSR, 8 Mi rows (problems.skewed_csr), windows 2^17 and 900, cold caches (a 256 MiB -> 256 MiB copy sweeps the caches before every timed apply);
   3. GCR(5), Poisson 128^3, 20 steps, tol 0: solve_multi(k) against k single solves (system-iterations per second).
 Every figure is the median of --runs (>= 6) timings with the two sides interleaved (A B A B ...), range reported; hipEvents on
-the library stream (mgcr_timer_*, mgcr_bench_op_apply, mgcr_bench_op_apply_multi).  Next to each measured ratio stands the
+the library stream (mgcr_timer_*, mgcr_bench_op_apply, mgcr_bench_op_apply_multi).
+  4. (--parts kscan, not in the default set; result also written to profiles/kscan.json with --out) hopping-parameter scans, one
+     MultiDiracOp solve against one DiracOp solve per value, on (a) the 3072-row sample (--sample FILE, text CSR) and (b) a DiracOp on
+     problems.skewed_csr with 2^20 rows and window 2^17: equal-length columns (k = 4, 8, tol 0, 200 steps on (a), 40 on (b); time per
+     system-iteration), and the six-value scan of tests/kscan_cases.py on (a) (batched wall time against the sum of the six single
+     solves: the batched solve runs as long as its slowest column);
+  5. (--parts uniform --lib SO: one side; --parts uniform_ab --parent-lib SO: both sides, alternating, one process per timing)
+     apply_multi of a plain DiracOp at k = 8 on (a) and (b) with the library of the parent commit against this one, next to the spread
+     of parent against parent from the same call.  Next to each measured ratio stands the
 byte-model ratio k (M + 2 V) / (M + 2 k V), M = matrix bytes, V = 16 n; for the solve, bytes per step from the terms of
 bench.py's gcr_phase_model, averaged over a GCR(5) cycle (lim = 1 .. 5 stored directions): the single solve's one-launch steps
 move M + (2 lim + 4) V in a cycle and M + (3 R + 5) V in the step that closes it (11.2 V on average); the batched solve moves,
@@ -21,7 +29,8 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mgpreconditionedgcr_amd import (Field, GCR, GCR_Param, HierarchicalSparse, MultiField, Sparse, _lib, problems)  # noqa: E402
+from mgpreconditionedgcr_amd import (DiracOp, Field, GCR, GCR_Param, HierarchicalSparse, MultiField, Sparse, _lib, problems,  # noqa: E402
+                                     read_data)
 
 
 def stats(v):
@@ -70,6 +79,109 @@ def record(k, s, m, M, V):
             "byte_model_ratio": k * (M + 2 * V) / (M + 2 * k * V)}
 
 
+SCAN_KS = [0.05, 0.10, 0.15, 0.15 + 0.05j, 0.18, 0.20]      # tests/kscan_cases.py
+SCAN_ARGS = (0, 5, 400, 1e-10)
+
+
+def kscan_systems(sample):
+    n = 1 << 20
+    yield "sample", read_data(os.path.basename(sample), directory=os.path.dirname(os.path.abspath(sample))), 200, \
+        lambda k: [0.05 + 0.13 * j / (k - 1) for j in range(k)]
+    yield "skewed_2p20_w2p17", Sparse(n, n, *problems.skewed_csr(n, np.random.default_rng(4), window=1 << 17)), 40, \
+        lambda k: [0.01 + 0.002 * j for j in range(k)]
+
+
+def scan_pair(D, ks, args, rhs, runs):
+    """(one single solve per k_j, one batched solve with per-column k) in ms, interleaved; iterations per column of either side"""
+    from mgpreconditionedgcr_amd import MultiDiracOp
+    n, k = D.get_dim(), len(ks)
+    prm = GCR_Param(*args, False)
+    singles = [GCR(DiracOp(D, kj), prm) for kj in ks]
+    gm = GCR(MultiDiracOp(D, ks), prm)
+    x, X = Field((n,)), MultiField((n,), k)
+    R = MultiField.from_fields(rhs)
+    for j in range(k):
+        singles[j].solve(rhs[j], x.set_zero())
+    gm.solve_multi(R, X.set_zero())
+    its_single, its_multi = [g.last_iterations for g in singles], list(gm.last_iterations)
+    finite = all(np.isfinite(h).all() for h in gm.last_history)
+    single, multi = [], []
+    for _ in range(runs):
+        t = 0.0
+        for j in range(k):
+            x.set_zero()
+            t += timer(lambda: singles[j].solve(rhs[j], x))
+        single.append(t)
+        X.set_zero()
+        multi.append(timer(lambda: gm.solve_multi(R, X)))
+    return stats(single), stats(multi), its_single, its_multi, finite
+
+
+def kscan(sample, runs):
+    out = {}
+    for name, D, steps, ladder in kscan_systems(sample):
+        n = D.get_dim()
+        rec = {"rows": n, "layout": D.ell_layout(), "storage_format": D.storage_format()[0], "steps": steps, "restart": 5, "equal_length": []}
+        b = Field((n,)).fill_rhs(1)
+        for k in (4, 8):
+            s, m, its_s, its_m, finite = scan_pair(D, ladder(k), (0, 5, steps, 0.0), [b] * k, runs)
+            assert its_s == its_m == [steps] * k, (its_s, its_m)
+            rec["equal_length"].append({"k": k, "ks": [str(v) for v in ladder(k)], "single_ms": s, "multi_ms": m, "histories_finite": finite,
+                                        "ratio": s["median"] / m["median"],
+                                        "ranges_overlap": not (m["max"] < s["min"] or s["max"] < m["min"]),
+                                        "single_us_per_system_iteration": 1e3 * s["median"] / (k * steps),
+                                        "multi_us_per_system_iteration": 1e3 * m["median"] / (k * steps)})
+        if name == "sample":
+            b = Field((n,), problems.rhs_grid(n, 1))
+            s, m, its_s, its_m, _ = scan_pair(D, SCAN_KS, SCAN_ARGS, [b] * len(SCAN_KS), runs)
+            assert its_s == its_m, (its_s, its_m)
+            rec["scan"] = {"ks": [str(v) for v in SCAN_KS], "restart": 5, "max_iter": 400, "tol": 1e-10, "iterations": its_m,
+                           "sum_of_singles_ms": s, "batched_ms": m, "ratio_singles_over_batched": s["median"] / m["median"],
+                           "ranges_overlap": not (m["max"] < s["min"] or s["max"] < m["min"]),
+                           "sum_iterations": sum(its_m), "max_iterations": max(its_m),
+                           "batched_us_per_lockstep_step": 1e3 * m["median"] / max(its_m),
+                           "single_us_per_iteration": 1e3 * s["median"] / sum(its_m)}
+        out[name] = rec
+        del D
+    return out
+
+
+def uniform_side(sample, runs):
+    """apply_multi of a plain DiracOp at k = 8 (the uniform-shift path), ms per apply, on the two systems of the scan measurement"""
+    out = {}
+    for name, D, _, _ in kscan_systems(sample):
+        n = D.get_dim()
+        A = DiracOp(D, 0.15 + 0.05j)
+        X = MultiField.from_fields([Field((n,)).fill_rhs(j) for j in range(8)])
+        Y = MultiField((n,), 8)
+        reps = 2000 if n < 1 << 16 else 40
+        A.bench_apply_multi(X, Y, reps=reps)
+        out[name] = stats([A.bench_apply_multi(X, Y, reps=reps) for _ in range(runs)])
+        out[name]["checksum"] = float(Y.squarednorm().sum())
+    return out
+
+
+def uniform_ab(sample, parent_lib, runs):
+    """parent, this, parent, this, ...: one process per timing (a process loads one library); the spread of parent against parent is
+    the spread between the parent's own processes"""
+    import subprocess
+    sides = {"parent": [], "this": []}
+    for _ in range(runs):
+        for side, lib in (("parent", parent_lib), ("this", _lib.LIB_PATH)):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--parts", "uniform", "--lib", lib, "--sample", sample],
+                               capture_output=True, text=True, check=True, timeout=600)
+            sides[side].append(json.loads(p.stdout.strip().splitlines()[-1])["uniform"])
+    out = {}
+    for name in sides["parent"][0]:
+        pa = [r[name]["median"] for r in sides["parent"]]
+        th = [r[name]["median"] for r in sides["this"]]
+        assert len({r[name]["checksum"] for r in sides["parent"] + sides["this"]}) == 1      # the same bits from both libraries
+        out[name] = {"k": 8, "parent_ms": stats(pa), "this_ms": stats(th), "this_over_parent": float(np.median(th) / np.median(pa)),
+                     "parent_spread": (max(pa) - min(pa)) / float(np.median(pa)),
+                     "inside_parent_spread": bool(min(pa) <= np.median(th) <= max(pa))}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ks", type=int, nargs="+", default=[1, 2, 4, 8, 12])
@@ -78,9 +190,23 @@ def main():
     ap.add_argument("--block-rows", type=int, default=36000)
     ap.add_argument("--irregular-rows", type=int, default=1 << 23)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sample", default=None, help="kscan / uniform: the 3072-row sample matrix (text CSR, e.g. 4x4parsed.txt)")
+    ap.add_argument("--lib", default=None, help="uniform: load this libmgcr_hip.so instead of the in-tree one")
+    ap.add_argument("--parent-lib", default=None, help="uniform_ab: the library built from the parent commit")
     a = ap.parse_args()
     runs = max(6, a.runs)
     out = {"tool": "bench_multi_rhs", "runs": runs}
+    if a.lib:      # (a library from before the MultiDiracOp entry points lacks their symbols: bind what it has)
+        _lib.LIB_PATH = os.path.abspath(a.lib)
+        have = C.CDLL(_lib.LIB_PATH)
+        for name in [nm for nm in _lib._SIGS if not hasattr(have, nm)]:
+            del _lib._SIGS[name]
+    if "kscan" in a.parts:
+        out["kscan"] = kscan(a.sample, runs)
+    if "uniform" in a.parts:
+        out["uniform"] = uniform_side(a.sample, runs)
+    if "uniform_ab" in a.parts:
+        out["uniform_ab"] = uniform_ab(a.sample, a.parent_lib, runs)
     if "bcsr" in a.parts:
         nb, bs = a.block_rows, 20
         rows, cols, blocks = problems.unstructured_blocks(nb, bs)
