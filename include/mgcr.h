@@ -208,7 +208,8 @@ int mgcr_set_option(const char *name, int value, int *previous);
  * because a one-launch path gave up (foreign work on the device: its grid was not co-resident), "halo_split_exchanges" =
  * peer-write halo exchanges of distributed applies that ran split (store + publish | interior rows | wait | boundary rows),
  * "pw_tail_folds" = reductions folded and summed over the ranks inside their producing kernel, "multi_solves" = batched solves
- * (mgcr_gcr_solve_multi) completed. */
+ * (mgcr_gcr_solve_multi) completed — queued solves are not counted there but in "queue_solves" = mgcr_gcr_solve_queue calls completed,
+ * "queue_admissions" = systems those loaded into a slot after step 0, "queue_steps" = lockstep steps they launched. */
 int mgcr_stat(const char *name, int64_t *value);
 
 /* Self-test of the hardware behaviour the one-launch solver paths (csrc/gcr_resident.hip, gcr_stepbuild.hip) build on: inside
@@ -263,6 +264,28 @@ int mgcr_gcr_solve(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_vec_t rhs, mgc
  * next while n, k and the cycle length stay the same, and are freed by mgcr_finalize. */
 int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t rhs, mgcr_mvec_t x, double *hist, int32_t hist_cap,
                          int32_t *n_iter, int32_t *converged);
+/* Queued batched GCR: nsys independent systems (any nsys) stream through `width` <= 16 slots (columns) of ONE batched restarted solve
+ * (csrc/gcr_multi.hip; the schedule is csrc/queue_plan.h).  System s: A x_s = rhs_s (k_ri == NULL), or (1 - k_s D) x_s = rhs_s with
+ * A = D a single-GPU Sparse (k_ri: [nsys][2], no zero entry).  At step 0 the first min(width, nsys) systems occupy the slots; a slot
+ * whose system has stopped is drained (its x, history, iteration count handed back) and refilled with the next waiting system, first
+ * in, first out, at the next boundary of the restart cycle — or at once when every slot has stopped.  The host drives all of it
+ * between launches: it polls the columns' device states at every cycle boundary and every check_every steps; no kernel waits on
+ * another.  width > nsys is allowed (the surplus slots stay empty).
+ * rhs, x: [nsys] Fields of the operator's dimension.  rhs handles may repeat (a scan has one b); the x handles must be pairwise
+ * distinct and none of them may be a right-hand side (MGCR_ERR_INVALID, nothing is touched).  x_s is read and updated in place as
+ * mgcr_gcr_solve does it, use_x0 included.  hist: [nsys][hist_cap] or NULL; n_iter, converged: [nsys] or NULL — per SYSTEM, in
+ * the caller's order.
+ * Operators: k_ri == NULL — whatever mgcr_gcr_solve_multi takes except a MultiDiracOp (its width is a block's:
+ * MGCR_ERR_UNSUPPORTED); k_ri != NULL — a plain single-GPU Sparse (MGCR_ERR_INVALID otherwise, MGCR_ERR_UNSUPPORTED when it is
+ * distributed).  MGCR_ERR_UNSUPPORTED: every case of mgcr_gcr_solve_multi (truncation != 0, restart == 0, cycles longer than 16, a
+ * preconditioner, flexible, profile_spmv, distributed operators, GCR / MG objects).  MGCR_ERR_INVALID: width outside 1 .. 16,
+ * nsys < 1, a null handle, a size mismatch.
+ * Rule: history, iteration count, convergence flag and x of system s are BIT-IDENTICAL to mgcr_gcr_solve on that system alone (with
+ * k_ri: on DiracOp(D, k_s)), under the conditions mgcr_gcr_solve_multi states (default options, mgcr_op_xr_fuse_kind 0 or 1, more
+ * rows than the small-solve limit) — whatever the width, the order of the systems and check_every.
+ * The work storage is mgcr_gcr_solve_multi's at k = min(width, nsys) plus two blocks (x, b), kept and freed likewise. */
+int mgcr_gcr_solve_queue(mgcr_op_t A, const mgcr_gcr_param *param, int32_t width, int32_t nsys, const mgcr_vec_t *rhs, const mgcr_vec_t *x,
+                         const double *k_ri, double *hist, int32_t hist_cap, int32_t *n_iter, int32_t *converged);
 /* Unpreconditioned solves on a single-GPU Sparse / DiracOp with at most `rows` unknowns (default
  * 1024, $MGCR_SMALL_SOLVE_ROWS; and at most 16*rows stored entries) and <= 8 stored directions run
  * as ONE launch of one workgroup (latency regime: coarsest multigrid levels); 0 disables that path.

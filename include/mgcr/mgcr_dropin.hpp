@@ -781,6 +781,33 @@ public:
             last_converged[(size_t)j] = conv[(size_t)j] != 0;
         }
     }
+    // Any number of systems through `width` <= 16 columns of one batched solve (extension, mgcr_gcr_solve_queue): a column whose
+    // system has stopped takes the next waiting one at the next boundary of the restart cycle.  System s: A x_s = rhs_s, or — ks
+    // given, A the Sparse D — (1 - ks[s] D) x_s = rhs_s.  rhs may repeat, the x Fields are distinct and updated in place; per
+    // SYSTEM: last_history[s], last_iterations[s], last_converged[s] — the bits of solve() on that system alone.
+    void solve_queue(const std::vector<const Field<num_type> *> &rhs, const std::vector<Field<num_type> *> &x, int width,
+                     const std::vector<std::complex<double>> *ks = nullptr) {
+        if (!A_operator) { std::fprintf(stderr, "GCR has no operator (call initialise first)\n"); std::abort(); }
+        if (rhs.size() != x.size() || (ks && ks->size() != rhs.size())) { std::fprintf(stderr, "GCR::solve_queue: one x (and one k) per right-hand side\n"); std::abort(); }
+        mgcr_gcr_param p = cparam();
+        const int nsys = (int)rhs.size(), cap = (param->max_iter > 0 ? param->max_iter : 1) + 1;
+        std::vector<mgcr_vec_t> bh, xh;
+        for (int s = 0; s < nsys; s++) { bh.push_back(rhs[(size_t)s]->device()); xh.push_back(x[(size_t)s]->device()); }
+        std::vector<double> kri, hist((size_t)nsys * cap, 0.);
+        if (ks) for (const std::complex<double> &k : *ks) { kri.push_back(k.real()); kri.push_back(k.imag()); }
+        std::vector<int32_t> it((size_t)nsys, 0), conv((size_t)nsys, 0);
+        mgcr_detail::ok(mgcr_gcr_solve_queue(need_handle(A_operator), &p, width, nsys, bh.data(), xh.data(), ks ? kri.data() : nullptr, hist.data(), cap,
+                                             it.data(), conv.data()),
+                        "GCR::solve_queue");
+        last_history.assign((size_t)nsys, std::vector<double>());
+        last_iterations.assign(it.begin(), it.end());
+        last_converged.assign((size_t)nsys, false);
+        for (int s = 0; s < nsys; s++) {
+            x[(size_t)s]->device_written();
+            last_history[(size_t)s].assign(hist.begin() + (size_t)s * cap, hist.begin() + (size_t)s * cap + it[(size_t)s] + 1);
+            last_converged[(size_t)s] = conv[(size_t)s] != 0;
+        }
+    }
     std::vector<std::vector<double>> last_history;
     std::vector<int> last_iterations;
     std::vector<bool> last_converged;

@@ -136,6 +136,8 @@ _SIGS = {
     "mgcr_op_apply_multi": (C.c_int, [_vp, _vp, _vp]),
     "mgcr_bench_op_apply_multi": (C.c_int, [_vp, _vp, _vp, C.c_int32, _dp]),
     "mgcr_gcr_solve_multi": (C.c_int, [_vp, C.POINTER(GcrParamC), _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mgcr_gcr_solve_queue": (C.c_int, [_vp, C.POINTER(GcrParamC), C.c_int32, C.c_int32, C.POINTER(_vp), C.POINTER(_vp), _dp, _vp, C.c_int32,
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mgcr_timer_start": (C.c_int, []),
     "mgcr_timer_stop": (C.c_int, [_dp]),
 }

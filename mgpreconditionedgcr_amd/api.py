@@ -563,6 +563,36 @@ class GCR(Operator):
         self.last_history = [hist[j, : it[j] + 1].copy() for j in range(k)]
         return X
 
+    def solve_queue(self, rhs_list, x_list, width=8, ks=None):
+        """len(rhs_list) independent systems (any number) through `width` <= 16 slots of one batched solve (mgcr_gcr_solve_queue):
+        a slot whose system has stopped is refilled with the next one at the next boundary of the restart cycle.  System s is
+        A x_s = rhs_s with A the operator of this GCR, or — ks given, A the Sparse D — (1 - ks[s] D) x_s = rhs_s.  rhs Fields may
+        repeat, the x Fields are distinct and updated in place; last_history, last_iterations and last_converged are kept per
+        system, each with the bits of solve() on that system alone."""
+        if self.A is None:
+            raise MgcrError(1, "GCR has no operator (call initialise first)")
+        nsys = len(rhs_list)
+        if len(x_list) != nsys:
+            raise MgcrError(1, "solve_queue: %d right-hand sides, %d x Fields" % (nsys, len(x_list)))
+        kv = None
+        if ks is not None:
+            kv = MultiDiracOp._values(ks)
+            if kv.shape[0] != nsys:
+                raise MgcrError(1, "solve_queue: %d hopping parameters for %d systems" % (kv.shape[0], nsys))
+        cap = max(self.param.max_iter, 1) + 1
+        hist = np.zeros((max(nsys, 1), cap), np.float64)
+        it, conv = (C.c_int32 * max(nsys, 1))(), (C.c_int32 * max(nsys, 1))()
+        bh = (C.c_void_p * max(nsys, 1))(*[f.h for f in rhs_list])
+        xh = (C.c_void_p * max(nsys, 1))(*[f.h for f in x_list])
+        pc = self.param._c()
+        check(_lib.lib().mgcr_gcr_solve_queue(self.A.h, C.byref(pc), int(width), nsys, bh, xh,
+                                              kv.ctypes.data_as(C.POINTER(C.c_double)) if kv is not None else None,
+                                              hist.ctypes.data, cap, it, conv))
+        self.last_iterations = [int(v) for v in it][:nsys]
+        self.last_converged = [bool(v) for v in conv][:nsys]
+        self.last_history = [hist[j, : it[j] + 1].copy() for j in range(nsys)]
+        return x_list
+
 
 def legacy_dense_gcr(matrix, rhs, x, tol, max_iter, truncation, verbose=True):
     """GCR(matrix, dimension).solve(rhs, x, tol, max_iter, truncation) — the reference's legacy raw-pointer dense solve

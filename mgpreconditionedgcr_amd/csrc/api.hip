@@ -257,6 +257,9 @@ int mgcr_stat(const char *name, int64_t *value) {
     else if (!strcmp(name, "halo_split_exchanges")) *value = dist_halo_split_count();
     else if (!strcmp(name, "pw_tail_folds")) *value = comm_pw_tail_count();
     else if (!strcmp(name, "multi_solves")) *value = gcr_multi_solve_count();
+    else if (!strcmp(name, "queue_solves")) *value = gcr_queue_stat(0);
+    else if (!strcmp(name, "queue_admissions")) *value = gcr_queue_stat(1);
+    else if (!strcmp(name, "queue_steps")) *value = gcr_queue_stat(2);
     else { set_error("mgcr_stat: unknown counter '%s'", name); return MGCR_ERR_INVALID; }
     return MGCR_OK;
 }
@@ -476,6 +479,64 @@ int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t r
                "mgcr_gcr_solve_multi: the MultiDiracOp carries %d hopping parameters, the blocks have %d columns", A->nk, (int)x->k);
     LOCK();
     return gcr_multi_run(A, *param, rhs->d, x->d, x->n, x->k, hist, hist_cap, n_iter, converged);
+}
+
+int mgcr_gcr_solve_queue(mgcr_op_t A, const mgcr_gcr_param *param, int32_t width, int32_t nsys, const mgcr_vec_t *rhs, const mgcr_vec_t *x,
+                         const double *k_ri, double *hist, int32_t hist_cap, int32_t *n_iter, int32_t *converged) {
+    const char *who = "mgcr_gcr_solve_queue";
+    MGCR_TRY(require_ctx());
+    MGCR_CHECK(A && param && rhs && x, MGCR_ERR_INVALID, "%s: null argument", who);
+    MGCR_CHECK(param->truncation >= 0 && param->restart >= 0 && param->max_iter >= 0, MGCR_ERR_INVALID, "negative GCR parameter");
+    MGCR_CHECK(param->truncation == 0, MGCR_ERR_UNSUPPORTED, "%s: truncation mode is not supported (restart mode only)", who);
+    MGCR_CHECK(param->restart != 0, MGCR_ERR_UNSUPPORTED, "%s: restart mode only (restart != 0)", who);
+    MGCR_CHECK(!param->left_precond && !param->right_precond, MGCR_ERR_UNSUPPORTED, "%s: preconditioners are not supported", who);
+    MGCR_CHECK(!param->flexible && !param->profile_spmv, MGCR_ERR_UNSUPPORTED, "%s: flexible / profile_spmv are not supported", who);
+    MGCR_CHECK(A->kind != OP_GCR && A->kind != OP_MG, MGCR_ERR_UNSUPPORTED, "%s: the operator must be a matrix", who);
+    {
+        const Op *b0 = op_matrix(A);
+        MGCR_CHECK(!A->dist && !A->comm && !b0->dist && !b0->comm, MGCR_ERR_UNSUPPORTED, "%s: distributed operators are not supported", who);
+    }
+    if (k_ri) {
+        MGCR_CHECK(A->kind == OP_CSR, MGCR_ERR_INVALID, "%s: with hopping parameters the operator must be the plain Sparse D of 1 - k D", who);
+        MGCR_CHECK(A->csr.nrow == A->csr.ncol, MGCR_ERR_INVALID, "%s: matrix must be square", who);
+    } else {
+        MGCR_CHECK(A->kind != OP_DIRAC_MULTI, MGCR_ERR_UNSUPPORTED,
+                   "%s: a MultiDiracOp's width is that of a block; pass its Sparse and the hopping parameters (k_ri) instead", who);
+    }
+    MGCR_CHECK(width >= 1 && width <= MV_MAX_K, MGCR_ERR_INVALID, "%s: width = %d slots, 1 .. %d are supported", who, (int)width, MV_MAX_K);
+    MGCR_CHECK(nsys >= 1, MGCR_ERR_INVALID, "%s: nsys = %d systems", who, (int)nsys);
+    MGCR_CHECK((A->nrow ? A->nrow : A->dim) == A->dim, MGCR_ERR_INVALID, "%s: the operator must be square", who);
+    std::vector<const void *> xs, bs;
+    for (int32_t s = 0; s < nsys; s++) {
+        MGCR_CHECK(rhs[s] && x[s], MGCR_ERR_INVALID, "%s: system %d has a null Field", who, (int)s);
+        MGCR_CHECK(rhs[s]->n == A->dim, MGCR_ERR_INVALID, "Field dimension does not match with Operator!");
+        MGCR_CHECK(x[s]->n == A->dim, MGCR_ERR_INVALID, "x dimension does not match with Operator!");
+        xs.push_back(x[s]->d);
+        bs.push_back(rhs[s]->d);
+    }
+    if (A->dim > 0) {   // the x Fields are written while other systems still read their right-hand sides
+        std::sort(xs.begin(), xs.end());
+        std::sort(bs.begin(), bs.end());
+        MGCR_CHECK(std::adjacent_find(xs.begin(), xs.end()) == xs.end(), MGCR_ERR_INVALID, "%s: the x Fields must be pairwise distinct", who);
+        for (const void *q : xs)
+            MGCR_CHECK(!std::binary_search(bs.begin(), bs.end(), q), MGCR_ERR_INVALID, "%s: an x Field is also a right-hand side", who);
+    }
+    std::vector<cplx> ks;
+    if (k_ri) {
+        ks.resize((size_t)nsys);
+        for (int32_t s = 0; s < nsys; s++) {
+            MGCR_CHECK(k_ri[2 * s] != 0. || k_ri[2 * s + 1] != 0., MGCR_ERR_INVALID, "%s: k[%d] is zero (No k value supplied for Dirac Operator!)", who, (int)s);
+            ks[(size_t)s] = make_double2(k_ri[2 * s], k_ri[2 * s + 1]);
+        }
+    }
+    LOCK();
+    std::vector<const cplx *> bp((size_t)nsys);
+    std::vector<cplx *> xp((size_t)nsys);
+    for (int32_t s = 0; s < nsys; s++) {
+        bp[(size_t)s] = rhs[s]->d;
+        xp[(size_t)s] = x[s]->w();
+    }
+    return gcr_queue_run(A, *param, width, nsys, bp.data(), xp.data(), k_ri ? ks.data() : nullptr, A->dim, hist, hist_cap, n_iter, converged);
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@
 #include "reduce.h"
 #include "gcr_dev.h"
 #include "multi_dev.h"
+#include "queue_plan.h"   // host only: the schedule of the queued solve
 
 namespace mgcr {
 
@@ -35,6 +36,17 @@ struct MPtrs {   // slots of a restart cycle: ps[0] = P0, ps[m] = D_m; aps[j] = 
 
 __device__ __forceinline__ bool m_active(const DevState *st, int col, int k, int it) {
     return col < k && !(st[col].stop_at < st[col].base + it);
+}
+
+// The queued solve (gcr_queue_run) admits columns at different steps, so a column's LAST step (own step number == max_iter) is not the
+// launch's: such a column takes the finishing bookkeeping (q_finish_kernel, which freezes it with stop_at == its step number) while
+// its neighbours run a full step, and the kernels behind that bookkeeping — coefficients, closing x update, build — must leave it
+// alone although stop_at == base + it reads as active.  Those three have q_ TWINS (q_coef_kernel, q_build_kernel, q_close_x_kernel):
+// the m_ kernel with this test in place of m_active.  A change to the arithmetic of either twin belongs in both — the bit-for-bit
+// rule ties solve_multi and solve_queue to the same single solve.  They are copies because a body shared through an inlined
+// __device__ function compiles to other code for the m_ entries (the work-group size is then looked up, not assumed).
+__device__ __forceinline__ bool q_active(const DevState *st, int col, int k, int it, int max_it) {
+    return m_active(st, col, k, it) && st[col].base + it < max_it;
 }
 
 __global__ void m_reset_kernel(DevState *st, double tol2, int k) {
@@ -204,6 +216,7 @@ __global__ void __launch_bounds__(RED_THREADS) m_dot_kernel(const cplx *__restri
     }
 }
 
+// (twin: q_coef_kernel below)
 // the prologue of build_lean_kernel / build_close_kernel, one workgroup per column: betas, the step's bookkeeping, and either
 // row `lim` of the coefficient table (in-cycle step) or the closing coefficients cp
 __global__ void __launch_bounds__(RED_THREADS) m_coef_kernel(DevState *st, int it, const double *__restrict__ partsB, const double *__restrict__ partsR,
@@ -243,7 +256,46 @@ __global__ void __launch_bounds__(RED_THREADS) m_coef_kernel(DevState *st, int i
         coef->cp[j][m] = lean_close_coef(lc, sbeta, lim, m);
     }
 }
+// ... in the queued solve (the same kernel but for the test of the column's own last step)
+__global__ void __launch_bounds__(RED_THREADS) q_coef_kernel(DevState *st, int it, const double *__restrict__ partsB, const double *__restrict__ partsR,
+                                                             int nblk, double *__restrict__ hist, int hist_cap, const cplx *__restrict__ den,
+                                                             LeanCoef *__restrict__ lcs, MCoef *__restrict__ coef, int lim, int closing, int max_it) {
+    __shared__ double lds[2 * 17];
+    __shared__ cplx sbeta[LND];
+    const int j = blockIdx.x;
+    if (!q_active(st, j, (int)gridDim.x, it, max_it)) return;   // stopped, or at its own last step: q_finish_kernel has done the bookkeeping
+    LeanCoef *lc = lcs + j;
+    for (int d = 0; d < lim; d++) {
+        double s[2];
+        fold_partials<2>(partsB + (size_t)((j * LND + d) * 2) * RED_MAX_BLOCKS, nblk, RED_MAX_BLOCKS, s, lds);
+        if (threadIdx.x == 0) sbeta[d] = cdiv(make_double2(s[0], s[1]), den[j * LND + d]);
+    }
+    double rr[1];
+    fold_partials<1>(partsR + (size_t)j * RED_MAX_BLOCKS, nblk, RED_MAX_BLOCKS, rr, lds);
+    if (threadIdx.x == 0) close_step(st + j, it, rr[0], hist + (size_t)j * hist_cap, hist_cap, closing != 0);
+    __syncthreads();
+    const int m = threadIdx.x;
+    if (m < lim) coef->beta[j][m] = sbeta[m];
+    if (!closing) {
+        if (lim < LND && m <= lim) {   // table row k = lim (build_lean_kernel)
+            const int kk = lim;
+            cplx a = make_double2(0., 0.);
+            if (m == 0) {
+                for (int q = 0; q < kk; q++) a = csub(a, cmul(sbeta[q], q == 0 ? make_double2(1., 0.) : lc->t[q]));
+                lc->t[kk] = a;
+            } else if (m < kk) {
+                for (int q = m; q < kk; q++) a = csub(a, cmul(sbeta[q], q == m ? make_double2(1., 0.) : lc->T[q * LND + m]));
+                lc->T[kk * LND + m] = a;
+            } else {
+                lc->T[kk * LND + kk] = make_double2(1., 0.);
+            }
+        }
+    } else if (m < lim) {              // cp (build_close_kernel / close_x_kernel)
+        coef->cp[j][m] = lean_close_coef(lc, sbeta, lim, m);
+    }
+}
 
+// (twin: q_build_kernel below)
 // Ap' = Ar - sum_d beta_d Ap_d (d ascending) with the <r,Ap'>, <Ap',Ap'> partials: the loop of build_lean_kernel.  ap_out may be
 // slot 0 itself (closing step): a thread reads its rows of every slot before it writes.
 template <int KC>
@@ -290,7 +342,53 @@ __global__ void __launch_bounds__(RED_THREADS) m_build_kernel(const DevState *__
     const int t = (int)threadIdx.x;
     if (t < 4 * KC && m_active(st, c0 + t / 4, k, it)) partsA[(size_t)((c0 + t / 4) * 4 + (t & 3)) * RED_MAX_BLOCKS + blockIdx.x] = tot;
 }
+// ... in the queued solve
+template <int KC>
+__global__ void __launch_bounds__(RED_THREADS) q_build_kernel(const DevState *__restrict__ st, int it, const MCoef *__restrict__ coef, MPtrs d, int lim,
+                                                              const cplx *r, const cplx *ar, cplx *ap_out, int64_t n, int k,
+                                                              double *__restrict__ partsA, int max_it) {
+    __shared__ double lds[4 * KC * 17];
+    const int c0 = (int)blockIdx.y * KC;
+    bool act[KC];
+    bool any = false;
+#pragma unroll
+    for (int c = 0; c < KC; c++) {
+        act[c] = q_active(st, c0 + c, k, it, max_it);
+        any = any || act[c];
+    }
+    if (!any) return;
+    double v[4 * KC];
+#pragma unroll
+    for (int s = 0; s < 4 * KC; s++) v[s] = 0.;
+    MV_GRID_STRIDE(i, n) {
+        cplx av[KC], rv[KC], ac[KC];
+        mv_load<KC>(ar, i, k, c0, av);
+        mv_load<KC>(r, i, k, c0, rv);
+#pragma unroll
+        for (int c = 0; c < KC; c++) ac[c] = make_double2(0., 0.);
+        for (int q = 0; q < lim; q++) {
+            cplx aj[KC];
+            mv_load<KC>(d.aps[q], i, k, c0, aj);
+#pragma unroll
+            for (int c = 0; c < KC; c++)
+                if (c0 + c < k) ac[c] = csub(ac[c], cmul(coef->beta[c0 + c][q], aj[c]));
+        }
+#pragma unroll
+        for (int c = 0; c < KC; c++) {
+            const cplx an = cadd(av[c], ac[c]);
+            if (act[c]) ap_out[i * k + c0 + c] = an;
+            const cplx t = cconj_mul(rv[c], an);
+            v[4 * c] += t.x; v[4 * c + 1] += t.y;
+            const cplx u = cconj_mul(an, an);
+            v[4 * c + 2] += u.x; v[4 * c + 3] += u.y;
+        }
+    }
+    const double tot = block_sum_owner<4 * KC>(v, lds);
+    const int t = (int)threadIdx.x;
+    if (t < 4 * KC && q_active(st, c0 + t / 4, k, it, max_it)) partsA[(size_t)((c0 + t / 4) * 4 + (t & 3)) * RED_MAX_BLOCKS + blockIdx.x] = tot;
+}
 
+// (twin: q_close_x_kernel below)
 // the x / P0 half of the step that closes a cycle (close_x_kernel): x += sum_m cx_m (P0, D_1 ..), P0' = dir - sum_m cp_m (P0, D_1 ..),
 // written over slot 0.  No sums: 256-thread workgroups.
 template <int KC>
@@ -303,6 +401,44 @@ __global__ void __launch_bounds__(256) m_close_x_kernel(const DevState *__restri
 #pragma unroll
     for (int c = 0; c < KC; c++) {
         act[c] = m_active(st, c0 + c, k, it);
+        any = any || act[c];
+    }
+    if (!any) return;
+    MV_GRID_STRIDE(i, n) {
+        cplx xv[KC], dv[KC], pc[KC];
+        mv_load<KC>(x, i, k, c0, xv);
+        mv_load<KC>(dir, i, k, c0, dv);
+#pragma unroll
+        for (int c = 0; c < KC; c++) pc[c] = make_double2(0., 0.);
+        for (int q = 0; q < lim; q++) {
+            cplx pj[KC];
+            mv_load<KC>(d.ps[q], i, k, c0, pj);
+#pragma unroll
+            for (int c = 0; c < KC; c++)
+                if (c0 + c < k) {
+                    xv[c] = cadd(xv[c], cmul(lc[c0 + c].cx[q], pj[c]));
+                    pc[c] = csub(pc[c], cmul(coef->cp[c0 + c][q], pj[c]));
+                }
+        }
+#pragma unroll
+        for (int c = 0; c < KC; c++)
+            if (act[c]) {
+                x[i * k + c0 + c] = xv[c];
+                p_out[i * k + c0 + c] = cadd(dv[c], pc[c]);
+            }
+    }
+}
+// ... in the queued solve
+template <int KC>
+__global__ void __launch_bounds__(256) q_close_x_kernel(const DevState *__restrict__ st, int it, const MCoef *__restrict__ coef,
+                                                        const LeanCoef *__restrict__ lc, MPtrs d, int lim, const cplx *dir, cplx *p_out, cplx *x,
+                                                        int64_t n, int k, int max_it) {
+    const int c0 = (int)blockIdx.y * KC;
+    bool act[KC];
+    bool any = false;
+#pragma unroll
+    for (int c = 0; c < KC; c++) {
+        act[c] = q_active(st, c0 + c, k, it, max_it);
         any = any || act[c];
     }
     if (!any) return;
@@ -366,6 +502,170 @@ __global__ void __launch_bounds__(RED_THREADS) m_resid_sub_kernel(cplx *r, const
 }
 
 // ------------------------------------------------------------------------------------------------
+// queued solve: retire / admit single columns of the block (gcr_queue_run).  `mask`: bit j = column j takes part
+// ------------------------------------------------------------------------------------------------
+struct QFields {   // per column: the system's Fields (by value in the kernel arguments)
+    const cplx *b[MV_MAX_K];
+    cplx *x[MV_MAX_K];
+};
+
+// a column's own last step: the bookkeeping of m_finish_kernel, then the column is frozen
+__global__ void __launch_bounds__(RED_THREADS) q_finish_kernel(DevState *st, int it, int max_it, const double *__restrict__ partsR, int nblk,
+                                                               double *__restrict__ hist, int hist_cap) {
+    __shared__ double lds[17];
+    const int j = blockIdx.x;
+    if (st[j].stop_at < st[j].base + it || st[j].base + it != max_it) return;
+    double rr[1];
+    fold_partials<1>(partsR + (size_t)j * RED_MAX_BLOCKS, nblk, RED_MAX_BLOCKS, rr, lds);
+    if (threadIdx.x == 0) {
+        close_step(st + j, it, rr[0], hist + (size_t)j * hist_cap, hist_cap, false);
+        st[j].stop_at = st[j].base + it;
+    }
+}
+
+// retire: x_s = column j of the x block + the column's pending updates (the expression of m_flush_kernel), written to the system's
+// Field.  The block's column is left as it is: nothing reads it again, so the pending updates cannot be applied twice.
+template <int KC>
+__global__ void __launch_bounds__(256) q_retire_kernel(unsigned mask, const DevState *__restrict__ st, const LeanCoef *__restrict__ lc, MPtrs d,
+                                                       const cplx *__restrict__ x, QFields f, int64_t n, int k) {
+    const int c0 = (int)blockIdx.y * KC;
+    if (((mask >> c0) & ((1u << KC) - 1u)) == 0) return;
+    bool ret[KC];
+    int np[KC];
+    int npmax = 0;
+#pragma unroll
+    for (int c = 0; c < KC; c++) {
+        ret[c] = c0 + c < k && ((mask >> (c0 + c)) & 1u);
+        np[c] = ret[c] ? st[c0 + c].npend : 0;
+        if (np[c] > LND) np[c] = LND;
+        npmax = np[c] > npmax ? np[c] : npmax;
+    }
+    MV_GRID_STRIDE(i, n) {
+        cplx xv[KC];
+        mv_load<KC>(x, i, k, c0, xv);
+        for (int q = 0; q < npmax; q++) {
+            cplx pj[KC];
+            mv_load<KC>(d.ps[q], i, k, c0, pj);
+#pragma unroll
+            for (int c = 0; c < KC; c++)
+                if (q < np[c]) xv[c] = cadd(xv[c], cmul(lc[c0 + c].cx[q], pj[c]));
+        }
+#pragma unroll
+        for (int c = 0; c < KC; c++)
+            if (ret[c]) f.x[c0 + c][i] = xv[c];
+    }
+}
+
+// admit, pass 1: the system's x and b into column blockIdx.y of the x and b blocks; without x0 also r0 = P0 = b
+__global__ void __launch_bounds__(RED_THREADS) q_scatter_kernel(unsigned mask, QFields f, cplx *__restrict__ xb, cplx *__restrict__ bb, cplx *__restrict__ r,
+                                                                cplx *__restrict__ p0, int64_t n, int k, int use_x0) {
+    const int j = (int)blockIdx.y;
+    if (!((mask >> j) & 1u)) return;
+    const cplx *bs = f.b[j];
+    const cplx *xs = f.x[j];
+    MV_GRID_STRIDE(i, n) {
+        const cplx bv = bs[i];
+        xb[i * k + j] = xs[i];
+        bb[i * k + j] = bv;
+        if (!use_x0) {
+            r[i * k + j] = bv;
+            p0[i * k + j] = bv;
+        }
+    }
+}
+
+// admit with x0: r0 = P0 = b - A x0 of the admitted columns; t holds A x0 (sub: resid_sub_kernel's expression) or, for a plain
+// Sparse, b - A x0 formed by the apply itself
+__global__ void __launch_bounds__(RED_THREADS) q_r0_kernel(unsigned mask, const cplx *__restrict__ t, const cplx *__restrict__ bb, cplx *__restrict__ r,
+                                                           cplx *__restrict__ p0, int64_t n, int k, int sub) {
+    const int j = (int)blockIdx.y;
+    if (!((mask >> j) & 1u)) return;
+    MV_GRID_STRIDE(i, n) {
+        const cplx v = sub ? csub(bb[i * k + j], t[i * k + j]) : t[i * k + j];
+        r[i * k + j] = v;
+        p0[i * k + j] = v;
+    }
+}
+
+// admit, pass 2: A r0 (the k-wide apply left it in ar) into slot 0 of the admitted columns, and their four start sums — rows per
+// thread and summation tree of m_init_partials_kernel.  A continuing column's sums (the closing step's build wrote them) stay.
+template <int KC>
+__global__ void __launch_bounds__(RED_THREADS) q_admit_kernel(unsigned mask, const cplx *__restrict__ b, const cplx *__restrict__ r,
+                                                              const cplx *__restrict__ ar, cplx *__restrict__ ap0, int64_t n, int k,
+                                                              double *__restrict__ partsN, double *__restrict__ partsR, double *__restrict__ partsA) {
+    __shared__ double lds[6 * KC * 17];
+    const int c0 = (int)blockIdx.y * KC;
+    if (((mask >> c0) & ((1u << KC) - 1u)) == 0) return;   // (uniform over the workgroup)
+    bool adm[KC];
+#pragma unroll
+    for (int c = 0; c < KC; c++) adm[c] = c0 + c < k && ((mask >> (c0 + c)) & 1u);
+    double v[6 * KC];
+#pragma unroll
+    for (int s = 0; s < 6 * KC; s++) v[s] = 0.;
+    MV_GRID_STRIDE(i, n) {
+        cplx bv[KC], rv[KC], av[KC];
+        mv_load<KC>(b, i, k, c0, bv);
+        mv_load<KC>(r, i, k, c0, rv);
+        mv_load<KC>(ar, i, k, c0, av);
+#pragma unroll
+        for (int c = 0; c < KC; c++) {
+            if (adm[c]) ap0[i * k + c0 + c] = av[c];
+            v[6 * c + 4] += bv[c].x * bv[c].x + bv[c].y * bv[c].y;
+            v[6 * c + 5] += rv[c].x * rv[c].x + rv[c].y * rv[c].y;
+            const cplx t = cconj_mul(rv[c], av[c]);
+            v[6 * c] += t.x; v[6 * c + 1] += t.y;
+            const cplx u = cconj_mul(av[c], av[c]);
+            v[6 * c + 2] += u.x; v[6 * c + 3] += u.y;
+        }
+    }
+    const double tot = block_sum_owner<6 * KC>(v, lds);
+    const int t = (int)threadIdx.x;
+    if (t < 6 * KC) {
+        const int col = c0 + t / 6, s = t % 6;
+        if (col < k && ((mask >> col) & 1u)) {
+            if (s < 4) partsA[(size_t)(col * 4 + s) * RED_MAX_BLOCKS + blockIdx.x] = tot;
+            else if (s == 4) partsN[(size_t)col * RED_MAX_BLOCKS + blockIdx.x] = tot;
+            else partsR[(size_t)col * RED_MAX_BLOCKS + blockIdx.x] = tot;
+        }
+    }
+}
+
+// admit, scalar stage (m_reset_kernel + m_init_kernel for one column, one workgroup per column): the column starts at its own step 0
+// when the launches count `global` steps
+__global__ void __launch_bounds__(RED_THREADS) q_admit_state_kernel(unsigned mask, DevState *st, int global, double tol2, const double *__restrict__ partsN,
+                                                                    const double *__restrict__ partsR, int nblk, double *__restrict__ hist, int hist_cap,
+                                                                    LeanCoef *__restrict__ lcs, MCoef *__restrict__ coef) {
+    __shared__ double lds[17];
+    const int j = blockIdx.x;
+    if (!((mask >> j) & 1u)) return;
+    double b[1], r[1];
+    fold_partials<1>(partsN + (size_t)j * RED_MAX_BLOCKS, nblk, RED_MAX_BLOCKS, b, lds);
+    fold_partials<1>(partsR + (size_t)j * RED_MAX_BLOCKS, nblk, RED_MAX_BLOCKS, r, lds);
+    const int t = (int)threadIdx.x;
+    const cplx zero = make_double2(0., 0.);
+    for (int e = t; e < LND * LND; e += RED_THREADS) lcs[j].T[e] = zero;
+    if (t < LND) {
+        lcs[j].t[t] = zero;
+        lcs[j].cx[t] = zero;
+        coef->beta[j][t] = zero;
+        coef->cp[j][t] = zero;
+    }
+    for (int e = 1 + t; e < hist_cap; e += RED_THREADS) hist[(size_t)j * hist_cap + e] = 0.;
+    if (t == 0) {
+        coef->alpha[j] = zero;
+        st[j].stop_at = INT_MAX;
+        st[j].base = -global;
+        st[j].iter = 0;
+        st[j].npend = 0;
+        st[j].bnorm2 = b[0];
+        st[j].rr = r[0];
+        st[j].tol2 = tol2;
+        st[j].closed = 0;
+        hist[(size_t)j * hist_cap] = sqrt(r[0]) / sqrt(b[0]);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host driver
 // ------------------------------------------------------------------------------------------------
 #define MK(kernel, grid, block, ...)                                                         \
@@ -389,6 +689,7 @@ struct MWork {
     int64_t n = -1;
     int k = 0, storage = 0, cap = 0;
     cplx *r = nullptr, *ar = nullptr, *den = nullptr;
+    cplx *xq = nullptr, *bq = nullptr;   // the queued solve's x and b blocks (made by its first call at this n and k)
     std::vector<cplx *> ps, aps;
     DevState *st = nullptr;
     LeanCoef *lc = nullptr;
@@ -400,6 +701,7 @@ struct MWork {
         for (void *p : ptrs) hipFree(p);
         ptrs.clear();
         ps.clear(); aps.clear();
+        xq = bq = nullptr;
         n = -1;
     }
     template <typename T>
@@ -436,6 +738,14 @@ struct MWork {
         if (rc != MGCR_OK) { release(); return rc; }
         n = n_; k = k_; storage = storage_; cap = cap_;
         return MGCR_OK;
+    }
+    int prepare_queue() {
+        if (xq && bq) return MGCR_OK;
+        const size_t ne = (size_t)n * (size_t)k;
+        int rc = alloc(&xq, ne);
+        if (rc == MGCR_OK) rc = alloc(&bq, ne);
+        if (rc != MGCR_OK) release();
+        return rc;
     }
 };
 MWork g_work;
@@ -570,6 +880,156 @@ int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int6
         }
     }
     g_multi_solves++;
+    return resident_check();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Queued batched solve: nsys systems stream through k = min(width, nsys) columns of ONE batched solve.  The schedule — when the
+// host polls, which slots it retires and refills — is queue_plan.h's; this driver carries it out.  Every launch is enqueued by
+// the host in stream order: no kernel waits on another workgroup, on a flag or on the host.
+//   retire (slots found stopped by a poll): q_retire_kernel (pending x updates + unpack into the system's Field), the history
+//     row and the iteration count go to the system's entries;
+//   admit (phase 0 of the cycle, `global` steps launched): q_scatter_kernel; with x0 the k-wide apply into the free `ar` block and
+//     q_r0_kernel; the k-wide apply of r into `ar` (column j has the bits of the single apply: Rule 1) and q_admit_kernel, which
+//     copies the admitted columns into slot 0 while it takes their four start sums; q_admit_state_kernel (base = -global).
+//     Per admission point: 2 (3 with x0) passes over the block + 1 (2) k-wide applies, whatever the number of columns admitted.
+//   step: gcr_multi_run's, except that a column at its OWN last step takes q_finish_kernel and is left out of what follows.
+// ks != nullptr: system s is (1 - ks[s] D) x = b, D = A a plain Sparse; the slots' shifts live in a MultiDiracOp made here, whose
+// values travel in the kernel arguments of every apply (KCols): admitting system s into slot j sets entry j.
+// ------------------------------------------------------------------------------------------------
+static int64_t g_queue_solves = 0, g_queue_admissions = 0, g_queue_steps = 0;
+int64_t gcr_queue_stat(int which) { return which == 0 ? g_queue_solves : which == 1 ? g_queue_admissions : g_queue_steps; }
+
+int gcr_queue_run(Op *A0, const mgcr_gcr_param &p, int width, int nsys, const cplx *const *rhs, cplx *const *x, const cplx *ks, int64_t n,
+                  double *hist, int hist_cap, int *n_iter, int *converged) {
+    Context &c = ctx();
+    const int restart = p.restart;
+    QueuePlan qp(width < nsys ? width : nsys, nsys, restart, p.max_iter, p.check_every);
+    const int storage = qp.storage, max_it = qp.max_it, k = qp.width;
+    MGCR_CHECK(storage <= LND, MGCR_ERR_UNSUPPORTED, "batched GCR: restart cycles of at most %d steps (the lean cycle) are supported", LND);
+    const int cap = max_it + 1;
+    const int g = red_grid(n);
+    const int kc = mv_group(k), groups = (k + kc - 1) / kc;
+    const int gx = red_grid(n) * 4 > 2048 ? 2048 : red_grid(n) * 4;   // the 256-thread kernels (m_close_x_kernel, m_flush_kernel)
+    MWork &wk = g_work;
+    MGCR_TRY(wk.prepare(n, k, storage, cap));
+    MGCR_TRY(wk.prepare_queue());
+    cplx *r = wk.r, *ar = wk.ar, *den = wk.den, *xb = wk.xq, *bb = wk.bq;
+    std::vector<cplx *> &ps = wk.ps, &aps = wk.aps;
+    DevState *st = wk.st;
+    LeanCoef *lc = wk.lc;
+    MCoef *coef = wk.coef;
+    double *partsA = wk.partsA, *partsR = wk.partsR, *partsN = wk.partsN, *partsB = wk.partsB, *dhist = wk.dhist;
+    MGCR_HIP(hipMemsetAsync(dhist, 0, sizeof(double) * (size_t)k * cap, c.stream));
+    MGCR_HIP(hipMemsetAsync(lc, 0, sizeof(LeanCoef) * MV_MAX_K, c.stream));
+    MGCR_HIP(hipMemsetAsync(coef, 0, sizeof(MCoef), c.stream));
+
+    Op shifted;   // ks: the slots' MultiDiracOp (borrows A0; lives for this call)
+    Op *A = A0;
+    if (ks) {
+        shifted.kind = OP_DIRAC_MULTI;
+        shifted.dim = A0->dim;
+        shifted.nrow = A0->nrow;
+        shifted.base = A0;
+        shifted.nk = k;
+        for (int j = 0; j < MV_MAX_K; j++) shifted.ks[j] = make_double2(j < k ? 1. : 0., 0.);
+        A = &shifted;
+    }
+    MPtrs d;
+    for (int j = 0; j < LND; j++) { d.ps[j] = ps[(size_t)(j < storage ? j : 0)]; d.aps[j] = aps[(size_t)(j < storage ? j : 0)]; }
+    int64_t reach = 0;
+    {
+        const Op *b0 = op_matrix(A);
+        if (b0 && b0->kind == OP_CSR) reach = b0->csr.reach;
+    }
+    const RowMap rmap = make_row_map(n, g, reach);
+    const bool residual_form = A->kind == OP_CSR && A->csr.nrow == n && A->csr.ncol == n;   // b - A x0 in one pass (op_residual_raw)
+
+    MK(m_reset_kernel, dim3(1), MV_MAX_K, st, p.tol * p.tol, 0);   // every slot empty
+    std::vector<DevState> hs((size_t)MV_MAX_K);
+    std::vector<double> row;
+    QFields f{};
+    int64_t admissions0 = qp.admissions;
+    for (;;) {
+        if (qp.poll_due()) {
+            MGCR_HIP(hipMemcpyAsync(hs.data(), st, sizeof(DevState) * MV_MAX_K, hipMemcpyDeviceToHost, c.stream));
+            MGCR_HIP(hipStreamSynchronize(c.stream));
+            qp.polled();
+            unsigned mask = 0;
+            for (int j = 0; j < k; j++)
+                if (qp.occupied(j) && hs[(size_t)j].stop_at != INT_MAX) mask |= 1u << j;
+            if (mask) {
+                MK_KC(q_retire_kernel, gx, 256, mask, (const DevState *)st, (const LeanCoef *)lc, d, (const cplx *)xb, f, n, k);
+                for (int j = 0; j < k; j++) {
+                    if (!((mask >> j) & 1u)) continue;
+                    const int s = qp.sys[j], it = hs[(size_t)j].iter;
+                    if (n_iter) n_iter[s] = it;
+                    if (converged) converged[s] = it == p.max_iter ? 0 : 1;
+                    if ((hist && hist_cap > 0) || p.verbose) {   // (the row is final: the column stopped before the poll's synchronise)
+                        row.resize((size_t)cap);
+                        MGCR_HIP(hipMemcpy(row.data(), dhist + (size_t)j * cap, sizeof(double) * (size_t)(it + 1), hipMemcpyDeviceToHost));
+                        if (hist)
+                            for (int i = 0; i <= it && i < hist_cap; i++) hist[(size_t)s * hist_cap + i] = row[(size_t)i];
+                        if (p.verbose)
+                            for (int i = 0; i <= it; i++) printf("[%d] Step %d residual norm = %.10e\n", s, i, row[(size_t)i]);
+                    }
+                    qp.retire(j);
+                }
+            }
+        }
+        int slots[QP_MAX_WIDTH], systems[QP_MAX_WIDTH];
+        const int m = qp.admit(slots, systems);
+        if (m > 0) {
+            unsigned mask = 0;
+            for (int i = 0; i < m; i++) {
+                const int j = slots[i], s = systems[i];
+                mask |= 1u << j;
+                f.b[j] = rhs[s];
+                f.x[j] = x[s];
+                if (ks) shifted.ks[j] = ks[s];
+            }
+            const dim3 cols((unsigned)g, (unsigned)k);
+            MK(q_scatter_kernel, cols, RED_THREADS, mask, f, xb, bb, r, ps[0], n, k, p.use_x0 ? 1 : 0);
+            if (p.use_x0) {
+                if (residual_form) MGCR_TRY(op_apply_multi_raw(A, xb, ar, n, k, bb));
+                else MGCR_TRY(op_apply_multi_raw(A, xb, ar, n, k));
+                MK(q_r0_kernel, cols, RED_THREADS, mask, (const cplx *)ar, (const cplx *)bb, r, ps[0], n, k, residual_form ? 0 : 1);
+            }
+            MGCR_TRY(op_apply_multi_raw(A, r, ar, n, k));
+            MK_KC(q_admit_kernel, g, RED_THREADS, mask, (const cplx *)bb, (const cplx *)r, (const cplx *)ar, aps[0], n, k, partsN, partsR, partsA);
+            MK(q_admit_state_kernel, dim3((unsigned)k), RED_THREADS, mask, st, qp.global, p.tol * p.tol, (const double *)partsN, (const double *)partsR, g,
+               dhist, cap, lc, coef);
+        }
+        if (qp.finished()) break;
+        MGCR_CHECK(qp.any_running(), MGCR_ERR_HIP, "queued GCR: a column is still marked as running after its last step");
+        const QueueStep s = qp.step();
+        g_queue_steps++;
+        const int it = s.it, lim = s.lim;
+        const cplx *rin = s.cur >= 1 ? ps[(size_t)s.cur] : r;
+        cplx *dslot = s.nxt >= 1 ? ps[(size_t)s.nxt] : r;
+        MK(m_alpha_kernel, dim3((unsigned)k), RED_THREADS, st, it, (const double *)partsA, g, den, s.cur, lc, coef);
+        MK_KC(m_xr_kernel, g, RED_THREADS, (const DevState *)st, it, (const MCoef *)coef, (const cplx *)aps[(size_t)s.cur], rin, dslot, n, k, partsR);
+        if (s.any_last) MK(q_finish_kernel, dim3((unsigned)k), RED_THREADS, st, it, max_it, (const double *)partsR, g, dhist, cap);
+        if (s.all_last) continue;
+        MGCR_TRY(op_apply_multi_raw(A, dslot, ar, n, k));
+        {
+            constexpr int NDT = 2;
+            const dim3 grid((unsigned)g, (unsigned)groups, (unsigned)((lim + NDT - 1) / NDT));
+            if (kc == 1) MK((m_dot_kernel<1, NDT>), grid, RED_THREADS, (const cplx *)ar, d, lim, n, k, rmap, partsB);
+            else if (kc == 2) MK((m_dot_kernel<2, NDT>), grid, RED_THREADS, (const cplx *)ar, d, lim, n, k, rmap, partsB);
+            else MK((m_dot_kernel<4, NDT>), grid, RED_THREADS, (const cplx *)ar, d, lim, n, k, rmap, partsB);
+        }
+        MK(q_coef_kernel, dim3((unsigned)k), RED_THREADS, st, it, (const double *)partsB, (const double *)partsR, g, dhist, cap, (const cplx *)den, lc,
+           coef, lim, s.closing ? 1 : 0, max_it);
+        if (s.closing)
+            MK_KC(q_close_x_kernel, gx, 256, (const DevState *)st, it, (const MCoef *)coef, (const LeanCoef *)lc, d, lim, (const cplx *)dslot, ps[0], xb, n,
+                  k, max_it);
+        MK_KC(q_build_kernel, g, RED_THREADS, (const DevState *)st, it, (const MCoef *)coef, d, lim, (const cplx *)dslot, (const cplx *)ar,
+              aps[(size_t)s.nxt], n, k, partsA, max_it);
+    }
+    MGCR_HIP(hipStreamSynchronize(c.stream));   // the last retirement's writes to the systems' Fields
+    g_queue_admissions += qp.admissions - admissions0;
+    g_queue_solves++;
     return resident_check();
 }
 

@@ -403,6 +403,11 @@ int op_apply_multi_raw(Op *op, const cplx *x, cplx *y, int64_t n, int k, const c
 int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int64_t n, int k, double *hist, int hist_cap, int *n_iter,
                   int *converged);
 int64_t gcr_multi_solve_count();
+// nsys systems through min(width, nsys) columns of one batched solve (queue_plan.h has the schedule); ks != nullptr: system s is
+// (1 - ks[s] A) x = rhs[s] with A a plain Sparse
+int gcr_queue_run(Op *A, const mgcr_gcr_param &p, int width, int nsys, const cplx *const *rhs, cplx *const *x, const cplx *ks, int64_t n,
+                  double *hist, int hist_cap, int *n_iter, int *converged);
+int64_t gcr_queue_stat(int which);   // 0: solves completed, 1: systems admitted after step 0, 2: lockstep steps launched
 void multi_release();   // frees the batched solve's cached work storage and the block BLAS-1 buffers (mgcr_finalize)
 
 // ---- gcr_small.hip ---------------------------------------------------------------------------

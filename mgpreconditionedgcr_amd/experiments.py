@@ -4,6 +4,7 @@ either side of the hot path — plus the MatrixMarket 
 
     python -m mgpreconditionedgcr_amd.experiments kcritical  --dir data/sample_matrix
     python -m mgpreconditionedgcr_amd.experiments kcritical  --dir data/sample_matrix --batched
+    python -m mgpreconditionedgcr_amd.experiments kcritical  --dir data/sample_matrix --queue 2
     python -m mgpreconditionedgcr_amd.experiments mg_property --dir data/sample_matrix
     python -m mgpreconditionedgcr_amd.experiments hermiticity --dir data/sample_matrix
     python -m mgpreconditionedgcr_amd.experiments parse  conf.mtx parsed.txt
@@ -101,6 +102,25 @@ def test_kcritical_batched(D, dims, k_c, k_start, steps=5, restart=10, max_iter=
     return out
 
 
+def test_kcritical_queue(D, dims, k_c, k_start, steps=5, restart=10, max_iter=50000, tol=1e-13, seed=42, width=4):
+    """test_kcritical as ONE queued solve: the ladder of k (any length) streams through `width` columns of a batched solve, a column
+    whose k has stopped takes the next waiting k at the next boundary of the restart cycle (GCR.solve_queue), so a value near k_c
+    that runs long holds one column only.  Prints the same lines and returns the same tuples: system j has the bits of the single
+    solve with DiracOp(D, k_j)."""
+    field = Field(dims).fill_rhs(seed)
+    step = (k_c - k_start) / steps
+    ks = [k_start + step * i for i in range(steps)]
+    sols = [Field(dims).set_zero() for _ in ks]
+    gcr = GCR(D, GCR_Param(0, restart, max_iter, tol, False, check_every=50))
+    gcr.solve_queue([field] * steps, sols, width=width, ks=ks)
+    out = []
+    for j, k in enumerate(ks):
+        print("k = %f: %s after %d steps, residual %.10e" % (k, "converged" if gcr.last_converged[j] else "did not converge",
+                                                             gcr.last_iterations[j], gcr.last_history[j][-1]))
+        out.append((k, gcr.last_iterations[j], gcr.last_converged[j], float(gcr.last_history[j][-1])))
+    return out
+
+
 def test_MG_property(Dirac, dims, subblock=2, n_eigen=2, null_vectors=None, seed=42):
     """src/main.cpp:877-918 and MG::test_MG (src/MG.h:432-512): projector identities
     (R P R = R, P R P R = P R) and coarse-operator consistency P R A v = P A_c R v on span(P)."""
@@ -133,6 +153,7 @@ def main():
     ap.add_argument("--dir", default="../../data/sample_matrix/")
     ap.add_argument("--file", default="4x4parsed.txt")
     ap.add_argument("--batched", action="store_true", help="kcritical: every k as one column of ONE batched solve")
+    ap.add_argument("--queue", type=int, default=0, metavar="WIDTH", help="kcritical: the ladder through WIDTH columns of one queued solve")
     a = ap.parse_args()
     if a.what == "parse":
         parse_data(a.args[0], a.args[1])
@@ -143,7 +164,11 @@ def main():
         test_hermiticity(D, dims)
     elif a.what == "kcritical":
         kc = K_CRITICAL.get(a.file, 0.20611)
-        (test_kcritical_batched if a.batched else test_kcritical)(D, dims, kc, kc - 0.00611 if a.file.startswith("4x4") else 0.174)
+        k0 = kc - 0.00611 if a.file.startswith("4x4") else 0.174
+        if a.queue:
+            test_kcritical_queue(D, dims, kc, k0, width=a.queue)
+        else:
+            (test_kcritical_batched if a.batched else test_kcritical)(D, dims, kc, k0)
     else:
         test_MG_property(DiracOp(D, 0.1), dims)
 

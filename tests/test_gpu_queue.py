@@ -1,0 +1,255 @@
+"""The queued batched GCR on the GPU (mgcr_gcr_solve_queue, csrc/gcr_multi.hip): any number of systems through `width` columns of one
+batched solve, a column that has stopped refilled at the next boundary of the restart cycle.  Every comparison is bit for bit
+(np.array_equal) with mgcr_gcr_solve on the system alone — history, iteration count, convergence flag, x — the rule include/mgcr.h
+states; the single solves are computed once per module and shared.  The number of lockstep steps is compared with the schedule's
+model (tests/queue_cases.py; the C++ schedule itself is checked on the CPU in tests/test_queue_plan.py)."""
+import os
+
+import numpy as np
+import pytest
+
+from mgpreconditionedgcr_amd import (DiracOp, Field, GCR, GCR_Param, HierarchicalSparse, MgcrError, MultiDiracOp, MultiField, Sparse,
+                                     experiments, problems, read_data, set_option, stat)
+from tests import kscan_cases as kc
+from tests import queue_cases as qc
+
+pytestmark = pytest.mark.gpu
+
+SCAN = (0, kc.SCAN_RESTART, kc.SCAN_MAX_ITER, kc.SCAN_TOL)
+
+
+@pytest.fixture(scope="module")
+def sample(sample_matrix_path):
+    return read_data(os.path.basename(sample_matrix_path), directory=os.path.dirname(sample_matrix_path))
+
+
+_operators = {}
+
+
+def poisson(n, patterns=True):
+    if (n, patterns) not in _operators:
+        prev = set_option("pattern_storage", 1 if patterns else 0)
+        try:
+            _operators[(n, patterns)] = Sparse(*problems.poisson3d_csr(n))
+        finally:
+            set_option("pattern_storage", prev)
+    return _operators[(n, patterns)], n ** 3
+
+
+def param(args, use_x0=False, check_every=0):
+    return GCR_Param(*args, False, use_x0=use_x0, check_every=check_every)
+
+
+_singles = {}
+
+
+def single(key, A, args, b, x0=None, use_x0=False):
+    """(iterations, converged, history, x) of mgcr_gcr_solve on the system alone; computed once per key and never changed"""
+    if key not in _singles:
+        n = A.get_dim()
+        x = Field((n,), x0) if x0 is not None else Field((n,)).set_zero()
+        g = GCR(A, param(args, use_x0))
+        g.solve(Field((n,), b), x)
+        res = (g.last_iterations, g.last_converged, g.last_history.copy(), x.to_numpy())
+        for a in res[2:]:
+            a.setflags(write=False)
+        _singles[key] = res
+    return _singles[key]
+
+
+def check_queue(A, args, bs, refs, width, ks=None, x0s=None, use_x0=False, check_every=0):
+    """runs the queue and compares every system with its single solve; returns (queue_steps, queue_admissions) of the call"""
+    n = A.get_dim()
+    fields = {}
+    rhs = [fields.setdefault(id(b), Field((n,), b)) for b in bs]       # one Field per distinct right-hand side: handles repeat
+    xs = [Field((n,), x0s[s]) if x0s is not None else Field((n,)).set_zero() for s in range(len(bs))]
+    g = GCR(A, param(args, use_x0, check_every))
+    before = stat("queue_steps"), stat("queue_admissions"), stat("queue_solves"), stat("multi_solves")
+    g.solve_queue(rhs, xs, width=width, ks=ks)
+    after = stat("queue_steps"), stat("queue_admissions"), stat("queue_solves"), stat("multi_solves")
+    assert after[2] == before[2] + 1 and after[3] == before[3]
+    for s, (it, conv, hist, x) in enumerate(refs):
+        assert g.last_iterations[s] == it, (s, g.last_iterations, [r[0] for r in refs])
+        assert g.last_converged[s] == conv, s
+        assert np.array_equal(g.last_history[s], hist), s
+        assert np.array_equal(xs[s].to_numpy(), x), s
+    return after[0] - before[0], after[1] - before[1]
+
+
+def scan_singles(sample, ks, args=SCAN, x0s=None, use_x0=False, tag=""):
+    assert sample.xr_fuse_kind() in (0, 1)          # the premise of the rule (include/mgcr.h)
+    b = problems.rhs_grid(sample.get_dim(), kc.SCAN_RHS_SEED)
+    return b, [single(("scan", k, args, use_x0, tag, s if x0s is not None else -1), DiracOp(sample, k), args, b,
+                      x0s[s] if x0s is not None else None, use_x0) for s, k in enumerate(ks)]
+
+
+# ---- 1, 2: the scan; the number of lockstep steps ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("width", [1, 2, 3, 4, 6, 8])
+def test_scan_in_the_given_order(sample, width):
+    b, refs = scan_singles(sample, kc.SCAN_KS)
+    its = [r[0] for r in refs]
+    assert len(set(its)) >= 4 and its[-1] == kc.SCAN_MAX_ITER, its
+    steps, admissions = check_queue(sample, SCAN, [b] * 6, refs, width, ks=kc.SCAN_KS, check_every=5)
+    assert steps == qc.lockstep_steps(its, width, 5), (steps, its)
+    assert admissions == 6 - min(width, 6)
+
+
+def test_scan_longest_first(sample):
+    b, refs = scan_singles(sample, qc.LONGEST_FIRST_KS)
+    its = [r[0] for r in refs]
+    steps, admissions = check_queue(sample, SCAN, [b] * 6, refs, 2, ks=qc.LONGEST_FIRST_KS, check_every=5)
+    assert steps == qc.lockstep_steps(its, 2, 5), (steps, its)      # 635 with the oracle's counts; waiting for the whole group: 850
+    assert steps < qc.wait_for_group_steps(its, 2, 5) and admissions == 4
+
+
+# ---- 3: check_every ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("check_every", [0, 1, 7])
+def test_check_every_does_not_change_the_results(sample, check_every):
+    b, refs = scan_singles(sample, qc.LONGEST_FIRST_KS)
+    check_queue(sample, SCAN, [b] * 6, refs, 2, ks=qc.LONGEST_FIRST_KS, check_every=check_every)
+
+
+# ---- 4: a column's own last step -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("max_iter", [20, 23, 3])       # the last step closes a cycle / falls in mid-cycle / the cycle never closes
+def test_every_system_runs_to_max_iter(sample, max_iter):
+    args = (0, 5, max_iter, 0.0)
+    ks = kc.SCAN_KS[:5]
+    b, refs = scan_singles(sample, ks, args)
+    assert [r[0] for r in refs] == [max_iter] * 5 and not any(r[1] for r in refs)
+    steps, admissions = check_queue(sample, args, [b] * 5, refs, 2, ks=ks)
+    assert admissions == 3
+    if max_iter == 3:
+        assert steps == 9                               # three groups, each admitted at once when the one before has ended
+    A, N = poisson(12)
+    assert A.xr_fuse_kind() in (0, 1)
+    bs = [problems.rhs_grid(N, 1 + s) for s in range(5)]
+    refs = [single(("p12", args, s), A, args, bs[s]) for s in range(5)]
+    assert [r[0] for r in refs] == [max_iter] * 5
+    check_queue(A, args, bs, refs, 2)
+
+
+# ---- 5: some converge, some do not ---------------------------------------------------------------------------------------------------
+def eigenvector(n, a, b, c):
+    s = [np.sin(np.pi * m * np.arange(1, n + 1) / (n + 1)) for m in (a, b, c)]
+    return (s[0][:, None, None] * s[1][None, :, None] * s[2][None, None, :]).reshape(-1).astype(np.complex128)
+
+
+def test_mixed_stops():
+    n = 16
+    A, N = poisson(n)
+    assert A.xr_fuse_kind() in (0, 1)
+    args = (0, 3, 50, 1e-8)
+    e = lambda *m: eigenvector(n, *m)                   # a sum of m eigenvectors is solved in m steps; a grid of random numbers is not in 50
+    bs = [e(1, 1, 1), problems.rhs_grid(N, 1), e(1, 1, 1) + e(2, 1, 3), problems.rhs_grid(N, 2), e(1, 2, 1) + e(3, 3, 3) + e(5, 1, 2),
+          e(1, 1, 1) + 1e-3 * problems.rhs_grid(N, 3), e(2, 2, 2) + e(4, 1, 1) + e(1, 5, 2) + e(6, 6, 1) + e(3, 1, 7)]
+    refs = [single(("mixed", s), A, args, bs[s]) for s in range(7)]
+    its = [r[0] for r in refs]
+    assert len(set(its)) >= 2 and 50 in its and min(its) < 50, its
+    check_queue(A, args, bs, refs, 3)
+
+
+# ---- 6: x0 -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("use_x0", [True, False])
+def test_nonzero_x_on_entry(sample, use_x0):
+    n = sample.get_dim()
+    x0s = [0.01 * problems.rhs_grid(n, 7 + s) for s in range(6)]
+    b, refs = scan_singles(sample, kc.SCAN_KS, x0s=x0s, use_x0=use_x0, tag="x0")
+    check_queue(sample, SCAN, [b] * 6, refs, 3, ks=kc.SCAN_KS, x0s=x0s, use_x0=use_x0)
+    A, N = poisson(12)                                 # a plain Sparse without shifts: b - A x0 in one pass
+    args = (0, 5, 60, 1e-9)
+    bs = [problems.rhs_grid(N, 1 + s) for s in range(5)]
+    x0s = [0.01 * problems.rhs_grid(N, 11 + s) for s in range(5)]
+    refs = [single(("p12x0", use_x0, s), A, args, bs[s], x0s[s], use_x0) for s in range(5)]
+    check_queue(A, args, bs, refs, 2, x0s=x0s, use_x0=use_x0)
+
+
+# ---- 7: the other operator kinds, without shifts -------------------------------------------------------------------------------------
+def test_dirac_operator(sample):
+    n = sample.get_dim()
+    A = DiracOp(sample, 0.15)
+    args = (0, 5, 300, 1e-10)
+    bs = [problems.rhs_grid(n, 1 + s) for s in range(5)]
+    refs = [single(("dirac", s), A, args, bs[s]) for s in range(5)]
+    check_queue(A, args, bs, refs, 2)
+
+
+def test_block_csr():
+    nb, bs_ = 600, 20
+    H = HierarchicalSparse(nb, nb, *problems.unstructured_blocks(nb, bs_))
+    args = (0, 5, 200, 1e-10)
+    bs = [problems.rhs_grid(nb * bs_, 1 + s) for s in range(5)]
+    refs = [single(("bcsr", s), H, args, bs[s]) for s in range(5)]
+    check_queue(H, args, bs, refs, 2)
+
+
+def test_slab_sparse():
+    A, N = poisson(16, patterns=False)
+    assert A.storage_format()[0] == 0 and A.xr_fuse_kind() in (0, 1)
+    args = (0, 5, 60, 1e-6)
+    bs = [problems.rhs_grid(N, 1 + s) for s in range(5)]
+    refs = [single(("slab", s), A, args, bs[s]) for s in range(5)]
+    check_queue(A, args, bs, refs, 2)
+
+
+# ---- 8: the work storage is kept and shared ------------------------------------------------------------------------------------------
+def test_reuse_and_a_batched_solve_in_between(sample):
+    n = sample.get_dim()
+    b, refs = scan_singles(sample, qc.LONGEST_FIRST_KS)
+    check_queue(sample, SCAN, [b] * 6, refs, 2, ks=qc.LONGEST_FIRST_KS)
+    check_queue(sample, SCAN, [b] * 6, refs, 2, ks=qc.LONGEST_FIRST_KS)
+    g = GCR(MultiDiracOp(sample, qc.LONGEST_FIRST_KS[:2]), param(SCAN))        # the same n, width and cycle length: the same storage
+    X = MultiField((n,), 2).set_zero()
+    g.solve_multi(MultiField.from_fields([Field((n,), b)] * 2), X)
+    for j in range(2):
+        assert g.last_iterations[j] == refs[j][0] and np.array_equal(g.last_history[j], refs[j][2]) and np.array_equal(X.to_numpy()[j], refs[j][3])
+    check_queue(sample, SCAN, [b] * 6, refs, 2, ks=qc.LONGEST_FIRST_KS)
+
+
+# ---- 9: errors -----------------------------------------------------------------------------------------------------------------------
+def test_errors_leave_every_x_untouched(sample):
+    n = sample.get_dim()
+    bs = [Field((n,), problems.rhs_grid(n, 1 + s)) for s in range(3)]
+    xs = [Field((n,), problems.rhs_grid(n, 20 + s)) for s in range(3)]
+    ref = [x.to_numpy() for x in xs] + [b.to_numpy() for b in bs]
+    A = DiracOp(sample, 0.1)
+    prm = GCR_Param(0, 5, 10, 1e-8, False)
+    ks = [0.05, 0.1, 0.15]
+
+    def code(fn):
+        with pytest.raises(MgcrError) as e:
+            fn()
+        return e.value.code
+
+    before = stat("queue_solves"), stat("queue_steps")
+    assert code(lambda: GCR(A, prm).solve_queue(bs, xs, width=0)) == 1
+    assert code(lambda: GCR(A, prm).solve_queue(bs, xs, width=17)) == 1
+    assert code(lambda: GCR(A, prm).solve_queue([], [], width=2)) == 1                                   # nsys = 0
+    assert code(lambda: GCR(A, prm).solve_queue(bs, [xs[0], xs[1], xs[0]], width=2)) == 1                # a repeated x
+    assert code(lambda: GCR(A, prm).solve_queue(bs, [xs[0], bs[2], xs[2]], width=2)) == 1                # an x among the right-hand sides
+    assert code(lambda: GCR(A, prm).solve_queue(bs, xs[:2] + [Field((n + 1,))], width=2)) == 1           # a size mismatch
+    assert code(lambda: GCR(MultiDiracOp(sample, ks), prm).solve_queue(bs, xs, width=3)) == 7            # a MultiDiracOp
+    assert code(lambda: GCR(A, prm).solve_queue(bs, xs, width=2, ks=ks)) == 1                            # shifts on a DiracOp
+    assert code(lambda: GCR(sample, prm).solve_queue(bs, xs, width=2, ks=[0.05, 0.0, 0.15])) == 1        # a zero k
+    assert code(lambda: GCR(A, GCR_Param(4, 0, 10, 1e-8, False)).solve_queue(bs, xs, width=2)) == 7      # truncation mode
+    assert code(lambda: GCR(A, GCR_Param(0, 0, 10, 1e-8, False)).solve_queue(bs, xs, width=2)) == 7      # full mode
+    assert code(lambda: GCR(A, GCR_Param(0, 17, 100, 1e-8, False)).solve_queue(bs, xs, width=2)) == 7    # a cycle longer than 16
+    inner = GCR(A, GCR_Param(0, 5, 2, 1e-8, False))
+    assert code(lambda: GCR(A, GCR_Param(0, 5, 10, 1e-8, False, solver_l=inner)).solve_queue(bs, xs, width=2)) == 7
+    assert code(lambda: GCR(A, GCR_Param(0, 5, 10, 1e-8, False, solver_r=inner, flexible=True)).solve_queue(bs, xs, width=2)) == 7
+    assert code(lambda: GCR(inner, prm).solve_queue(bs, xs, width=2)) == 7                               # a GCR object as operator
+    assert all(np.array_equal(f.to_numpy(), r) for f, r in zip(xs + bs, ref))
+    assert (stat("queue_solves"), stat("queue_steps")) == before
+    GCR(A, prm).solve_queue(bs, xs, width=8)                                                             # width > nsys is allowed
+    assert stat("queue_solves") == before[0] + 1 and stat("queue_steps") == before[1] + 10
+
+
+# ---- 10: the experiment --------------------------------------------------------------------------------------------------------------
+def test_kcritical_queue_equals_kcritical(sample, capsys):
+    kw = dict(steps=4, max_iter=400, tol=1e-10)
+    one = experiments.test_kcritical(sample, experiments.DIMS_4x4, 0.20611, 0.05, **kw)
+    printed_one = capsys.readouterr().out
+    queued = experiments.test_kcritical_queue(sample, experiments.DIMS_4x4, 0.20611, 0.05, width=2, **kw)
+    printed_queued = capsys.readouterr().out
+    assert len(queued) == 4 and queued == one
+    assert printed_queued == printed_one and printed_one.count("\n") == 4
+    assert len({t[1] for t in one}) > 1

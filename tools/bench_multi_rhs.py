@@ -15,6 +15,13 @@ the library stream (mgcr_timer_*, mgcr_bench_op_apply, mgcr_bench_op_apply_multi
   5. (--parts uniform --lib SO: one side; --parts uniform_ab --parent-lib SO: both sides, alternating, one process per timing)
      apply_multi of a plain DiracOp at k = 8 on (a) and (b) with the library of the parent commit against this one, next to the spread
      of parent against parent from the same call.  Next to each measured ratio stands the
+  6. (--parts queue, not in the default set; profiles/queue.json with --out) the queued solve (GCR.solve_queue): the six-value scan on
+     (a) as six DiracOp solves, as one solve_multi at k = 6 and as solve_queue at W = 2, 3, 4 in the given order and longest first — wall
+     time, lockstep steps (mgcr_stat "queue_steps"), microseconds per lockstep step — next to the schedule's model; and on (b) six
+     shifts 0.010 .. 0.050 capped at 40 steps with ONE tolerance (a call takes one) taken from a first pass, between the third and
+     the fourth column's final residual, so that the stops differ.  --parts kscan_ab --parent-lib SO:
+     the existing batched solve (the scan and the equal-length k = 8 solve on (a), --parts kscan_side) with the parent commit's
+     library against this one, alternating processes, next to the parent's own spread.
 byte-model ratio k (M + 2 V) / (M + 2 k V), M = matrix bytes, V = 16 n; for the solve, bytes per step from the terms of
 bench.py's gcr_phase_model, averaged over a GCR(5) cycle (lim = 1 .. 5 stored directions): the single solve's one-launch steps
 move M + (2 lim + 4) V in a cycle and M + (3 R + 5) V in the step that closes it (11.2 V on average); the batched solve moves,
@@ -182,6 +189,130 @@ def uniform_ab(sample, parent_lib, runs):
     return out
 
 
+from tests.queue_cases import LONGEST_FIRST_KS as LONGEST_FIRST, lockstep_steps  # noqa: E402  (the schedule's model the tests assert)
+
+
+def queue_sides(D, b, ks, args, widths, runs, orders):
+    """interleaved: the single solves, one solve_multi over all of ks, solve_queue per (order, W); ms, iterations, lockstep steps"""
+    from mgpreconditionedgcr_amd import MultiDiracOp, stat
+    n, k = D.get_dim(), len(ks)
+    prm = GCR_Param(*args, False, check_every=args[1])
+    singles = [GCR(DiracOp(D, kj), prm) for kj in ks]
+    gm, gq = GCR(MultiDiracOp(D, ks), prm), GCR(D, prm)
+    x, X, xs = Field((n,)), MultiField((n,), k), [Field((n,)) for _ in ks]
+    R = MultiField.from_fields([b] * k)
+    for j in range(k):
+        singles[j].solve(b, x.set_zero())
+    its = [g.last_iterations for g in singles]
+    gm.solve_multi(R, X.set_zero())
+    assert list(gm.last_iterations) == its
+    conf = [(name, order, W) for name, order in orders for W in widths]
+    steps = {}
+    for name, order, W in conf:
+        for f in xs:
+            f.set_zero()
+        before = stat("queue_steps")
+        gq.solve_queue([b] * k, xs, width=W, ks=order)
+        steps[(name, W)] = stat("queue_steps") - before
+        assert sorted(gq.last_iterations) == sorted(its)
+    t_single, t_multi, t_queue = [], [], {c[0::2]: [] for c in conf}
+    for _ in range(runs):
+        t = 0.0
+        for j in range(k):
+            x.set_zero()
+            t += timer(lambda: singles[j].solve(b, x))
+        t_single.append(t)
+        X.set_zero()
+        t_multi.append(timer(lambda: gm.solve_multi(R, X)))
+        for name, order, W in conf:
+            for f in xs:
+                f.set_zero()
+            t_queue[(name, W)].append(timer(lambda: gq.solve_queue([b] * k, xs, width=W, ks=order)))
+    s, m = stats(t_single), stats(t_multi)
+    rec = {"ks": [str(v) for v in ks], "restart": args[1], "max_iter": args[2], "tol": args[3], "iterations": its, "sum_iterations": sum(its),
+           "singles_ms": s, "single_us_per_iteration": 1e3 * s["median"] / sum(its),
+           "batched_ms": m, "batched_lockstep_steps": max(its), "batched_us_per_lockstep_step": 1e3 * m["median"] / max(its),
+           "singles_over_batched": s["median"] / m["median"], "queue": []}
+    for name, order, W in conf:
+        q = stats(t_queue[(name, W)])
+        order_its = [its[ks.index(v)] for v in order]
+        rec["queue"].append({"order": name, "width": W, "ms": q, "lockstep_steps": steps[(name, W)],
+                             "model_lockstep_steps": lockstep_steps(order_its, W, args[1]),
+                             "us_per_lockstep_step": 1e3 * q["median"] / steps[(name, W)],
+                             "singles_over_queue": s["median"] / q["median"], "batched_over_queue": m["median"] / q["median"],
+                             "ranges_overlap_singles": not (q["max"] < s["min"] or s["max"] < q["min"]),
+                             "ranges_overlap_batched": not (q["max"] < m["min"] or m["max"] < q["min"])})
+    return rec
+
+
+def queue_part(sample, runs, large=True):
+    out = {}
+    D = read_data(os.path.basename(sample), directory=os.path.dirname(os.path.abspath(sample)))
+    n = D.get_dim()
+    out["sample"] = dict(rows=n, **queue_sides(D, Field((n,), problems.rhs_grid(n, 1)), SCAN_KS, SCAN_ARGS, (2, 3, 4), runs,
+                                               [("given", SCAN_KS), ("longest_first", LONGEST_FIRST)]))
+    del D
+    if large:      # the matrix stream dominates a step: 2^20 rows
+        n = 1 << 20
+        D = Sparse(n, n, *problems.skewed_csr(n, np.random.default_rng(4), window=1 << 17))
+        b = Field((n,)).fill_rhs(1)
+        for spacing in (0.008, 0.002):      # wider than the kscan part's ladder (0.002) so that the columns' rates differ — if all of it converges
+            ks = [0.01 + spacing * j for j in range(6)]
+            hist = []
+            for kj in ks:      # first pass: 40 steps each, then ONE tolerance for the call (the entry point takes one)
+                g = GCR(DiracOp(D, kj), GCR_Param(0, 5, 40, 0.0, False))
+                g.solve(b, Field((n,)).set_zero())
+                hist.append(g.last_history)
+            ends = sorted(float(h[-1]) for h in hist)
+            if np.isfinite(ends).all() and ends[-1] < 1e-2:
+                break
+        tol = float(np.sqrt(ends[2] * ends[3]))      # between the third and the fourth column's: three stop early, at their own steps
+        out["skewed_2p20_w2p17"] = dict(rows=n, first_pass_final_residuals=ends,
+                                        **queue_sides(D, b, ks, (0, 5, 40, tol), (2, 3, 4), runs, [("given", ks), ("longest_first", ks[::-1])]))
+    return out
+
+
+def kscan_side(sample, runs):
+    """the existing batched solve on the sample: the six-value scan and the equal-length k = 8 solve (ms), one side of kscan_ab"""
+    from mgpreconditionedgcr_amd import MultiDiracOp
+    D = read_data(os.path.basename(sample), directory=os.path.dirname(os.path.abspath(sample)))
+    n = D.get_dim()
+    out = {}
+    for name, ks, args, b in (("scan", SCAN_KS, SCAN_ARGS, Field((n,), problems.rhs_grid(n, 1))),
+                              ("equal_k8", [0.05 + 0.13 * j / 7 for j in range(8)], (0, 5, 200, 0.0), Field((n,)).fill_rhs(1))):
+        g = GCR(MultiDiracOp(D, ks), GCR_Param(*args, False))
+        R, X = MultiField.from_fields([b] * len(ks)), MultiField((n,), len(ks))
+        g.solve_multi(R, X.set_zero())
+        t = []
+        for _ in range(runs):
+            X.set_zero()
+            t.append(timer(lambda: g.solve_multi(R, X)))
+        out[name] = stats(t)
+        out[name]["checksum"] = float(X.squarednorm().sum())
+        out[name]["iterations"] = list(g.last_iterations)
+    return out
+
+
+def kscan_ab(sample, parent_lib, runs):
+    """uniform_ab's protocol for the batched solve: parent, this, parent, this, ... one process per timing"""
+    import subprocess
+    sides = {"parent": [], "this": []}
+    for _ in range(runs):
+        for side, lib in (("parent", parent_lib), ("this", _lib.LIB_PATH)):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--parts", "kscan_side", "--lib", lib, "--sample", sample],
+                               capture_output=True, text=True, check=True, timeout=600)
+            sides[side].append(json.loads(p.stdout.strip().splitlines()[-1])["kscan_side"])
+    out = {}
+    for name in sides["parent"][0]:
+        pa = [r[name]["median"] for r in sides["parent"]]
+        th = [r[name]["median"] for r in sides["this"]]
+        assert len({r[name]["checksum"] for r in sides["parent"] + sides["this"]}) == 1      # the same bits from both libraries
+        out[name] = {"parent_ms": stats(pa), "this_ms": stats(th), "this_over_parent": float(np.median(th) / np.median(pa)),
+                     "parent_spread": (max(pa) - min(pa)) / float(np.median(pa)),
+                     "inside_parent_spread": bool(min(pa) <= np.median(th) <= max(pa))}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ks", type=int, nargs="+", default=[1, 2, 4, 8, 12])
@@ -190,9 +321,10 @@ def main():
     ap.add_argument("--block-rows", type=int, default=36000)
     ap.add_argument("--irregular-rows", type=int, default=1 << 23)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--sample", default=None, help="kscan / uniform: the 3072-row sample matrix (text CSR, e.g. 4x4parsed.txt)")
-    ap.add_argument("--lib", default=None, help="uniform: load this libmgcr_hip.so instead of the in-tree one")
-    ap.add_argument("--parent-lib", default=None, help="uniform_ab: the library built from the parent commit")
+    ap.add_argument("--sample", default=None, help="kscan / uniform / queue: the 3072-row sample matrix (text CSR, e.g. 4x4parsed.txt)")
+    ap.add_argument("--lib", default=None, help="uniform / kscan_side: load this libmgcr_hip.so instead of the in-tree one")
+    ap.add_argument("--parent-lib", default=None, help="uniform_ab / kscan_ab: the library built from the parent commit")
+    ap.add_argument("--queue-sample-only", action="store_true", help="queue: leave out the 2^20-row system")
     a = ap.parse_args()
     runs = max(6, a.runs)
     out = {"tool": "bench_multi_rhs", "runs": runs}
@@ -205,6 +337,12 @@ def main():
         out["kscan"] = kscan(a.sample, runs)
     if "uniform" in a.parts:
         out["uniform"] = uniform_side(a.sample, runs)
+    if "queue" in a.parts:
+        out["queue"] = queue_part(a.sample, runs, not a.queue_sample_only)
+    if "kscan_side" in a.parts:
+        out["kscan_side"] = kscan_side(a.sample, runs)
+    if "kscan_ab" in a.parts:
+        out["kscan_ab"] = kscan_ab(a.sample, a.parent_lib, runs)
     if "uniform_ab" in a.parts:
         out["uniform_ab"] = uniform_ab(a.sample, a.parent_lib, runs)
     if "bcsr" in a.parts:
