@@ -16,8 +16,13 @@
 // same fold tree — the same bits (tests/test_gpu_stepbuild.py compares with the three-kernel path bit for bit).
 // The scalar stage between "the sums have arrived" and "stream the rows" (step bookkeeping, the coefficient table's row, the
 // closing coefficients) IS the three-kernel path's: gcr_dev.h; the exchange scaffolding is exchange_dev.h's.
-// Up to 3 stored directions (the closing step with XR at 3 excepted) step_keep_kernel runs the step, reading r once; beyond
-// that, and as the reference side of tests/test_gpu_stepbuild_keep_all.py, step_build_kernel.
+// Up to 3 stored directions (the closing step with XR at 3 excepted) step_keep_kernel runs the step, reading r once; at 4 with XR
+// and at the close at 5 step_keep_wide_kernel does: the same body (gcr_stepbuild_keep_body.h) under another compile-time policy
+// (SbKeepPolicy).  Everywhere else, and as the reference side of tests/test_gpu_stepbuild_keep_all.py and
+// tests/test_gpu_stepbuild_keep_wide.py, step_build_kernel.
+// The body is a text included into the two kernel templates, not a __device__ function template: called through a forceinline
+// function (by value or by reference, its LDS declared inside or handed in) step_keep_kernel<3, true, false, false> needs 8 B of
+// scratch per lane and step_keep_kernel<2, true, true, false> 64 instead of 61 VGPRs; included, the old name's code is what it was.
 // Neither reads from memory what it holds: step_keep_kernel's build takes its first Ap_0 rows from the registers of the pass-1
 // dots (sb_keep_rows), and the closing step_build_kernel at 4 and 5 directions loads a row's r once for the close pass and the
 // build, which are one loop there, the thread's last close row behind the exchange-2 publish (sb_close_merged;
@@ -46,6 +51,12 @@ constexpr int SB_MAX_ND = 5;
 constexpr int SB_KEEP_TB = 2;      // step_keep_kernel: trips whose streams are in registers at a time
 // step_keep_kernel: rows of Ap_0 that stay in registers from the pass-1 dots to the build (4 at 1 direction, 3 or 4 at 2 spill)
 template <int NDT> constexpr int sb_keep_rows() { return NDT == 1 ? 3 : 2; }
+// The compile-time policy of the keep body (gcr_stepbuild_keep_body.h): trips per batch of the build and the close pass, rows of Ap_0 kept across exchange 1, and
+// whether the trips' byte offsets are formed on the fly (trip 0's + t x the row step) instead of held, one register per trip
+template <int TB_, int KT_, bool OTF_> struct SbKeepPolicy {
+    static constexpr int TB = TB_, KT = KT_;
+    static constexpr bool OTF = OTF_;
+};
 // step_build_kernel<CLOSE>: the forms whose close pass and build are one loop over the rows — those it costs no scratch (at 3
 // directions the build's prefetched first row lives longer: 28 B; at 5 without the next residual update, a solve's last step: 12 B)
 template <int NDT, bool XR, bool CLOSE> constexpr bool sb_close_merged() { return CLOSE && (NDT == 4 || (NDT == 5 && XR)); }
@@ -333,8 +344,8 @@ __device__ __forceinline__ double sb_block_owner_from_lds(double *lds) {
     return t;
 }
 
-// KEEP-ALL: step_build_kernel's step (in-cycle / closing, with / without XR) with r read ONCE per launch: the thread's residual
-// rows are loaded by the apply, next to the stencil gather (the same lines: a cache hit), and stay in registers (SB_MAX_TRIPS x
+// KEEP-ALL (the body is gcr_stepbuild_keep_body.h): step_build_kernel's step (in-cycle / closing, with / without XR) with r read
+// ONCE per launch: the thread's residual rows are loaded by the apply, next to the stencil gather (the same lines: a cache hit), and stay in registers (SB_MAX_TRIPS x
 // 16 B) for the shift epilogue, the build's <r,Ap'>, the close pass's P0' and XR; no later pass loads a.x.
 // Register use: the pass-1 dots walk one direction (all trips) at a time, the last direction first, and hand its two sums to the
 // wave trees as soon as they are final (sb_wave_pair_to_lds: the bits of block_sum_owner<2 NDT>, whatever the order of the
@@ -343,218 +354,25 @@ __device__ __forceinline__ double sb_block_owner_from_lds(double *lds) {
 // time, one direction after the other; every stream is addressed as scalar base + one 32-bit offset per trip.  Every element sees
 // the same operations in the same order as in step_build_kernel (ac -= beta_j Ap_j in j order, each per-thread accumulator adds
 // the rows in trip order): the same bits.  Only the forms that fit 64 VGPRs without scratch are launched (sb_keep_fits).
+// With 4 and 5 directions that policy spills (48 B at 4); step_keep_wide_kernel's does not: the build and the close pass walk ONE
+// trip at a time, no row of Ap_0 is kept across exchange 1 (the build loads all of them: a pass-1 line it re-reads directly behind
+// pass 1), and at 5 with XR only trip 0's offset is held, the others formed as off[0] + t x (row step in bytes, a scalar register)
+// where they are used — written as that one sum: added to the scalar base first, the form costs 20 B.  The policies are
+// `if constexpr` on POL only: forming the offsets on the fly in step_keep_kernel<3, true, false, *> costs it 20 B.
 // CLOSE runs build | publish exchange 2 | close pass | poll 2 | XR: the build's Ap_j re-reads follow pass 1 closely, and the close
 // pass (x update and P0', which need only beta and cp) runs while the exchange-2 partials travel.  xr_out = ps[1] (read by the
 // close pass) and p_out = ps[0]: a thread reads an element of them before it writes it, and no other thread touches it; lc->cx,
 // which workgroup 0 updates behind poll 2, is read before this workgroup publishes.
 template <int NDT, bool XR, bool CLOSE, bool REALC>
 __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs a) {
-    __shared__ double lds[(2 * NDT > 4 ? 2 * NDT : 4) * 17];
-    __shared__ double lds_pw[2 * SB_MAX_ND * 17], lds_ws[2 * SB_MAX_ND * RES_GRP];
-    __shared__ int gave_up;
-    __shared__ cplx sbeta[NDT], scp[NDT], scx[NDT];
-    extern __shared__ __attribute__((aligned(16))) unsigned char sb_smem[];   // Ar of this workgroup's rows: [trip][thread]
-    if (a.st->stop_at < a.st->base + a.it) return;
-    const int lb = logical_workgroup(a.rm, (int)blockIdx.x, (int)gridDim.x);
-    if (lb >= a.nlogical) return;
-    cplx *arL = reinterpret_cast<cplx *>(sb_smem);
-    const int tid = (int)threadIdx.x;
-    ResSync sy;
-    res_sync_init(sy, a.slots, a.gen0, a.nlogical, lb, a.abort_dev, a.spin_limit, lds_pw, lds_ws, &gave_up);
-    if (a.test_stall && lb == a.test_stall - 1) return;
-    int64_t i0, end, stride;
-    row_range(a.rm, lb, a.nlogical, a.n, &i0, &end, &stride);
-    auto row = [&](int t) -> int64_t { return i0 + (int64_t)t * stride; };
-    // the rows' byte offsets (n < 2^28 rows here), one VGPR per trip for every stream: the loads and stores take a scalar base
-    // and this offset (64-bit addresses per stream and trip would be kept from pass 1 to the build, and spill)
-    uint32_t off[SB_MAX_TRIPS];
-#pragma unroll
-    for (int t = 0; t < SB_MAX_TRIPS; t++) off[t] = (uint32_t)row(t) * (uint32_t)sizeof(cplx);
-    auto at = [&](auto *p, int t) { return sb_elem(p, off[t]); };
-    cplx rk[SB_MAX_TRIPS];   // r of the thread's rows, from the apply to the last pass
-    // ---- apply (gcr_fused.hip step_apply_kernel): Ar to LDS, r kept ----
-#pragma unroll
-    for (int t = 0; t < SB_MAX_TRIPS; t++) {
-        const int64_t i = row(t);
-        rk[t] = make_double2(0., 0.);
-        if (i < end) {
-            const PatLds pl{nullptr, nullptr, nullptr};
-            cplx sum;
-            // (the stencil's columns are clamped to 0..n-1: 32-bit byte offsets from the scalar base, as below)
-            const auto xj = [&](int32_t j) -> cplx { return *sb_elem(a.x, (uint32_t)j * (uint32_t)sizeof(cplx)); };
-            if constexpr (REALC) sum = sten_row_product_t<7, false, 1>(a.m, i, xj);
-            else sum = fused_row_product<3, 7>(a.m, i, 0, pl, xj);
-            rk[t] = *at(a.x, t);
-            arL[t * RED_THREADS + tid] = a.m.shift ? csub(rk[t], cmul(a.m.k, sum)) : sum;
-        }
-        __builtin_amdgcn_sched_barrier(0);   // (one trip's gathers in registers at a time)
-    }
-    // ---- <Ar, Ap_j>, one direction (all trips) at a time: its two sums go through the wave trees as soon as they are final ----
-    // The directions are walked LAST TO FIRST (every direction's pair of sums has its own LDS slots, so their order enters no
-    // sum): Ap_0 comes last and its first KT rows stay in registers for the build, which starts with Ap_0 — those rows are not
-    // read again (the streams are non-temporal and a vector is an XCD's whole L2: a re-read is a trip to memory).
-    constexpr int KT = sb_keep_rows<NDT>();
-    cplx pre[KT];
-    {
-#pragma unroll
-        for (int jj = 0; jj < NDT; jj++) {
-            const int j = NDT - 1 - jj;
-            cplx b[SB_MAX_TRIPS];
-#pragma unroll
-            for (int t = 0; t < SB_MAX_TRIPS; t++) b[t] = row(t) < end ? ld_stream<true>(at(a.aps[j], t)) : make_double2(0., 0.);
-            double v[2] = {0., 0.};
-#pragma unroll
-            for (int t = 0; t < SB_MAX_TRIPS; t++) {
-                if (row(t) < end) {
-                    const cplx tt = cconj_mul(arL[t * RED_THREADS + tid], b[t]);
-                    v[0] += tt.x;
-                    v[1] += tt.y;
-                }
-            }
-            if (j == 0) {
-#pragma unroll
-                for (int u = 0; u < KT; u++) pre[u] = b[u];
-            }
-            sb_wave_pair_to_lds(v, lds, 2 * j);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        const double mine = sb_block_owner_from_lds<2 * NDT>(lds);
-        if (tid < 2 * NDT) {
-            const v4i w4 = {__double2loint(mine), __double2hiint(mine), (int)sy.gen, 0};
-            __builtin_amdgcn_raw_buffer_store_b128(w4, sy.slots, ((1 * RES_NV + tid) * RES_BLK + lb) * 16, 0, RES_SC1);
-        }
-    }
-    if (!res_collect<2 * NDT>(sy, 1)) {
-        res_abort(a.abort_dev, a.abort_host);
-        for (int64_t i = i0; i < end; i += stride) a.ap_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
-        if (tid < 4) a.partsA[tid * RED_MAX_BLOCKS + lb] = __builtin_nan("");
-        return;
-    }
-    // ---- direction build (as in step_build_kernel) ----
-    bool ends_here = false;
-    if (XR || lb == 0) {
-        double rr[1];
-        fold_partials<1>(a.partsR, a.nblkR, a.strideR, rr, lds);
-        if (lb == 0 && threadIdx.x == 0) {
-            close_step(a.st, a.it, rr[0], a.hist, a.hist_cap, CLOSE);
-            if (CLOSE) a.st->closed = 1;
-        }
-        ends_here = __builtin_amdgcn_readfirstlane(!((rr[0] / a.st->bnorm2) > a.st->tol2)) != 0;   // (decided here: not sunk to XR)
-    }
-    if (tid < NDT) sbeta[tid] = cdiv(make_double2(res_total(sy, 2 * tid), res_total(sy, 2 * tid + 1)), a.den[tid]);
-    __syncthreads();
-    if constexpr (CLOSE) {
-        if (tid < NDT) {
-            scp[tid] = lean_close_coef(a.lc, sbeta, NDT, tid);
-            scx[tid] = a.lc->cx[tid];
-        }
-        __syncthreads();
-    }
-    if (!CLOSE && lb == 0 && tid <= NDT) lean_table_row<NDT>(a.lc, sbeta, tid);
-    {
-        cplx beta[NDT];   // (in scalar registers once: read from LDS per batch, the compiler keeps them in vector registers)
-#pragma unroll
-        for (int j = 0; j < NDT; j++) beta[j] = to_sgpr(sbeta[j]);
-        double v[4] = {0., 0., 0., 0.};
-#pragma unroll
-        for (int t0 = 0; t0 < SB_MAX_TRIPS; t0 += SB_KEEP_TB) {
-            cplx ac[SB_KEEP_TB];
-#pragma unroll
-            for (int u = 0; u < SB_KEEP_TB; u++) ac[u] = make_double2(0., 0.);
-#pragma unroll
-            for (int j = 0; j < NDT; j++) {
-                cplx aj[SB_KEEP_TB];
-#pragma unroll
-                for (int u = 0; u < SB_KEEP_TB; u++)
-                    aj[u] = (j == 0 && t0 + u < KT) ? pre[t0 + u < KT ? t0 + u : 0]
-                            : row(t0 + u) < end   ? ld_stream<NTS>(at(a.aps[j], t0 + u))
-                                                  : make_double2(0., 0.);
-#pragma unroll
-                for (int u = 0; u < SB_KEEP_TB; u++) ac[u] = csub(ac[u], cmul(beta[j], aj[u]));
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int u = 0; u < SB_KEEP_TB; u++) {
-                const int t = t0 + u;
-                const int64_t i = row(t);
-                if (i < end) {
-                    const cplx an = cadd(arL[t * RED_THREADS + tid], ac[u]);
-                    *at(a.ap_out, t) = an;
-                    if (XR) arL[t * RED_THREADS + tid] = an;   // (A r is not needed any more; the update below wants Ap')
-                    const cplx tt = cconj_mul(rk[t], an);
-                    v[0] += tt.x; v[1] += tt.y;
-                    const cplx w = cconj_mul(an, an);
-                    v[2] += w.x; v[3] += w.y;
-                }
-            }
-        }
-        const double mine = block_sum_owner<4>(v, lds);
-        if (tid < 4) a.partsA[tid * RED_MAX_BLOCKS + lb] = mine;
-        if (XR && tid < 4) {
-            const v4i w4 = {__double2loint(mine), __double2hiint(mine), (int)sy.gen, 0};
-            __builtin_amdgcn_raw_buffer_store_b128(w4, sy.slots, ((2 * RES_NV + tid) * RES_BLK + lb) * 16, 0, RES_SC1);
-        }
-    }
-    if constexpr (CLOSE) {
-        // x += sum_j cx_j p_j;  P0' = r - sum_j cp_j p_j  (p_0 = P0, p_m = D_m), while the exchange-2 partials travel
-        cplx cx[NDT], cp[NDT];
-#pragma unroll
-        for (int j = 0; j < NDT; j++) {
-            cx[j] = to_sgpr(scx[j]);
-            cp[j] = to_sgpr(scp[j]);
-        }
-#pragma unroll
-        for (int t0 = 0; t0 < SB_MAX_TRIPS; t0 += SB_KEEP_TB) {
-            cplx xv[SB_KEEP_TB], pc[SB_KEEP_TB];
-#pragma unroll
-            for (int u = 0; u < SB_KEEP_TB; u++) {
-                xv[u] = row(t0 + u) < end ? *at(a.xvec, t0 + u) : make_double2(0., 0.);
-                pc[u] = make_double2(0., 0.);
-            }
-#pragma unroll
-            for (int j = 0; j < NDT; j++) {
-                cplx pj[SB_KEEP_TB];
-#pragma unroll
-                for (int u = 0; u < SB_KEEP_TB; u++) pj[u] = row(t0 + u) < end ? ld_stream<NTS>(at(a.ps[j], t0 + u)) : make_double2(0., 0.);
-#pragma unroll
-                for (int u = 0; u < SB_KEEP_TB; u++) {
-                    xv[u] = cadd(xv[u], cmul(cx[j], pj[u]));
-                    pc[u] = csub(pc[u], cmul(cp[j], pj[u]));
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < SB_KEEP_TB; u++) {
-                const int64_t i = row(t0 + u);
-                if (i < end) {
-                    *at(a.xvec, t0 + u) = xv[u];
-                    st_stream<NTS>(at(a.p_out, t0 + u), cadd(rk[t0 + u], pc[u]));
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    if constexpr (XR) {
-        if (!res_collect<4>(sy, 2)) {
-            res_abort(a.abort_dev, a.abort_host);
-            for (int64_t i = i0; i < end; i += stride) a.xr_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
-            if (threadIdx.x == 0) a.partsR_out[lb] = __builtin_nan("");
-            return;
-        }
-        if (ends_here) return;
-        const cplx alpha = sb_xr_alpha(sy, a.st, a.lc, a.xr_den_slot, a.xr_slot, lb);
-        double vr[1] = {0.};
-#pragma unroll
-        for (int t = 0; t < SB_MAX_TRIPS; t++) {
-            const int64_t i = row(t);
-            if (i < end) {
-                const cplx rn = csub(rk[t], cmul(alpha, arL[t * RED_THREADS + tid]));
-                *at(a.xr_out, t) = rn;
-                vr[0] += rn.x * rn.x + rn.y * rn.y;
-            }
-        }
-        const double tot = block_sum_owner<1>(vr, lds);
-        if (threadIdx.x == 0) a.partsR_out[lb] = tot;
-    }
+    using POL = SbKeepPolicy<SB_KEEP_TB, sb_keep_rows<NDT>(), false>;
+#include "gcr_stepbuild_keep_body.h"
+}
+// 4 stored directions with XR, 5 at the close (sb_keep_wide_fits): one trip at a time, no kept row, at 5 with XR the offsets on the fly
+template <int NDT, bool XR, bool CLOSE, bool REALC>
+__global__ void __launch_bounds__(RED_THREADS, 8) step_keep_wide_kernel(StepBuildArgs a) {
+    using POL = SbKeepPolicy<1, 0, NDT == 5 && XR>;
+#include "gcr_stepbuild_keep_body.h"
 }
 
 // The start of a solve from x0 = 0 as ONE launch (r0 = P0 = b, no preconditioner): what gcr.hip ran as copy2_kernel (r = P0 = b),
@@ -668,17 +486,40 @@ bool set_start_build_enabled(bool on) { return g_start_build.set(on); }
 bool set_stepbuild_keep_all_enabled(bool on) { return g_sb_keep_all.set(on); }
 static int64_t g_stepbuild_launches = 0;
 int64_t stepbuild_launch_count() { return g_stepbuild_launches; }
+static int64_t g_keep_wide_launches = 0;   // ... of them, step_keep_wide_kernel
+int64_t stepbuild_keep_wide_launch_count() { return g_keep_wide_launches; }
 
 // The instantiation a step with `nd` stored directions launches (sb_kernel).
 // KEEP-ALL (step_keep_kernel) where an instantiation keeps 0 scratch and 8 waves per SIMD: up to 2 stored directions in every
 // form, 3 except the closing step with XR (tests/test_stepbuild_keep_all_regs.py).  With more directions the kept rows spill (the
-// build's two trips of NDT streams, beta and the kept rows exceed 64 VGPRs): step_build_kernel takes those steps.
+// build's two trips of NDT streams, beta and the kept rows exceed 64 VGPRs): sb_keep_wide below, or step_build_kernel.
 template <int NDT, bool XR, bool CLOSE> constexpr bool sb_keep_fits() { return NDT <= 2 || (NDT == 3 && !(XR && CLOSE)); }
 template <int NDT, bool XR, bool CLOSE, bool R> const void *sb_keep() {
     if constexpr (sb_keep_fits<NDT, XR, CLOSE>()) return (const void *)step_keep_kernel<NDT, XR, CLOSE, R>;
     else return nullptr;
 }
+// ... and step_keep_wide_kernel — the same body one trip at a time, no kept row — where it has 0 scratch and 8 waves per SIMD
+// (tests/test_stepbuild_keep_wide_regs.py) AND was measured faster than the step_build_kernel form it replaces: 4 stored directions
+// with XR, inside a cycle and closing one (restart 4), and the close at 5 with and without XR.  At 4 directions without XR the
+// in-cycle form was measured no faster (62.1 against 61.7 us at 128^3) and the closing one not at all: step_build_kernel, as for
+// 5 directions inside a cycle (restart > 5).
+template <int NDT, bool XR, bool CLOSE> constexpr bool sb_keep_wide_fits() { return (NDT == 4 && XR) || (NDT == 5 && CLOSE); }
+template <int NDT, bool XR, bool CLOSE, bool R> const void *sb_keep_wide_form() {
+    if constexpr (sb_keep_wide_fits<NDT, XR, CLOSE>()) return (const void *)step_keep_wide_kernel<NDT, XR, CLOSE, R>;
+    else return nullptr;
+}
+static const void *sb_keep_wide(int nd, bool xr, bool close, bool realc) {
+#define SKR(NDT, R) (close ? (xr ? sb_keep_wide_form<NDT, true, true, R>() : sb_keep_wide_form<NDT, false, true, R>()) \
+                           : (xr ? sb_keep_wide_form<NDT, true, false, R>() : sb_keep_wide_form<NDT, false, false, R>()))
+#define SKK(NDT) (realc ? SKR(NDT, true) : SKR(NDT, false))
+    return nd == 4 ? SKK(4) : nd == 5 ? SKK(5) : nullptr;
+#undef SKK
+#undef SKR
+}
 static const void *sb_kernel(int nd, bool xr, bool close, bool realc) {
+    if (g_sb_keep_all.on() && nd > 3) {
+        if (const void *wide = sb_keep_wide(nd, xr, close, realc)) return wide;
+    }
     if (g_sb_keep_all.on() && nd <= 3) {
 #define SKR(NDT, R) (close ? (xr ? sb_keep<NDT, true, true, R>() : sb_keep<NDT, false, true, R>()) \
                            : (xr ? sb_keep<NDT, true, false, R>() : sb_keep<NDT, false, false, R>()))
@@ -785,9 +626,11 @@ int csr_step_build(const CsrDev &A, const cplx *x, bool shift, cplx k, const cpl
     for (int j = 0; j < SB_MAX_ND; j++) a.ps[j] = close_ps ? close_ps[j < nd ? j : 0] : nullptr;
     a.p_out = close_p_out; a.xvec = close_x;
     a.xr_out = xr_out; a.xr_den_slot = xr_den_slot; a.xr_slot = xr_slot; a.partsR_out = partsR_out;
-    MGCR_TRY(sb_launch(sb_kernel(nd, xr_out != nullptr, close_ps != nullptr, g_sb_real.on() && a.m.realv), &a, a.nlogical, sb_lds_bytes(A, a.nlogical),
-                       "csr_step_build"));
+    const bool xr = xr_out != nullptr, close = close_ps != nullptr, realc = g_sb_real.on() && a.m.realv;
+    const void *kernel = sb_kernel(nd, xr, close, realc);
+    MGCR_TRY(sb_launch(kernel, &a, a.nlogical, sb_lds_bytes(A, a.nlogical), "csr_step_build"));
     g_stepbuild_launches++;
+    if (nd > 3 && kernel == sb_keep_wide(nd, xr, close, realc)) g_keep_wide_launches++;
     return MGCR_OK;
 }
 

@@ -1,0 +1,217 @@
+// The body of gcr_stepbuild.hip's step_keep_kernel and step_keep_wide_kernel (see there): included INSIDE each of the two kernel
+// templates, behind `using POL = SbKeepPolicy<...>`, with the template parameters NDT, XR, CLOSE, REALC and the argument `a` in scope.
+// One text, two kernel names; not a header to include anywhere else.
+    constexpr int TB = POL::TB, KT = POL::KT;
+    constexpr bool OTF = POL::OTF;
+    __shared__ double lds[(2 * NDT > 4 ? 2 * NDT : 4) * 17];
+    __shared__ double lds_pw[2 * SB_MAX_ND * 17], lds_ws[2 * SB_MAX_ND * RES_GRP];
+    __shared__ int gave_up;
+    __shared__ cplx sbeta[NDT], scp[NDT], scx[NDT];
+    extern __shared__ __attribute__((aligned(16))) unsigned char sb_smem[];   // Ar of this workgroup's rows: [trip][thread]
+    if (a.st->stop_at < a.st->base + a.it) return;
+    const int lb = logical_workgroup(a.rm, (int)blockIdx.x, (int)gridDim.x);
+    if (lb >= a.nlogical) return;
+    cplx *arL = reinterpret_cast<cplx *>(sb_smem);
+    const int tid = (int)threadIdx.x;
+    ResSync sy;
+    res_sync_init(sy, a.slots, a.gen0, a.nlogical, lb, a.abort_dev, a.spin_limit, lds_pw, lds_ws, &gave_up);
+    if (a.test_stall && lb == a.test_stall - 1) return;
+    int64_t i0, end, stride;
+    row_range(a.rm, lb, a.nlogical, a.n, &i0, &end, &stride);
+    auto row = [&](int t) -> int64_t { return i0 + (int64_t)t * stride; };
+    // the rows' byte offsets (n < 2^28 rows here), one VGPR per trip for every stream: the loads and stores take a scalar base
+    // and this offset (64-bit addresses per stream and trip would be kept from pass 1 to the build, and spill)
+    // (POL::OTF: only trip 0's offset is held; the others are formed where they are used, from the row step in a scalar register)
+    uint32_t off[OTF ? 1 : SB_MAX_TRIPS];
+#pragma unroll
+    for (int t = 0; t < (OTF ? 1 : SB_MAX_TRIPS); t++) off[t] = (uint32_t)row(t) * (uint32_t)sizeof(cplx);
+    const uint32_t soff = OTF ? (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)stride * (uint32_t)sizeof(cplx))) : 0u;
+    auto at = [&](auto *p, int t) {
+        if constexpr (OTF) return sb_elem(p, off[0] + (uint32_t)t * soff);
+        else return sb_elem(p, off[t]);
+    };
+    cplx rk[SB_MAX_TRIPS];   // r of the thread's rows, from the apply to the last pass
+    // ---- apply (gcr_fused.hip step_apply_kernel): Ar to LDS, r kept ----
+#pragma unroll
+    for (int t = 0; t < SB_MAX_TRIPS; t++) {
+        const int64_t i = row(t);
+        rk[t] = make_double2(0., 0.);
+        if (i < end) {
+            const PatLds pl{nullptr, nullptr, nullptr};
+            cplx sum;
+            // (the stencil's columns are clamped to 0..n-1: 32-bit byte offsets from the scalar base, as below)
+            const auto xj = [&](int32_t j) -> cplx { return *sb_elem(a.x, (uint32_t)j * (uint32_t)sizeof(cplx)); };
+            if constexpr (REALC) sum = sten_row_product_t<7, false, 1>(a.m, i, xj);
+            else sum = fused_row_product<3, 7>(a.m, i, 0, pl, xj);
+            rk[t] = *at(a.x, t);
+            arL[t * RED_THREADS + tid] = a.m.shift ? csub(rk[t], cmul(a.m.k, sum)) : sum;
+        }
+        __builtin_amdgcn_sched_barrier(0);   // (one trip's gathers in registers at a time)
+    }
+    // ---- <Ar, Ap_j>, one direction (all trips) at a time: its two sums go through the wave trees as soon as they are final ----
+    // The directions are walked LAST TO FIRST (every direction's pair of sums has its own LDS slots, so their order enters no
+    // sum): Ap_0 comes last and its first KT rows stay in registers for the build, which starts with Ap_0 — those rows are not
+    // read again (the streams are non-temporal and a vector is an XCD's whole L2: a re-read is a trip to memory).
+    cplx pre[KT > 0 ? KT : 1];
+    {
+#pragma unroll
+        for (int jj = 0; jj < NDT; jj++) {
+            const int j = NDT - 1 - jj;
+            cplx b[SB_MAX_TRIPS];
+#pragma unroll
+            for (int t = 0; t < SB_MAX_TRIPS; t++) b[t] = row(t) < end ? ld_stream<true>(at(a.aps[j], t)) : make_double2(0., 0.);
+            double v[2] = {0., 0.};
+#pragma unroll
+            for (int t = 0; t < SB_MAX_TRIPS; t++) {
+                if (row(t) < end) {
+                    const cplx tt = cconj_mul(arL[t * RED_THREADS + tid], b[t]);
+                    v[0] += tt.x;
+                    v[1] += tt.y;
+                }
+            }
+            if constexpr (KT > 0) {
+                if (j == 0) {
+#pragma unroll
+                    for (int u = 0; u < KT; u++) pre[u] = b[u];
+                }
+            }
+            sb_wave_pair_to_lds(v, lds, 2 * j);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const double mine = sb_block_owner_from_lds<2 * NDT>(lds);
+        if (tid < 2 * NDT) {
+            const v4i w4 = {__double2loint(mine), __double2hiint(mine), (int)sy.gen, 0};
+            __builtin_amdgcn_raw_buffer_store_b128(w4, sy.slots, ((1 * RES_NV + tid) * RES_BLK + lb) * 16, 0, RES_SC1);
+        }
+    }
+    if (!res_collect<2 * NDT>(sy, 1)) {
+        res_abort(a.abort_dev, a.abort_host);
+        for (int64_t i = i0; i < end; i += stride) a.ap_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
+        if (tid < 4) a.partsA[tid * RED_MAX_BLOCKS + lb] = __builtin_nan("");
+        return;
+    }
+    // ---- direction build (as in step_build_kernel) ----
+    bool ends_here = false;
+    if (XR || lb == 0) {
+        double rr[1];
+        fold_partials<1>(a.partsR, a.nblkR, a.strideR, rr, lds);
+        if (lb == 0 && threadIdx.x == 0) {
+            close_step(a.st, a.it, rr[0], a.hist, a.hist_cap, CLOSE);
+            if (CLOSE) a.st->closed = 1;
+        }
+        ends_here = __builtin_amdgcn_readfirstlane(!((rr[0] / a.st->bnorm2) > a.st->tol2)) != 0;   // (decided here: not sunk to XR)
+    }
+    if (tid < NDT) sbeta[tid] = cdiv(make_double2(res_total(sy, 2 * tid), res_total(sy, 2 * tid + 1)), a.den[tid]);
+    __syncthreads();
+    if constexpr (CLOSE) {
+        if (tid < NDT) {
+            scp[tid] = lean_close_coef(a.lc, sbeta, NDT, tid);
+            scx[tid] = a.lc->cx[tid];
+        }
+        __syncthreads();
+    }
+    if (!CLOSE && lb == 0 && tid <= NDT) lean_table_row<NDT>(a.lc, sbeta, tid);
+    {
+        cplx beta[NDT];   // (in scalar registers once: read from LDS per batch, the compiler keeps them in vector registers)
+#pragma unroll
+        for (int j = 0; j < NDT; j++) beta[j] = to_sgpr(sbeta[j]);
+        double v[4] = {0., 0., 0., 0.};
+#pragma unroll
+        for (int t0 = 0; t0 < SB_MAX_TRIPS; t0 += TB) {
+            cplx ac[TB];
+#pragma unroll
+            for (int u = 0; u < TB; u++) ac[u] = make_double2(0., 0.);
+#pragma unroll
+            for (int j = 0; j < NDT; j++) {
+                cplx aj[TB];
+#pragma unroll
+                for (int u = 0; u < TB; u++)
+                    aj[u] = (j == 0 && t0 + u < KT) ? pre[t0 + u < KT ? t0 + u : 0]
+                            : row(t0 + u) < end   ? ld_stream<NTS>(at(a.aps[j], t0 + u))
+                                                  : make_double2(0., 0.);
+#pragma unroll
+                for (int u = 0; u < TB; u++) ac[u] = csub(ac[u], cmul(beta[j], aj[u]));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int u = 0; u < TB; u++) {
+                const int t = t0 + u;
+                const int64_t i = row(t);
+                if (i < end) {
+                    const cplx an = cadd(arL[t * RED_THREADS + tid], ac[u]);
+                    *at(a.ap_out, t) = an;
+                    if (XR) arL[t * RED_THREADS + tid] = an;   // (A r is not needed any more; the update below wants Ap')
+                    const cplx tt = cconj_mul(rk[t], an);
+                    v[0] += tt.x; v[1] += tt.y;
+                    const cplx w = cconj_mul(an, an);
+                    v[2] += w.x; v[3] += w.y;
+                }
+            }
+        }
+        const double mine = block_sum_owner<4>(v, lds);
+        if (tid < 4) a.partsA[tid * RED_MAX_BLOCKS + lb] = mine;
+        if (XR && tid < 4) {
+            const v4i w4 = {__double2loint(mine), __double2hiint(mine), (int)sy.gen, 0};
+            __builtin_amdgcn_raw_buffer_store_b128(w4, sy.slots, ((2 * RES_NV + tid) * RES_BLK + lb) * 16, 0, RES_SC1);
+        }
+    }
+    if constexpr (CLOSE) {
+        // x += sum_j cx_j p_j;  P0' = r - sum_j cp_j p_j  (p_0 = P0, p_m = D_m), while the exchange-2 partials travel
+        cplx cx[NDT], cp[NDT];
+#pragma unroll
+        for (int j = 0; j < NDT; j++) {
+            cx[j] = to_sgpr(scx[j]);
+            cp[j] = to_sgpr(scp[j]);
+        }
+#pragma unroll
+        for (int t0 = 0; t0 < SB_MAX_TRIPS; t0 += TB) {
+            cplx xv[TB], pc[TB];
+#pragma unroll
+            for (int u = 0; u < TB; u++) {
+                xv[u] = row(t0 + u) < end ? *at(a.xvec, t0 + u) : make_double2(0., 0.);
+                pc[u] = make_double2(0., 0.);
+            }
+#pragma unroll
+            for (int j = 0; j < NDT; j++) {
+                cplx pj[TB];
+#pragma unroll
+                for (int u = 0; u < TB; u++) pj[u] = row(t0 + u) < end ? ld_stream<NTS>(at(a.ps[j], t0 + u)) : make_double2(0., 0.);
+#pragma unroll
+                for (int u = 0; u < TB; u++) {
+                    xv[u] = cadd(xv[u], cmul(cx[j], pj[u]));
+                    pc[u] = csub(pc[u], cmul(cp[j], pj[u]));
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < TB; u++) {
+                const int64_t i = row(t0 + u);
+                if (i < end) {
+                    *at(a.xvec, t0 + u) = xv[u];
+                    st_stream<NTS>(at(a.p_out, t0 + u), cadd(rk[t0 + u], pc[u]));
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if constexpr (XR) {
+        if (!res_collect<4>(sy, 2)) {
+            res_abort(a.abort_dev, a.abort_host);
+            for (int64_t i = i0; i < end; i += stride) a.xr_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
+            if (threadIdx.x == 0) a.partsR_out[lb] = __builtin_nan("");
+            return;
+        }
+        if (ends_here) return;
+        const cplx alpha = sb_xr_alpha(sy, a.st, a.lc, a.xr_den_slot, a.xr_slot, lb);
+        double vr[1] = {0.};
+#pragma unroll
+        for (int t = 0; t < SB_MAX_TRIPS; t++) {
+            const int64_t i = row(t);
+            if (i < end) {
+                const cplx rn = csub(rk[t], cmul(alpha, arL[t * RED_THREADS + tid]));
+                *at(a.xr_out, t) = rn;
+                vr[0] += rn.x * rn.x + rn.y * rn.y;
+            }
+        }
+        const double tot = block_sum_owner<1>(vr, lds);
+        if (threadIdx.x == 0) a.partsR_out[lb] = tot;
+    }
