@@ -252,6 +252,7 @@ int mgcr_stat(const char *name, int64_t *value) {
     if (!strcmp(name, "resident_solves")) *value = resident_solve_count();
     else if (!strcmp(name, "step_build_launches")) *value = stepbuild_launch_count();
     else if (!strcmp(name, "step_keep_wide_launches")) *value = stepbuild_keep_wide_launch_count();
+    else if (!strcmp(name, "step_apply_own_launches")) *value = stepbuild_apply_own_launch_count();
     else if (!strcmp(name, "start_build_launches")) *value = start_build_launch_count();
     else if (!strcmp(name, "small_solves")) *value = gcr_small_solve_count();
     else if (!strcmp(name, "one_launch_fallbacks")) *value = gcr_fallback_count();

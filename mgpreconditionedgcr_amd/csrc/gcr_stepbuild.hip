@@ -27,6 +27,10 @@
 // dots (sb_keep_rows), and the closing step_build_kernel at 4 and 5 directions loads a row's r once for the close pass and the
 // build, which are one loop there, the thread's last close row behind the exchange-2 publish (sb_close_merged;
 // tests/test_gpu_stepbuild_reuse.py: the same bits, tests/test_stepbuild_reuse_regs.py: the same registers class).
+// The keep forms for real coefficients do not load a row's own r either: it IS the diagonal slot's gather (sb_apply_form; a trip of
+// their apply is 7 loads and one round trip where it was 8 and two; 34.8 against 36.7 us at 1 direction, +1.5 % on the headline).
+// Taking r[i - 1] and r[i + 1] from the neighbouring lanes on top of that (6 loads per trip) gives the same bits and was measured
+// slower: not built.  tests/test_gpu_stepbuild_apply_lanes.py, tests/test_stepbuild_apply_lanes_regs.py, DESIGN section 8.
 //
 // Needs all workgroups co-resident (they wait for each other): 64 VGPRs and <= 80 KB of LDS each, at most 2 x #CU
 // workgroups, no other process on the device (no live communicator).  Up to 5 stored directions (beyond that the
@@ -53,10 +57,23 @@ constexpr int SB_KEEP_TB = 2;      // step_keep_kernel: trips whose streams are 
 template <int NDT> constexpr int sb_keep_rows() { return NDT == 1 ? 3 : 2; }
 // The compile-time policy of the keep body (gcr_stepbuild_keep_body.h): trips per batch of the build and the close pass, rows of Ap_0 kept across exchange 1, and
 // whether the trips' byte offsets are formed on the fly (trip 0's + t x the row step) instead of held, one register per trip
-template <int TB_, int KT_, bool OTF_> struct SbKeepPolicy {
+// ... and how the apply gets the thread's own r and its two neighbours in the row (sb_apply_form)
+template <int TB_, int KT_, bool OTF_, int APPLY_> struct SbKeepPolicy {
     static constexpr int TB = TB_, KT = KT_;
     static constexpr bool OTF = OTF_;
+    static constexpr bool OWN = APPLY_ >= 1, LANES = APPLY_ >= 2;
 };
+// The apply of a keep form: 0 the seven gathers and a load of the row's own r behind them; 1 the own r IS the diagonal slot's
+// gather (one load and one dependent round trip less per trip); 2 r[i - 1] and r[i + 1] come from the neighbouring lanes as well
+// (spmv_dev.h sten_row_product_own_t).  1 and 2 need sten_lane_middle(A): the host checks it (sb_kernel).
+// Built: 1 in every form for real coefficients.  2 fits them all (0 scratch, 60..64 VGPRs) and gives the same bits, but was
+// measured slower than 1 in each of the headline's five kernels; -DMGCR_SB_APPLY=2 / 0 builds it / the old apply
+// for such a measurement.  The forms for complex coefficients keep 0: with 1 or 2 every one of them needs 12 to 20 B of scratch
+// (their scalar registers already spill into vector-register lanes).
+#ifndef MGCR_SB_APPLY
+#define MGCR_SB_APPLY 1
+#endif
+template <bool WIDE, int NDT, bool XR, bool CLOSE, bool REALC> constexpr int sb_apply_form() { return REALC ? MGCR_SB_APPLY : 0; }
 // step_build_kernel<CLOSE>: the forms whose close pass and build are one loop over the rows — those it costs no scratch (at 3
 // directions the build's prefetched first row lives longer: 28 B; at 5 without the next residual update, a solve's last step: 12 B)
 template <int NDT, bool XR, bool CLOSE> constexpr bool sb_close_merged() { return CLOSE && (NDT == 4 || (NDT == 5 && XR)); }
@@ -345,7 +362,8 @@ __device__ __forceinline__ double sb_block_owner_from_lds(double *lds) {
 }
 
 // KEEP-ALL (the body is gcr_stepbuild_keep_body.h): step_build_kernel's step (in-cycle / closing, with / without XR) with r read
-// ONCE per launch: the thread's residual rows are loaded by the apply, next to the stencil gather (the same lines: a cache hit), and stay in registers (SB_MAX_TRIPS x
+// ONCE per launch: the thread's residual rows ARE the apply's diagonal gathers (sb_apply_form; the forms for complex coefficients
+// load them again behind the gathers: the same lines, a cache hit) and stay in registers (SB_MAX_TRIPS x
 // 16 B) for the shift epilogue, the build's <r,Ap'>, the close pass's P0' and XR; no later pass loads a.x.
 // Register use: the pass-1 dots walk one direction (all trips) at a time, the last direction first, and hand its two sums to the
 // wave trees as soon as they are final (sb_wave_pair_to_lds: the bits of block_sum_owner<2 NDT>, whatever the order of the
@@ -365,13 +383,13 @@ __device__ __forceinline__ double sb_block_owner_from_lds(double *lds) {
 // which workgroup 0 updates behind poll 2, is read before this workgroup publishes.
 template <int NDT, bool XR, bool CLOSE, bool REALC>
 __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs a) {
-    using POL = SbKeepPolicy<SB_KEEP_TB, sb_keep_rows<NDT>(), false>;
+    using POL = SbKeepPolicy<SB_KEEP_TB, sb_keep_rows<NDT>(), false, sb_apply_form<false, NDT, XR, CLOSE, REALC>()>;
 #include "gcr_stepbuild_keep_body.h"
 }
 // 4 stored directions with XR, 5 at the close (sb_keep_wide_fits): one trip at a time, no kept row, at 5 with XR the offsets on the fly
 template <int NDT, bool XR, bool CLOSE, bool REALC>
 __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_wide_kernel(StepBuildArgs a) {
-    using POL = SbKeepPolicy<1, 0, NDT == 5 && XR>;
+    using POL = SbKeepPolicy<1, 0, NDT == 5 && XR, sb_apply_form<true, NDT, XR, CLOSE, REALC>()>;
 #include "gcr_stepbuild_keep_body.h"
 }
 
@@ -488,13 +506,17 @@ static int64_t g_stepbuild_launches = 0;
 int64_t stepbuild_launch_count() { return g_stepbuild_launches; }
 static int64_t g_keep_wide_launches = 0;   // ... of them, step_keep_wide_kernel
 int64_t stepbuild_keep_wide_launch_count() { return g_keep_wide_launches; }
+static int64_t g_apply_own_launches = 0;   // ... of them, keep forms whose apply takes the own r from the diagonal gather (sb_apply_form 1, 2)
+int64_t stepbuild_apply_own_launch_count() { return g_apply_own_launches; }
 
 // The instantiation a step with `nd` stored directions launches (sb_kernel).
 // KEEP-ALL (step_keep_kernel) where an instantiation keeps 0 scratch and 8 waves per SIMD: up to 2 stored directions in every
 // form, 3 except the closing step with XR (tests/test_stepbuild_keep_all_regs.py).  With more directions the kept rows spill (the
 // build's two trips of NDT streams, beta and the kept rows exceed 64 VGPRs): sb_keep_wide below, or step_build_kernel.
 template <int NDT, bool XR, bool CLOSE> constexpr bool sb_keep_fits() { return NDT <= 2 || (NDT == 3 && !(XR && CLOSE)); }
-template <int NDT, bool XR, bool CLOSE, bool R> const void *sb_keep() {
+// (*form: the apply form of the instantiation, sb_apply_form)
+template <int NDT, bool XR, bool CLOSE, bool R> const void *sb_keep(int *form) {
+    *form = sb_apply_form<false, NDT, XR, CLOSE, R>();
     if constexpr (sb_keep_fits<NDT, XR, CLOSE>()) return (const void *)step_keep_kernel<NDT, XR, CLOSE, R>;
     else return nullptr;
 }
@@ -504,30 +526,40 @@ template <int NDT, bool XR, bool CLOSE, bool R> const void *sb_keep() {
 // in-cycle form was measured no faster (62.1 against 61.7 us at 128^3) and the closing one not at all: step_build_kernel, as for
 // 5 directions inside a cycle (restart > 5).
 template <int NDT, bool XR, bool CLOSE> constexpr bool sb_keep_wide_fits() { return (NDT == 4 && XR) || (NDT == 5 && CLOSE); }
-template <int NDT, bool XR, bool CLOSE, bool R> const void *sb_keep_wide_form() {
+template <int NDT, bool XR, bool CLOSE, bool R> const void *sb_keep_wide_form(int *form) {
+    *form = sb_apply_form<true, NDT, XR, CLOSE, R>();
     if constexpr (sb_keep_wide_fits<NDT, XR, CLOSE>()) return (const void *)step_keep_wide_kernel<NDT, XR, CLOSE, R>;
     else return nullptr;
 }
-static const void *sb_keep_wide(int nd, bool xr, bool close, bool realc) {
-#define SKR(NDT, R) (close ? (xr ? sb_keep_wide_form<NDT, true, true, R>() : sb_keep_wide_form<NDT, false, true, R>()) \
-                           : (xr ? sb_keep_wide_form<NDT, true, false, R>() : sb_keep_wide_form<NDT, false, false, R>()))
+static const void *sb_keep_wide(int nd, bool xr, bool close, bool realc, int *form) {
+#define SKR(NDT, R) (close ? (xr ? sb_keep_wide_form<NDT, true, true, R>(form) : sb_keep_wide_form<NDT, false, true, R>(form)) \
+                           : (xr ? sb_keep_wide_form<NDT, true, false, R>(form) : sb_keep_wide_form<NDT, false, false, R>(form)))
 #define SKK(NDT) (realc ? SKR(NDT, true) : SKR(NDT, false))
     return nd == 4 ? SKK(4) : nd == 5 ? SKK(5) : nullptr;
 #undef SKK
 #undef SKR
 }
-static const void *sb_kernel(int nd, bool xr, bool close, bool realc) {
-    if (g_sb_keep_all.on() && nd > 3) {
-        if (const void *wide = sb_keep_wide(nd, xr, close, realc)) return wide;
-    }
+// `mid`: the stencil view's middle slots are the row and its two neighbours (sten_lane_middle) — a keep form whose apply builds on that
+// (sb_apply_form 1 and 2) is handed out only then; any other 7-slot view takes step_build_kernel: the same bits.
+// *wide / *own (may be null): was it step_keep_wide_kernel, is its apply form 1 or 2?
+static const void *sb_kernel(int nd, bool xr, bool close, bool realc, bool mid, bool *wide = nullptr, bool *own = nullptr) {
+    if (wide) *wide = false;
+    if (own) *own = false;
+    const void *keep = nullptr;
+    int form = 0;
+    if (g_sb_keep_all.on() && nd > 3) keep = sb_keep_wide(nd, xr, close, realc, &form);
     if (g_sb_keep_all.on() && nd <= 3) {
-#define SKR(NDT, R) (close ? (xr ? sb_keep<NDT, true, true, R>() : sb_keep<NDT, false, true, R>()) \
-                           : (xr ? sb_keep<NDT, true, false, R>() : sb_keep<NDT, false, false, R>()))
+#define SKR(NDT, R) (close ? (xr ? sb_keep<NDT, true, true, R>(&form) : sb_keep<NDT, false, true, R>(&form)) \
+                           : (xr ? sb_keep<NDT, true, false, R>(&form) : sb_keep<NDT, false, false, R>(&form)))
 #define SKK(NDT) (realc ? SKR(NDT, true) : SKR(NDT, false))
-        const void *keep = nd == 1 ? SKK(1) : nd == 2 ? SKK(2) : SKK(3);
+        keep = nd == 1 ? SKK(1) : nd == 2 ? SKK(2) : SKK(3);   // (nullptr: a form that does not fit, sb_keep_fits)
 #undef SKK
 #undef SKR
-        if (keep) return keep;   // (nullptr: a form that does not fit, sb_keep_fits)
+    }
+    if (keep && (form == 0 || mid)) {
+        if (wide) *wide = nd > 3;
+        if (own) *own = form >= 1;
+        return keep;
     }
 #define SBR(NDT, R) (close ? (xr ? (const void *)step_build_kernel<3, 7, NDT, true, true, R> : (const void *)step_build_kernel<3, 7, NDT, false, true, R>) \
                            : (xr ? (const void *)step_build_kernel<3, 7, NDT, true, false, R> : (const void *)step_build_kernel<3, 7, NDT, false, false, R>))
@@ -584,7 +616,7 @@ bool csr_step_build_eligible(const CsrDev &A, const DistCsr *dist, int lim) {
     const bool realc = g_sb_real.on() && row_mat(A, false, cplx{0., 0.}).realv;
     for (int xr = 0; xr < 2; xr++)
         for (int cl = 0; cl < 2; cl++)
-            if (!launch_is_coresident(sb_kernel(lim, xr != 0, cl != 0, realc), RED_THREADS, lds, g)) return false;
+            if (!launch_is_coresident(sb_kernel(lim, xr != 0, cl != 0, realc, sten_lane_middle(A)), RED_THREADS, lds, g)) return false;
     return true;
 }
 
@@ -627,10 +659,12 @@ int csr_step_build(const CsrDev &A, const cplx *x, bool shift, cplx k, const cpl
     a.p_out = close_p_out; a.xvec = close_x;
     a.xr_out = xr_out; a.xr_den_slot = xr_den_slot; a.xr_slot = xr_slot; a.partsR_out = partsR_out;
     const bool xr = xr_out != nullptr, close = close_ps != nullptr, realc = g_sb_real.on() && a.m.realv;
-    const void *kernel = sb_kernel(nd, xr, close, realc);
+    bool wide, own;
+    const void *kernel = sb_kernel(nd, xr, close, realc, sten_lane_middle(A), &wide, &own);
     MGCR_TRY(sb_launch(kernel, &a, a.nlogical, sb_lds_bytes(A, a.nlogical), "csr_step_build"));
     g_stepbuild_launches++;
-    if (nd > 3 && kernel == sb_keep_wide(nd, xr, close, realc)) g_keep_wide_launches++;
+    if (wide) g_keep_wide_launches++;
+    if (own) g_apply_own_launches++;
     return MGCR_OK;
 }
 

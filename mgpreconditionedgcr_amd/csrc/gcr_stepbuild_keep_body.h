@@ -36,11 +36,24 @@
     for (int t = 0; t < SB_MAX_TRIPS; t++) {
         const int64_t i = row(t);
         rk[t] = make_double2(0., 0.);
-        if (i < end) {
+        // (the stencil's columns are clamped to 0..n-1: 32-bit byte offsets from the scalar base, as below)
+        const auto xj = [&](int32_t j) -> cplx { return *sb_elem(a.x, (uint32_t)j * (uint32_t)sizeof(cplx)); };
+        if constexpr (POL::OWN) {
+            // The row product hands the row's own r back (the stencil's diagonal slot: the host has checked that it is one,
+            // sten_lane_middle) and, with POL::LANES, takes r[i - 1] and r[i + 1] from the neighbouring lanes: a whole wave enters,
+            // also its lanes beyond `end` (a wave's rows are 64 consecutive ones from a multiple of 64: its first lane decides)
+            static_assert(REALC, "the forms for complex coefficients spill with it");
+            if (__builtin_amdgcn_readfirstlane((int32_t)i) < (int32_t)end) {
+                cplx own;
+                const cplx sum = sten_row_product_own_t<1, POL::LANES>(a.m, i, xj, own);
+                if (i < end) {
+                    rk[t] = own;
+                    arL[t * RED_THREADS + tid] = a.m.shift ? csub(own, cmul(a.m.k, sum)) : sum;
+                }
+            }
+        } else if (i < end) {
             const PatLds pl{nullptr, nullptr, nullptr};
             cplx sum;
-            // (the stencil's columns are clamped to 0..n-1: 32-bit byte offsets from the scalar base, as below)
-            const auto xj = [&](int32_t j) -> cplx { return *sb_elem(a.x, (uint32_t)j * (uint32_t)sizeof(cplx)); };
             if constexpr (REALC) sum = sten_row_product_t<7, false, 1>(a.m, i, xj);
             else sum = fused_row_product<3, 7>(a.m, i, 0, pl, xj);
             rk[t] = *at(a.x, t);

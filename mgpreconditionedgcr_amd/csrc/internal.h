@@ -285,6 +285,7 @@ int64_t resident_solve_count();
 bool set_stepbuild_enabled(bool on);   // gcr_stepbuild.hip: apply + dots + build of a lean step as one launch
 int64_t stepbuild_launch_count();
 int64_t stepbuild_keep_wide_launch_count();    // ... of them, step_keep_wide_kernel (4 directions in a cycle, the close at 5)
+int64_t stepbuild_apply_own_launch_count();    // ... of them, keep forms whose apply takes the row's own r from the diagonal gather
 bool set_start_build_enabled(bool on);         // ... and the start of a solve as one launch
 int64_t start_build_launch_count();
 bool set_stepbuild_keep_all_enabled(bool on);  // ... every one-launch step reads r once (step_keep_kernel)

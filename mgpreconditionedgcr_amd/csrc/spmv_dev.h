@@ -234,6 +234,68 @@ __device__ __forceinline__ cplx sten_row_product_t(const RowMat &m, int64_t row,
     }
     return sum;
 }
+// A 7-slot stencil view whose middle slots are the row's left neighbour, the row itself and its right neighbour
+// (what sten_row_product_own_t below builds on; checked on the host, once per operator)
+inline bool sten_lane_middle(const CsrDev &A) {
+    return sten_slots(A) == 7 && !A.sten_rare && A.sten_off[2] == -1 && A.sten_off[3] == 0 && A.sten_off[4] == 1;
+}
+// One dword of every lane's v from the lane below (CTRL 0x138, wave_shr:1) or above (0x130, wave_shl:1) in ONE VALU operation of
+// gfx950; the lane without such a neighbour (0 / 63) keeps `old`.  Every lane of the wave must be active: an inactive lane
+// hands nothing on.
+template <int CTRL>
+__device__ __forceinline__ double wave_shift1(double old, double v) {
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(v), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+// sten_row_product_t<7, false, REALV> for the kernels that also want the row's OWN x (the one-launch GCR steps that keep r on
+// chip, gcr_stepbuild_keep_body.h), on a stencil view with sten_lane_middle: slot 3 IS the own value — it is handed back in
+// `own` instead of being loaded a second time, behind a second wait — and with LANES slots 2 and 4 are not gathered at all: they
+// are the own values of lanes l - 1 and l + 1, taken with two whole-wave shifts; only lane 0's left and lane 63's right
+// neighbour are loaded, by ONE load with those two lanes active.  Every xv[c] holds the bits the gather would have brought, the
+// presence selects and the sum are sten_row_product_t's: the same bits.
+// To be called by ALL 64 lanes of a wave (rows as there: consecutive from a multiple of 64, the first one inside the matrix),
+// also by those whose row lies beyond the caller's `end`: their loads are clamped like every slot's, their sums are not used,
+// and no present slot of a row < end takes a value from a row >= end that the gather would not have clamped to the same column.
+template <int REALV, bool LANES, class XF>
+__device__ __forceinline__ cplx sten_row_product_own_t(const RowMat &m, int64_t row, XF xf, cplx &own) {
+    constexpr int NS = STEN_COMMON;
+    const int32_t wave = __builtin_amdgcn_readfirstlane((int32_t)(row >> 6));
+    const sten_planes_ptr pp = sten_wave_planes(m, wave);
+    uint64_t pl[NS];
+#pragma unroll
+    for (int c = 0; c < NS; c++) pl[c] = pp[c];
+    const int lane = (int)(threadIdx.x & 63);
+    const auto clamped = [&](int32_t j) -> int32_t { return j < 0 ? 0 : j > m.sten_last ? m.sten_last : j; };
+    cplx xv[NS];
+#pragma unroll
+    for (int c = 0; c < NS; c++)
+        if (!LANES || (c != 2 && c != 4)) xv[c] = xf(clamped((int32_t)row + m.sten_off[c]));
+    cplx edge = make_double2(0., 0.);
+    if constexpr (LANES) {
+        if (lane == 0 || lane == 63) edge = xf(clamped((int32_t)row + (lane == 0 ? m.sten_off[2] : m.sten_off[4])));
+    }
+    // (as in sten_row_product_t: every load in flight before a presence bit is looked at)
+    __builtin_amdgcn_sched_barrier(0);
+    // ... and the presence words must be requested HERE, next to the loads: the caller uses the sum in its rows < end only,
+    // and the words' scalar loads would otherwise sink into that branch, behind the wait for the loads
+#pragma unroll
+    for (int c = 0; c < NS; c++) asm volatile("" ::"s"(pl[c]));
+    own = xv[3];
+    if constexpr (LANES) {
+        xv[2] = make_double2(wave_shift1<0x138>(edge.x, own.x), wave_shift1<0x138>(edge.y, own.y));
+        xv[4] = make_double2(wave_shift1<0x130>(edge.x, own.x), wave_shift1<0x130>(edge.y, own.y));
+    }
+    cplx sum = make_double2(0., 0.);
+#pragma unroll
+    for (int c = 0; c < NS; c++) {
+        const bool on = (pl[c] >> lane & 1ull) != 0ull;
+        const cplx nsum = cadd(sum, sten_term<REALV>(m, c, xv[c]));
+        sum.x = on ? nsum.x : sum.x;
+        sum.y = on ? nsum.y : sum.y;
+    }
+    return sum;
+}
 template <int NS, bool RARE, class XF>
 __device__ __forceinline__ cplx sten_row_product(const RowMat &m, int64_t row, XF xf) {
     // Real or complex slot values: the rare-tail kernels branch once per row (two copies of the body: 37.3 against 38.6 us
