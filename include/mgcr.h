@@ -121,6 +121,52 @@ int mgcr_dirac_set_k(mgcr_op_t dirac, const double k_ri[2]);       /* set_k src/
  * values hold for every later call and never for work already enqueued. */
 int mgcr_dirac_multi_create(mgcr_op_t csr, int32_t k, const double *k_ri /* [k][2] */, mgcr_op_t *out);
 int mgcr_dirac_multi_set_k(mgcr_op_t op, const double *k_ri /* [k][2] */);
+/* EvenOddDiracOp: the even-odd (red-black) preconditioned 1 - k D (no reference counterpart — test_kcritical, src/main.cpp:696-741,
+ * solves the full system).  D must be a pure hopping matrix: square, NO diagonal, every entry joining an even row to an odd one.
+ * Then A x = b reduces to the Schur system on the even half,
+ *     S x_e = bhat_e,   S = 1 - k^2 D_eo D_oe,   bhat_e = b_e + k D_eo b_o,   x_o = b_o + k D_oe x_e,
+ * and the operator made here IS S: an Operator on Fields of n_e entries (mgcr_op_dim = mgcr_op_nrow = n_e, mgcr_op_nnz = that of
+ * D).  Operators with a diagonal (Poisson, a clover term) are out of scope, and so is distributed use.
+ * mgcr_eo_create COPIES the matrix (host CSR, int64 indices).  parity: [n] 0 even / 1 odd, or NULL — the graph of D + D^T is then
+ * two-coloured breadth first, components in order of their smallest row, that row (an isolated or empty row included) even.
+ * Given or computed, the parity is checked: an entry that joins two rows of equal colour (a diagonal entry, an odd cycle, a wrong
+ * caller bit) is MGCR_ERR_INVALID, and the message names the first such (row, column).  k = 0: MGCR_ERR_INVALID, here and in
+ * mgcr_eo_set_k (DiracOp's "No k value supplied").
+ * Layout: even[] / odd[] are the ascending full-system rows of each colour; D_eo (n_e x n_o) and D_oe (n_o x n_e) keep their rows
+ * in list order, renumber the columns into the other list and keep a row's entries in stored order; each half is a Sparse of its
+ * own in whatever storage form mgcr_csr_create would choose for it.  mgcr_eo_half_op lends them (0: D_eo, 1: D_oe; owned by the
+ * operator like the levels mgcr_mg_level_op lends, not to be destroyed).
+ * mgcr_eo_split / mgcr_eo_merge move a full Field to / from its (even, odd) halves; mgcr_eo_prepare forms bhat_e from b;
+ * mgcr_eo_reconstruct forms x_o from b and x_e and merges.  mgcr_eo_solve = prepare, mgcr_gcr_solve(S, param, bhat_e, x_e),
+ * reconstruct (the operator keeps that solver's state and work Fields between calls); x_e is the even half of x_full on entry and use_x0 behaves as documented for mgcr_gcr_solve (the reference's
+ * r0 = b quirk applies to the EVEN system); history, iteration count and convergence flag are the Schur solve's, relative to
+ * |bhat_e|: the full system's true residual |(1 - k D) x - b| / |b| is hist[last] |bhat_e| / |b|, its odd half is rounding only.
+ * Accepted by: mgcr_op_apply (Fields of n_e entries), mgcr_bench_op_apply, mgcr_gcr_solve, mgcr_gcr_create /
+ * mgcr_gcr_set_operator, and as a preconditioner slot.  MGCR_ERR_UNSUPPORTED from: mgcr_op_apply_multi, mgcr_gcr_solve_multi,
+ * mgcr_gcr_solve_queue, mgcr_mg_create and the storage queries (stored_bytes / storage_format / ell_layout / xr_fuse_kind /
+ * halo_kind; ask the halves).  A Field of the wrong length: MGCR_ERR_INVALID, on every entry point.
+ * Rule 1 (apply): through the public entry points, BIT-IDENTICAL are
+ *     mgcr_op_apply(eo, x, y)            and  t = D_oe(x); u = D_eo(t); mgcr_add_scaled(y, x, -k2, u)   (k2 = k k, un-fused),
+ *     mgcr_eo_prepare                    and  mgcr_add_scaled(bhat_e, b_e, +k, D_eo(b_o)),
+ *     the odd half of mgcr_eo_reconstruct  and  mgcr_add_scaled(x_o, b_o, +k, D_oe(x_e)),
+ * with the half operators of mgcr_eo_half_op (the library is built without FP contraction: a - c s and a + (-c) s have the same bits).
+ * Rule 2 (solve): history, iteration count, convergence flag and x of a GCR solve on the operator are BIT-IDENTICAL with the
+ * option fused_apply on and off.  On: where D_eo is stored one thread per row, the second stage of each step's apply also takes
+ * the step's beta dot products (one launch less per step); off: two plain applies, then the dot products.
+ * A GCR solve on this operator always runs the multi-kernel path: no one-launch solve, step or start, no graph replay.
+ * mgcr_eo_set_k: the values travel in the kernel arguments of each launch — the new k holds for every later call and never for
+ * work already enqueued. */
+int mgcr_eo_create(int64_t n, const int64_t *rowptr, const int64_t *col, const double *val_ri,
+                   const int8_t *parity /* [n] 0 even, 1 odd; NULL: two-colour */, const double k_ri[2], mgcr_op_t *out);
+int mgcr_eo_set_k(mgcr_op_t eo, const double k_ri[2]);
+int mgcr_eo_info(mgcr_op_t eo, int64_t *n, int64_t *n_even, int64_t *n_odd);
+int mgcr_eo_parity(mgcr_op_t eo, int8_t *parity /* [n] */);
+int mgcr_eo_half_op(mgcr_op_t eo, int32_t which /* 0: D_eo, 1: D_oe */, mgcr_op_t *borrowed);
+int mgcr_eo_split(mgcr_op_t eo, mgcr_vec_t full, mgcr_vec_t even, mgcr_vec_t odd);
+int mgcr_eo_merge(mgcr_op_t eo, mgcr_vec_t even, mgcr_vec_t odd, mgcr_vec_t full);
+int mgcr_eo_prepare(mgcr_op_t eo, mgcr_vec_t b_full, mgcr_vec_t bhat_even);
+int mgcr_eo_reconstruct(mgcr_op_t eo, mgcr_vec_t b_full, mgcr_vec_t x_even, mgcr_vec_t x_full);
+/* (mgcr_eo_solve is declared below, with the solver entry points) */
 /* HierarchicalSparse<long,int> (block-CSR of dense bs x bs blocks, row-major inside a block,
  * src/HierarchicalSparse.h:22-48) from UNSORTED (block-row, block-col, block) triplets with the
  * constructor's semantics (:58-98): sorted by row*nbcol+col, duplicates of a pair kept and
@@ -209,7 +255,9 @@ int mgcr_set_option(const char *name, int value, int *previous);
  * peer-write halo exchanges of distributed applies that ran split (store + publish | interior rows | wait | boundary rows),
  * "pw_tail_folds" = reductions folded and summed over the ranks inside their producing kernel, "multi_solves" = batched solves
  * (mgcr_gcr_solve_multi) completed — queued solves are not counted there but in "queue_solves" = mgcr_gcr_solve_queue calls completed,
- * "queue_admissions" = systems those loaded into a slot after step 0, "queue_steps" = lockstep steps they launched. */
+ * "queue_admissions" = systems those loaded into a slot after step 0, "queue_steps" = lockstep steps they launched,
+ * "evenodd_fused_steps" = GCR steps on an even-odd preconditioned DiracOp whose second apply stage took the step's beta dot
+ * products (mgcr_eo_create, Rule 2). */
 int mgcr_stat(const char *name, int64_t *value);
 
 /* Self-test of the hardware behaviour the one-launch solver paths (csrc/gcr_resident.hip, gcr_stepbuild.hip) build on: inside
@@ -245,6 +293,9 @@ typedef struct mgcr_gcr_param {
  * *n_iter = iterations performed (global_count); *converged = 0 iff n_iter == max_iter. */
 int mgcr_gcr_solve(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_vec_t rhs, mgcr_vec_t x,
                    double *hist, int32_t hist_cap, int32_t *n_iter, int32_t *converged);
+/* The even-odd preconditioned solve of (1 - k D) x_full = b_full: see mgcr_eo_create. */
+int mgcr_eo_solve(mgcr_op_t eo, const mgcr_gcr_param *param, mgcr_vec_t b_full, mgcr_vec_t x_full,
+                  double *hist, int32_t hist_cap, int32_t *n_iter, int32_t *converged);
 /* k independent solves A x_j = rhs_j that share every launch (batched restarted GCR, csrc/gcr_multi.hip).
  * hist: [k][hist_cap] (may be NULL), row j as mgcr_gcr_solve fills it for column j; n_iter, converged: [k] (may be NULL).
  * Every column has its own device-resident scalars and stop flag; a column that has stopped (|r|^2/|b|^2 <= tol^2, or

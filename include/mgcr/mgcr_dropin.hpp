@@ -857,6 +857,99 @@ private:
     mgcr_op_t dense_op = nullptr;
 };
 
+// EvenOddDiracOp: the even-odd (red-black) preconditioned Id - k*D (extension, mgcr_eo_create) — an Operator on the EVEN half of the
+// rows, S = Id - k^2 D_eo D_oe.  D is a Sparse holding a pure hopping matrix (square, no diagonal, even rows coupled to odd rows
+// only; its arrays are copied, so later changes of the Sparse are not seen).  GCR(&op, &param) solves the Schur system like any other
+// operator; solve() runs prepare -> GCR -> reconstruct on full-system Fields and keeps the Schur solve's history (relative to
+// |bhat_e|), iteration count and flag.  Fields of a half are plain one-dimensional Fields of n_even / n_odd entries.
+template <typename num_type>
+class EvenOddDiracOp : public Operator<num_type> {
+public:
+    EvenOddDiracOp(Sparse<num_type> *mat, std::complex<double> k_factor, const std::vector<int8_t> *parity = nullptr) : k(k_factor) {
+        mgcr_detail::ensure_init();
+        const num_type rows = mat->get_nrow(), nnz = mat->get_nnz();
+        if (rows != mat->get_dim()) { std::fprintf(stderr, "EvenOddDiracOp: matrix must be square\n"); std::abort(); }
+        if (parity && (num_type)parity->size() != rows) { std::fprintf(stderr, "EvenOddDiracOp: parity has %zu entries, the matrix has %lld rows\n", parity->size(), (long long)rows); std::abort(); }
+        std::vector<int64_t> rp((size_t)rows + 1), ci((size_t)nnz);
+        std::vector<std::complex<double>> va((size_t)nnz);
+        for (num_type i = 0; i <= rows; i++) rp[(size_t)i] = (int64_t)mat->get_ROW(i);
+        for (num_type i = 0; i < nnz; i++) { ci[(size_t)i] = (int64_t)mat->get_COL(i); va[(size_t)i] = mat->val_at(i); }
+        double v[2] = {k.real(), k.imag()};
+        mgcr_detail::ok(mgcr_eo_create((int64_t)rows, rp.data(), ci.data(), reinterpret_cast<const double *>(va.data()), parity ? parity->data() : nullptr, v, &op),
+                        "EvenOddDiracOp");
+        int64_t nn = 0, ne = 0, no = 0;
+        mgcr_detail::ok(mgcr_eo_info(op, &nn, &ne, &no), "EvenOddDiracOp");
+        n = (num_type)nn; n_even = (num_type)ne; n_odd = (num_type)no;
+        this->dim = n_even;
+    }
+    EvenOddDiracOp(EvenOddDiracOp const &) = delete;
+    EvenOddDiracOp &operator=(EvenOddDiracOp const &) = delete;
+    ~EvenOddDiracOp() override { if (op) mgcr_op_destroy(op); }
+    std::complex<double> val_at(num_type, num_type) const override { return not_stored(); }
+    std::complex<double> val_at(num_type) const override { return not_stored(); }
+    Field<num_type> operator()(Field<num_type> const &f) override { return this->apply_handle(f, op, n_even); }
+    mgcr_op_t handle() override { return op; }
+    void set_k(std::complex<double> new_k) { k = new_k; double v[2] = {k.real(), k.imag()}; mgcr_detail::ok(mgcr_eo_set_k(op, v), "EvenOddDiracOp::set_k"); }
+    num_type get_n() const { return n; }
+    num_type get_n_even() const { return n_even; }
+    num_type get_n_odd() const { return n_odd; }
+    std::vector<int8_t> parity() const {
+        std::vector<int8_t> out((size_t)n);
+        mgcr_detail::ok(mgcr_eo_parity(op, out.data()), "EvenOddDiracOp::parity");
+        return out;
+    }
+    void split(const Field<num_type> &full, Field<num_type> &even, Field<num_type> &odd) {
+        mgcr_detail::ok(mgcr_eo_split(op, full.device(), even.device(), odd.device()), "EvenOddDiracOp::split");
+        even.device_written(); odd.device_written();
+    }
+    void merge(const Field<num_type> &even, const Field<num_type> &odd, Field<num_type> &full) {
+        mgcr_detail::ok(mgcr_eo_merge(op, even.device(), odd.device(), full.device()), "EvenOddDiracOp::merge");
+        full.device_written();
+    }
+    Field<num_type> prepare(const Field<num_type> &rhs_full) {   // bhat_e = b_e + k D_eo b_o
+        Field<num_type> out(&n_even, 1);
+        mgcr_detail::ok(mgcr_eo_prepare(op, rhs_full.device(), out.device()), "EvenOddDiracOp::prepare");
+        out.device_written();
+        return out;
+    }
+    Field<num_type> reconstruct(const Field<num_type> &rhs_full, const Field<num_type> &x_even) {   // x_o = b_o + k D_oe x_e, merged with x_e
+        Field<num_type> out(rhs_full.get_mesh());
+        mgcr_detail::ok(mgcr_eo_reconstruct(op, rhs_full.device(), x_even.device(), out.device()), "EvenOddDiracOp::reconstruct");
+        out.device_written();
+        return out;
+    }
+    // (Id - k D) x_full = rhs_full through the Schur system; x_full's even half is the start vector where param->use_x0 asks for one
+    void solve(const Field<num_type> &rhs_full, Field<num_type> &x_full, GCR_Param<num_type> *param) {
+        if (param->truncation != 0 && param->restart != 0) { std::fprintf(stderr, "Do not support concurrent restarting and truncation.\n"); std::abort(); }
+        mgcr_gcr_param p;
+        std::memset(&p, 0, sizeof(p));
+        p.truncation = param->truncation; p.restart = param->restart; p.max_iter = param->max_iter; p.tol = param->tol;
+        p.verbose = param->verbose ? 1 : 0;
+        p.left_precond = param->left_precond ? param->left_precond->handle() : nullptr;
+        p.right_precond = param->right_precond ? param->right_precond->handle() : nullptr;
+        p.use_x0 = param->use_x0; p.flexible = param->flexible;
+        const int cap = (param->max_iter > 0 ? param->max_iter : 1) + 1;
+        last_history.assign((size_t)cap, 0.);
+        int32_t it = 0, conv = 0;
+        mgcr_detail::ok(mgcr_eo_solve(op, &p, rhs_full.device(), x_full.device(), last_history.data(), cap, &it, &conv), "EvenOddDiracOp::solve");
+        x_full.device_written();
+        last_history.resize((size_t)it + 1);
+        last_iterations = it; last_converged = conv != 0;
+    }
+    std::vector<double> last_history;   // of the Schur solve, relative to |bhat_e|
+    int last_iterations = 0;
+    bool last_converged = false;
+
+private:
+    static std::complex<double> not_stored() {
+        std::fprintf(stderr, "EvenOddDiracOp::val_at: the Schur complement is applied, never formed\n");
+        std::abort();
+    }
+    std::complex<double> k = 0.;
+    num_type n = 0, n_even = 0, n_odd = 0;
+    mgcr_op_t op = nullptr;
+};
+
 // ------------------------------------------------------------------------------------------------
 // MG — src/MG.h:20-61.  operator() is the corrected V-cycle of DESIGN.md (the reference's returns
 // uninitialised memory, src/MG.h:124-129).

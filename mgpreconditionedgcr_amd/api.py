@@ -425,6 +425,94 @@ class MultiDiracOp(Operator):
         check(_lib.lib().mgcr_dirac_multi_set_k(self.h, kv.ctypes.data_as(C.POINTER(C.c_double))))
 
 
+class EvenOddDiracOp(Operator):
+    """The even-odd (red-black) preconditioned Id - k*D (mgcr_eo_create; no reference counterpart): an Operator on the EVEN half,
+    S = Id - k^2 D_eo D_oe.  `mat` is a Sparse holding a pure hopping matrix (square, no diagonal, even rows coupled to odd rows
+    only); its host arrays are copied.  parity: 0 even / 1 odd per row, or None — the rows are then two-coloured.  GCR(op, ...)
+    solves the Schur system like any other; solve() runs prepare -> GCR -> reconstruct on full-system Fields."""
+
+    def __init__(self, mat, k, parity=None):
+        super().__init__()
+        _lib.init()
+        n = int(mat._shape[0])
+        if mat._shape[0] != mat._shape[1]:
+            raise MgcrError(1, "EvenOddDiracOp: matrix must be square")
+        par = None if parity is None else np.ascontiguousarray(parity, np.int8)
+        if par is not None and par.size != n:
+            raise MgcrError(1, "EvenOddDiracOp: parity has %d entries, the matrix has %d rows" % (par.size, n))
+        h = C.c_void_p()
+        check(_lib.lib().mgcr_eo_create(n, mat.ROW.ctypes.data, mat.COL.ctypes.data, mat.VAL.ctypes.data,
+                                        par.ctypes.data if par is not None else None, _ri(k), C.byref(h)))
+        self.h = h
+        self.last_history = None
+        self.last_iterations = None
+        self.last_converged = None
+
+    def set_k(self, new_k):
+        check(_lib.lib().mgcr_eo_set_k(self.h, _ri(new_k)))
+
+    def sizes(self):
+        """(n, n_even, n_odd)"""
+        n, ne, no = C.c_int64(), C.c_int64(), C.c_int64()
+        check(_lib.lib().mgcr_eo_info(self.h, C.byref(n), C.byref(ne), C.byref(no)))
+        return n.value, ne.value, no.value
+
+    def parity(self):
+        par = np.empty(self.sizes()[0], np.int8)
+        check(_lib.lib().mgcr_eo_parity(self.h, par.ctypes.data))
+        return par
+
+    def halves(self):
+        """(D_eo, D_oe): borrowed views of the two half matrices, Sparse operators owned by this one."""
+        out = []
+        for which in (0, 1):
+            h = C.c_void_p()
+            check(_lib.lib().mgcr_eo_half_op(self.h, which, C.byref(h)))
+            op = Operator()
+            op.h = h
+            op._keep.append(self)
+            op.__class__ = _BorrowedOperator
+            out.append(op)
+        return tuple(out)
+
+    def split(self, full, even=None, odd=None):
+        _, ne, no = self.sizes()
+        even = Field((ne,)) if even is None else even
+        odd = Field((no,)) if odd is None else odd
+        check(_lib.lib().mgcr_eo_split(self.h, full.h, even.h, odd.h))
+        return even, odd
+
+    def merge(self, even, odd, full=None):
+        full = Field((self.sizes()[0],)) if full is None else full
+        check(_lib.lib().mgcr_eo_merge(self.h, even.h, odd.h, full.h))
+        return full
+
+    def prepare(self, rhs_full, bhat_even=None):
+        """bhat_e = b_e + k D_eo b_o"""
+        bhat_even = Field((self.sizes()[1],)) if bhat_even is None else bhat_even
+        check(_lib.lib().mgcr_eo_prepare(self.h, rhs_full.h, bhat_even.h))
+        return bhat_even
+
+    def reconstruct(self, rhs_full, x_even, x_full=None):
+        """x_o = b_o + k D_oe x_e, merged with x_e"""
+        x_full = Field(rhs_full.dims) if x_full is None else x_full
+        check(_lib.lib().mgcr_eo_reconstruct(self.h, rhs_full.h, x_even.h, x_full.h))
+        return x_full
+
+    def solve(self, rhs_full, x_full, gcr_param):
+        """(Id - k D) x_full = rhs_full through the Schur system; history, iteration count and flag are the Schur solve's
+        (relative to |bhat_e|) and are kept in last_history / last_iterations / last_converged."""
+        cap = max(gcr_param.max_iter, 1) + 1
+        hist = np.zeros(cap, np.float64)
+        it, conv = C.c_int32(), C.c_int32()
+        pc = gcr_param._c()
+        check(_lib.lib().mgcr_eo_solve(self.h, C.byref(pc), rhs_full.h, x_full.h, hist.ctypes.data, cap, C.byref(it), C.byref(conv)))
+        self.last_iterations = it.value
+        self.last_converged = bool(conv.value)
+        self.last_history = hist[: it.value + 1].copy()
+        return x_full
+
+
 class HierarchicalSparse(Operator):
     """HierarchicalSparse<long,int> (src/HierarchicalSparse.h:22-48) from unsorted
     (block_row, block_col, dense block) triplets, duplicates kept (ctor :58-98)."""

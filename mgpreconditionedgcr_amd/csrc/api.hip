@@ -160,6 +160,7 @@ int mgcr_op_destroy(mgcr_op_t op) {
         case OP_BCSR: bcsr_free(&op->bcsr); dist_free(op->dist); break;
         case OP_GCR: gcr_state_destroy(op->gcr); break;
         case OP_MG: mg_destroy(op->mg); break;
+        case OP_DIRAC_EO: eo_destroy(op->eo); break;
         default: break;  // OP_DIRAC and OP_DIRAC_MULTI borrow their Sparse (src/Operator.h:117,555-560)
     }
     delete op;
@@ -175,6 +176,7 @@ int64_t mgcr_op_nnz(mgcr_op_t op) {
         case OP_DIRAC:
         case OP_DIRAC_MULTI: return op->base->csr.nnz;
         case OP_BCSR: return (int64_t)op->bcsr.nblocks * op->bcsr.bs * op->bcsr.bs;  // src/HierarchicalSparse.h:31
+        case OP_DIRAC_EO: return eo_nnz(op->eo);   // that of D
         default: return -1;
     }
 }
@@ -262,6 +264,7 @@ int mgcr_stat(const char *name, int64_t *value) {
     else if (!strcmp(name, "queue_solves")) *value = gcr_queue_stat(0);
     else if (!strcmp(name, "queue_admissions")) *value = gcr_queue_stat(1);
     else if (!strcmp(name, "queue_steps")) *value = gcr_queue_stat(2);
+    else if (!strcmp(name, "evenodd_fused_steps")) *value = eo_fused_step_count();
     else { set_error("mgcr_stat: unknown counter '%s'", name); return MGCR_ERR_INVALID; }
     return MGCR_OK;
 }
@@ -421,6 +424,7 @@ int mgcr_bench_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y, int32_t reps, 
 // ---- blocks of k Fields: k-wide apply (spmm.hip), batched GCR (gcr_multi.hip) ------------------------------------------
 static int apply_multi_checks(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y, const char *who) {
     MGCR_CHECK(op && x && y, MGCR_ERR_INVALID, "%s: null argument", who);
+    MGCR_REFUSE_EVENODD(op, who);
     MGCR_CHECK(op->kind != OP_GCR && op->kind != OP_MG, MGCR_ERR_UNSUPPORTED, "%s: GCR and MG objects cannot be applied to a block of Fields", who);
     const Op *b0 = op_matrix(op);
     MGCR_CHECK(!op->dist && !op->comm && !b0->dist && !b0->comm, MGCR_ERR_UNSUPPORTED, "%s: distributed operators are not supported", who);
@@ -462,6 +466,7 @@ int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t r
                          int32_t *n_iter, int32_t *converged) {
     MGCR_TRY(require_ctx());
     MGCR_CHECK(A && param && rhs && x, MGCR_ERR_INVALID, "mgcr_gcr_solve_multi: null argument");
+    MGCR_REFUSE_EVENODD(A, "mgcr_gcr_solve_multi");
     MGCR_CHECK(param->truncation >= 0 && param->restart >= 0 && param->max_iter >= 0, MGCR_ERR_INVALID, "negative GCR parameter");
     MGCR_CHECK(param->truncation == 0, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: truncation mode is not supported (restart mode only)");
     MGCR_CHECK(param->restart != 0, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: restart mode only (restart != 0)");
@@ -488,6 +493,7 @@ int mgcr_gcr_solve_queue(mgcr_op_t A, const mgcr_gcr_param *param, int32_t width
     const char *who = "mgcr_gcr_solve_queue";
     MGCR_TRY(require_ctx());
     MGCR_CHECK(A && param && rhs && x, MGCR_ERR_INVALID, "%s: null argument", who);
+    MGCR_REFUSE_EVENODD(A, who);
     MGCR_CHECK(param->truncation >= 0 && param->restart >= 0 && param->max_iter >= 0, MGCR_ERR_INVALID, "negative GCR parameter");
     MGCR_CHECK(param->truncation == 0, MGCR_ERR_UNSUPPORTED, "%s: truncation mode is not supported (restart mode only)", who);
     MGCR_CHECK(param->restart != 0, MGCR_ERR_UNSUPPORTED, "%s: restart mode only (restart != 0)", who);

@@ -1,0 +1,139 @@
+// The host plan of the even-odd (red-black) preconditioned DiracOp (evenodd.hip): the two-colouring of a pure hopping matrix D,
+// its check, the index lists of the two colours and the half matrices D_eo / D_oe.  Pure host code — plain arrays in, plain
+// vectors out, no HIP header — tests/cpp/evenodd_plan_check.cpp runs it on the CPU.
+//
+// The rules:
+//   * without a caller parity the graph of D + D^T is two-coloured breadth first.  Components are visited in order of their
+//     smallest row, and that row — the component's root — is even; a row without entries is a component of its own, hence even.
+//     A row's colour is the parity of its distance from the root;
+//   * the parity, computed or given, is then CHECKED against the matrix: the first stored entry (rows ascending, a row's entries
+//     in stored order) that joins two rows of equal colour — a diagonal entry, an edge of an odd cycle, a wrong caller bit —
+//     makes the plan fail and is named in the message;
+//   * even[] / odd[] list the full-system rows of each colour, ascending; index[r] is row r's place in its list;
+//   * D_eo (n_e x n_o) holds the even rows, D_oe (n_o x n_e) the odd ones, both CSR: rows in list order, columns renumbered by
+//     index[], a row's entries IN STORED ORDER — the half applies then sum a row in the order the full apply does.
+#pragma once
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+namespace mgcr {
+
+struct HalfCsr {
+    int64_t nrow = 0, ncol = 0;
+    std::vector<int64_t> rowptr, col;
+    std::vector<double> val_ri;   // interleaved (re, im)
+};
+
+struct EvenOddPlan {
+    int64_t n = 0;
+    std::vector<int8_t> parity;        // [n] 0 even, 1 odd
+    std::vector<int64_t> even, odd;    // ascending full-system rows
+    std::vector<int64_t> index;        // [n] place of the row in its colour's list
+    HalfCsr eo, oe;                    // D_eo, D_oe
+    int64_t bad_row = -1, bad_col = -1;   // the entry the check refused
+};
+
+// breadth-first two-colouring of D + D^T (see the rules above); the matrix is taken as it is, nothing is checked here
+inline void evenodd_colour(int64_t n, const int64_t *rowptr, const int64_t *col, std::vector<int8_t> &parity) {
+    const int64_t nnz = n > 0 ? rowptr[n] : 0;
+    // the transposed pattern: who points at me
+    std::vector<int64_t> tptr((size_t)n + 1, 0), tcol((size_t)nnz);
+    for (int64_t e = 0; e < nnz; e++) tptr[(size_t)col[e] + 1]++;
+    for (int64_t r = 0; r < n; r++) tptr[(size_t)r + 1] += tptr[(size_t)r];
+    {
+        std::vector<int64_t> fill(tptr.begin(), tptr.end() - 1);
+        for (int64_t r = 0; r < n; r++)
+            for (int64_t e = rowptr[r]; e < rowptr[r + 1]; e++) tcol[(size_t)fill[(size_t)col[e]]++] = r;
+    }
+    parity.assign((size_t)n, (int8_t)-1);
+    std::vector<int64_t> queue;
+    queue.reserve((size_t)n);
+    for (int64_t root = 0; root < n; root++) {
+        if (parity[(size_t)root] >= 0) continue;
+        parity[(size_t)root] = 0;
+        queue.clear();
+        queue.push_back(root);
+        for (size_t head = 0; head < queue.size(); head++) {
+            const int64_t r = queue[head];
+            const int8_t other = (int8_t)(1 - parity[(size_t)r]);
+            for (int64_t e = rowptr[r]; e < rowptr[r + 1]; e++) {
+                const int64_t c = col[e];
+                if (parity[(size_t)c] < 0) { parity[(size_t)c] = other; queue.push_back(c); }
+            }
+            for (int64_t e = tptr[(size_t)r]; e < tptr[(size_t)r + 1]; e++) {
+                const int64_t c = tcol[(size_t)e];
+                if (parity[(size_t)c] < 0) { parity[(size_t)c] = other; queue.push_back(c); }
+            }
+        }
+    }
+}
+
+// false (with *err and the plan's bad_row / bad_col filled where an entry is to blame): the caller answers MGCR_ERR_INVALID
+inline bool evenodd_plan_build(int64_t n, const int64_t *rowptr, const int64_t *col, const double *val_ri, const int8_t *parity_in,
+                               EvenOddPlan *out, std::string *err) {
+    char msg[256];
+    auto fail = [&](const char *m) { if (err) *err = m; return false; };
+    if (n < 0 || !rowptr || !out) return fail("even-odd plan: bad argument");
+    if (rowptr[0] != 0) return fail("even-odd plan: rowptr[0] must be 0");
+    for (int64_t r = 0; r < n; r++)
+        if (rowptr[r + 1] < rowptr[r]) {
+            snprintf(msg, sizeof msg, "even-odd plan: rowptr is not non-decreasing at row %lld", (long long)r);
+            return fail(msg);
+        }
+    const int64_t nnz = rowptr[n];
+    if (nnz > 0 && (!col || !val_ri)) return fail("even-odd plan: null column or value array");
+    for (int64_t e = 0; e < nnz; e++)
+        if (col[e] < 0 || col[e] >= n) {
+            snprintf(msg, sizeof msg, "even-odd plan: column index %lld is outside [0, %lld)", (long long)col[e], (long long)n);
+            return fail(msg);
+        }
+    EvenOddPlan &p = *out;
+    p = EvenOddPlan();
+    p.n = n;
+    if (parity_in) {
+        p.parity.assign(parity_in, parity_in + n);
+        for (int64_t r = 0; r < n; r++)
+            if (p.parity[(size_t)r] != 0 && p.parity[(size_t)r] != 1) {
+                snprintf(msg, sizeof msg, "even-odd plan: parity[%lld] = %d is neither 0 (even) nor 1 (odd)", (long long)r, (int)p.parity[(size_t)r]);
+                return fail(msg);
+            }
+    } else {
+        evenodd_colour(n, rowptr, col, p.parity);
+    }
+    for (int64_t r = 0; r < n; r++)
+        for (int64_t e = rowptr[r]; e < rowptr[r + 1]; e++)
+            if (p.parity[(size_t)r] == p.parity[(size_t)col[e]]) {
+                p.bad_row = r;
+                p.bad_col = col[e];
+                snprintf(msg, sizeof msg,
+                         "even-odd plan: entry (row %lld, column %lld) joins two %s rows%s: the matrix must be a pure hopping matrix that couples even to odd rows only",
+                         (long long)r, (long long)col[e], p.parity[(size_t)r] ? "odd" : "even", r == col[e] ? " (a diagonal entry)" : "");
+                return fail(msg);
+            }
+    p.index.assign((size_t)n, 0);
+    for (int64_t r = 0; r < n; r++) {
+        std::vector<int64_t> &list = p.parity[(size_t)r] ? p.odd : p.even;
+        p.index[(size_t)r] = (int64_t)list.size();
+        list.push_back(r);
+    }
+    auto half = [&](const std::vector<int64_t> &rows, int64_t ncol, HalfCsr &h) {
+        h.nrow = (int64_t)rows.size();
+        h.ncol = ncol;
+        h.rowptr.assign(1, 0);
+        for (int64_t r : rows) {
+            for (int64_t e = rowptr[r]; e < rowptr[r + 1]; e++) {
+                h.col.push_back(p.index[(size_t)col[e]]);
+                h.val_ri.push_back(val_ri[2 * e]);
+                h.val_ri.push_back(val_ri[2 * e + 1]);
+            }
+            h.rowptr.push_back((int64_t)h.col.size());
+        }
+    };
+    half(p.even, (int64_t)p.odd.size(), p.eo);
+    half(p.odd, (int64_t)p.even.size(), p.oe);
+    return true;
+}
+
+}  // namespace mgcr

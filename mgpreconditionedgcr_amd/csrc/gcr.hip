@@ -707,6 +707,8 @@ int op_apply_raw(Op *op, const cplx *x, cplx *y, int64_t n) {
             return gcr_apply_as_operator(op->gcr, x, y);
         case OP_MG:
             return mg_apply(op->mg, x, y);
+        case OP_DIRAC_EO:   // the Schur complement on the even half: two launches (evenodd.hip)
+            return eo_apply(op, x, y, n);
         case OP_DIRAC_MULTI:   // (reached through a preconditioner slot; the entry points refuse it themselves)
             set_error("a MultiDiracOp has one hopping parameter per column of a block and cannot be applied to a single Field");
             return MGCR_ERR_UNSUPPORTED;
@@ -1018,6 +1020,9 @@ struct SolvePlan {
     // pending updates.  That kernel can just as well WRITE x = sum alpha_j p_j: no zeroing pass before, no read of x then.
     bool assign_x;
     bool fuse_ok;      // operator apply fused with the beta dot products: Sparse / DiracOp in a one-thread-per-row layout (gcr_fused.hip)
+    // even-odd preconditioned DiracOp (evenodd.hip): the general multi-kernel path on the plain row map — no one-launch solve, step or
+    // start, no residual update inside the apply, no graph replay; schur_fuse: stage 2 of its apply takes the beta dot products
+    bool schur, schur_fuse;
     // The plain start of a solve on a fusable Sparse / DiracOp (r0 = p0 = rhs: no x0, no preconditioner): r and p0 are
     // written by ONE kernel from one read of rhs, and Ap_0 = A rhs comes out of the pass that also takes <r0,Ap0>,
     // <Ap0,Ap0> and |r0|^2 = |b|^2 (gcr_fused.hip init_apply_kernel) — 3 launches instead of 6 and 6 V less traffic
@@ -1044,6 +1049,7 @@ static SolvePlan gcr_plan(const GcrState *s, const cplx *rhs, cplx *x, bool nest
     pl.max_it = p.max_iter > 0 ? p.max_iter : 1;
     pl.flex = p.flexible && p.right_precond;
     pl.skip_tail = !p.right_precond || pl.flex;
+    pl.schur = A->kind == OP_DIRAC_EO;
     pl.lean = p.restart != 0 && s->storage <= LND && g_lean.on() && !p.left_precond && (!p.right_precond || pl.flex);
     pl.small = gcr_small_eligible(A, p, s->storage, pl.n);
     const bool handoff = nested && (s->keep_pending || s->defer_residual);   // callers that take x or r in pieces (V-cycle pre-smoother)
@@ -1052,7 +1058,8 @@ static SolvePlan gcr_plan(const GcrState *s, const cplx *rhs, cplx *x, bool nest
     pl.comm = A->kind == OP_DIRAC ? A->base->comm : A->comm;
     pl.multi = comm_collectives(pl.comm);
     pl.g = red_grid(pl.n);
-    pl.rmap = make_row_map(pl.n, pl.g, pl.b0 ? pl.b0->csr.reach : 0);
+    pl.rmap = pl.schur ? RowMap{0, 0, 0, 0, 0, 0} : make_row_map(pl.n, pl.g, pl.b0 ? pl.b0->csr.reach : 0);
+    pl.schur_fuse = pl.schur && !p.left_precond && eo_schur_fusable(A);
     pl.defer = pl.lean || (p.restart != 0 && s->storage <= ND);
     pl.alias_p0 = pl.lean && !pl.flex && p.max_iter >= 1 && p.max_iter < p.restart;
     pl.alias0 = pl.alias_p0 && !p.use_x0;
@@ -1068,7 +1075,7 @@ static SolvePlan gcr_plan(const GcrState *s, const cplx *rhs, cplx *x, bool nest
                 !(nested && p.max_iter <= 1 && (s->defer_residual || s->discard_residual)) && !xr_able &&
                 csr_start_build_eligible(pl.b0->csr, pl.b0->dist) && csr_step_build_eligible(pl.b0->csr, pl.b0->dist, s->restart);
     pl.use_graph = g_graph.on() && pl.n <= GRAPH_MAX_ROWS && pl.defer && !pl.multi && !p.left_precond && !p.right_precond &&
-                   !p.profile_spmv && pl.max_it >= 2 * s->restart && s->restart <= s->storage;
+                   !p.profile_spmv && pl.max_it >= 2 * s->restart && s->restart <= s->storage && !pl.schur;
     return pl;
 }
 
@@ -1352,6 +1359,13 @@ static int step_apply_dots(GcrState *s, const SolvePlan &pl, const StepCursor &c
             if (*tail_rb) { pw.pa = s->partsR; pw.na = 1; pw.pb = s->partsB; pw.nb = 2 * lim; pw.out = s->dRB; pw.nblk = pl.g; }
             MGCR_TRY(csr_step_apply(M, st.dir, s->ar, pl.shift, pl.k, vecs, nf, s->partsB, dist, pl.rmap, *tail_rb ? &pw : nullptr));
         }
+        ch0 = lim <= FND ? nchunk : 1;
+    } else if (pl.schur_fuse) {
+        // t = D_oe dir, then Ar = dir - k^2 D_eo t with the partials of the first FND directions (evenodd.hip); the rest as above
+        const int nf = lim < FND ? lim : FND;
+        const cplx *vecs[FND];
+        for (int j = 0; j < FND; j++) vecs[j] = s->aps[j < nf ? j : 0];
+        MGCR_TRY(eo_schur_step(s->A, st.dir, s->ar, vecs, nf, s->partsB, pl.rmap));
         ch0 = lim <= FND ? nchunk : 1;
     } else {
         MGCR_TRY(op_apply_raw(s->A, st.dir, s->ar, pl.n));  // src/GCR.h:242

@@ -529,6 +529,7 @@ __global__ void __launch_bounds__(RED_THREADS, 8) sten_apply_carry_kernel(RowMat
 static EnvSwitch g_fuse("MGCR_FUSE"), g_fused_tile("MGCR_FUSED_TILE"), g_tile_carry("MGCR_TILE_CARRY"), g_xr_tile("MGCR_XR_FUSE_TILE"),
     g_apply_carry("MGCR_APPLY_CARRY");
 bool set_fuse_enabled(bool on) { return g_fuse.set(on); }
+bool fuse_enabled() { return g_fuse.on(); }
 bool csr_fusable(const CsrDev &A, const DistCsr *dist) {
     if (A.pat_mode == 1 && (int64_t)A.npat * A.W * 20 > 48 * 1024) return false;  // pattern table must fit LDS
     // a row block of a distributed matrix qualifies when its halo exchange is ordered on the compute stream

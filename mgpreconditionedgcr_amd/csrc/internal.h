@@ -83,7 +83,7 @@ struct MVec {
 };
 constexpr int MV_MAX_K = 16;
 
-enum OpKind { OP_CSR = 1, OP_DIRAC = 2, OP_BCSR = 3, OP_GCR = 4, OP_MG = 5, OP_DIRAC_MULTI = 6 };
+enum OpKind { OP_CSR = 1, OP_DIRAC = 2, OP_BCSR = 3, OP_GCR = 4, OP_MG = 5, OP_DIRAC_MULTI = 6, OP_DIRAC_EO = 7 };
 
 // ELL slab + CSR tail (int32 indices).
 //   ELL: W = nchunk*L entries per row, L lanes co-operate on a row.
@@ -159,6 +159,7 @@ struct GcrState;
 struct MgState;
 struct Comm;
 struct DistCsr;
+struct EoState;
 
 struct Op {
     OpKind kind;
@@ -171,6 +172,7 @@ struct Op {
     BcsrDev bcsr;        // OP_BCSR
     GcrState *gcr = nullptr;  // OP_GCR
     MgState *mg = nullptr;    // OP_MG
+    EoState *eo = nullptr;    // OP_DIRAC_EO: the Schur complement 1 - k^2 D_eo D_oe on the even half (evenodd.hip; owned)
     DistCsr *dist = nullptr;  // OP_CSR / OP_BCSR row block of a distributed matrix (halo.hip; owned)
     Comm *comm = nullptr;     // communicator the operator's Fields are distributed over (borrowed)
 };
@@ -181,6 +183,11 @@ inline const Op *op_matrix(const Op *op) { return op && (op->kind == OP_DIRAC ||
 #define MGCR_REFUSE_MULTI_DIRAC(op, who)                                                                                              \
     MGCR_CHECK(!(op) || (op)->kind != OP_DIRAC_MULTI, MGCR_ERR_UNSUPPORTED,                                                           \
                "%s: a MultiDiracOp has one hopping parameter per column of a block; only mgcr_op_apply_multi and mgcr_gcr_solve_multi take it", who)
+
+// ... and the block, queue and multigrid entry points' answer to an even-odd preconditioned DiracOp
+#define MGCR_REFUSE_EVENODD(op, who)                                                                                                  \
+    MGCR_CHECK(!(op) || (op)->kind != OP_DIRAC_EO, MGCR_ERR_UNSUPPORTED,                                                              \
+               "%s: an even-odd preconditioned DiracOp acts on single Fields of its even half only", who)
 
 // ---- blas1.hip -------------------------------------------------------------------------------
 int red_grid(int64_t n);
@@ -298,6 +305,7 @@ bool one_launch_paths_enabled();       // either of the two above
 int csr_apply(const CsrDev &A, const cplx *x, cplx *y, bool shift, cplx k, DistCsr *dist = nullptr, const cplx *w = nullptr);
 // SpMV fused with <y, v_j> partials (gcr_fused.hip); parts laid out like gcr.hip's partsB, red_grid(nrow) partials each
 bool csr_fusable(const CsrDev &A, const DistCsr *dist);
+bool fuse_enabled();   // the option fused_apply
 struct RowMap;  // gcr_dev.h
 struct PwTail;  // pw_tail_dev.h
 bool csr_step_apply_has_pw_tail(const CsrDev &A, const DistCsr *dist);
@@ -397,6 +405,16 @@ void gcr_state_set_use_x0(GcrState *s, bool use_x0);
 int gcr_state_set_param(GcrState *s, const mgcr_gcr_param *p);
 int gcr_apply_as_operator(GcrState *s, const cplx *f, cplx *y);
 void gcr_last_profile(double *phase_ms_total, int *n_iter, int *fused);
+
+// ---- evenodd.hip: the even-odd preconditioned DiracOp (OP_DIRAC_EO) -------------------------------
+void eo_destroy(EoState *e);
+int64_t eo_nnz(const EoState *e);
+int64_t eo_fused_step_count();   // GCR steps whose stage 2 took the beta dot products (schur_step_apply_kernel)
+int eo_apply(Op *op, const cplx *x, cplx *y, int64_t n);   // y = S x = x - k^2 D_eo (D_oe x), two launches
+// stage 2 of a GCR step fused with the step's beta dot products (schur_step_apply_kernel): exists for a D_eo stored one thread per row
+bool eo_schur_fusable(const Op *op);
+// t = D_oe x, then y = x - k^2 D_eo t with the partials of <y, vecs_j>, j < nd <= FND, laid out like gcr.hip's partsB
+int eo_schur_step(Op *op, const cplx *x, cplx *y, const cplx *const *vecs, int nd, double *parts, const RowMap &rm);
 
 // ---- mvec.hip / spmm.hip / gcr_multi.hip: blocks of k Fields ------------------------------------
 int mv_copy(cplx *dst, const cplx *src, int64_t n, int k);
