@@ -167,6 +167,40 @@ int mgcr_eo_merge(mgcr_op_t eo, mgcr_vec_t even, mgcr_vec_t odd, mgcr_vec_t full
 int mgcr_eo_prepare(mgcr_op_t eo, mgcr_vec_t b_full, mgcr_vec_t bhat_even);
 int mgcr_eo_reconstruct(mgcr_op_t eo, mgcr_vec_t b_full, mgcr_vec_t x_even, mgcr_vec_t x_full);
 /* (mgcr_eo_solve is declared below, with the solver entry points) */
+/* MultiEvenOddDiracOp, even-odd hopping-parameter scans: the Schur complements S_j = 1 - k_j^2 D_eo D_oe on column j of a block of
+ * exactly nk Fields of the even half (mgcr_op_dim = mgcr_op_nrow = n_e, mgcr_op_nnz = that of D).  The fewer steps of the even-odd
+ * solve and the shared matrix stream and launches of the batched solve in one operator.  It BORROWS the two half matrices and the
+ * index lists of `eo`, an EvenOddDiracOp, which must outlive it; nothing is copied or planned again, and eo's own k is not used.
+ * k_ri: [nk][2], 1 <= nk <= 16.  nk outside 1 .. 16, a zero k_j ("No k value supplied"), an `eo` that is no EvenOddDiracOp:
+ * MGCR_ERR_INVALID.  mgcr_eo_multi_set_k replaces all nk values.  The values and their squares (formed on the host, as
+ * mgcr_eo_set_k forms its one) travel in the kernel arguments of each launch: they hold for every later call and never for work
+ * already enqueued.
+ * Accepted by: mgcr_op_apply_multi (blocks of n_e rows x nk columns), mgcr_bench_op_apply_multi, mgcr_gcr_solve_multi (the nk Schur
+ * systems, under that entry point's restrictions), mgcr_op_destroy / dim / nrow / nnz, and the mgcr_eo_multi entry points: split,
+ * merge, prepare and reconstruct are mgcr_eo_split ... mgcr_eo_reconstruct on blocks of nk columns (full blocks have n rows, even
+ * ones n_e, odd ones n_o), and mgcr_eo_multi_solve = prepare, mgcr_gcr_solve_multi(S, param, Bhat_e, X_e), reconstruct, with X_e the
+ * even half of X_full on entry and use_x0 as in mgcr_eo_solve; hist: [nk][hist_cap], row j relative to |bhat_e,j|; n_iter,
+ * converged: [nk].  The operator keeps its work blocks (the batched solver's storage is the library's, see mgcr_gcr_solve_multi).
+ * MGCR_ERR_UNSUPPORTED, with a message naming the kind, from: mgcr_op_apply, mgcr_bench_op_apply, mgcr_gcr_solve, mgcr_gcr_create,
+ * mgcr_gcr_set_operator, mgcr_gcr_solve_queue, mgcr_mg_create and the storage queries (stored_bytes / storage_format / ell_layout /
+ * xr_fuse_kind / halo_kind; ask the halves of `eo`).  A block of another width or length, blocks that alias: MGCR_ERR_INVALID.
+ * The plain EvenOddDiracOp goes on refusing the block, queue and multigrid entry points.
+ * Rule 1: column j of mgcr_op_apply_multi, mgcr_eo_multi_prepare, mgcr_eo_multi_reconstruct, mgcr_eo_multi_split and
+ * mgcr_eo_multi_merge is BIT-IDENTICAL to mgcr_op_apply, mgcr_eo_prepare, mgcr_eo_reconstruct, mgcr_eo_split and mgcr_eo_merge on
+ * column j with EvenOddDiracOp(D, k_j), in every storage form of the halves.
+ * Rule 2: history, iteration count, convergence flag and x of column j of mgcr_gcr_solve_multi on the operator are BIT-IDENTICAL
+ * to mgcr_gcr_solve on EvenOddDiracOp(D, k_j) with column j alone, and those of mgcr_eo_multi_solve to mgcr_eo_solve — at ANY size:
+ * the single Schur solve never takes a one-workgroup or one-launch path, so the small-size exception of the MultiDiracOp's Rule 2
+ * does not arise.  The batched cycle takes the beta dot products in passes of their own; the single solve's fused second stage
+ * has their bits.
+ * Out of scope: the queue on the Schur system, distributed halves, operators with a diagonal. */
+int mgcr_eo_multi_create(mgcr_op_t eo, int32_t nk, const double *k_ri /* [nk][2] */, mgcr_op_t *out);
+int mgcr_eo_multi_set_k(mgcr_op_t op, const double *k_ri /* [nk][2] */);
+int mgcr_eo_multi_split(mgcr_op_t op, mgcr_mvec_t full, mgcr_mvec_t even, mgcr_mvec_t odd);
+int mgcr_eo_multi_merge(mgcr_op_t op, mgcr_mvec_t even, mgcr_mvec_t odd, mgcr_mvec_t full);
+int mgcr_eo_multi_prepare(mgcr_op_t op, mgcr_mvec_t B_full, mgcr_mvec_t Bhat_even);
+int mgcr_eo_multi_reconstruct(mgcr_op_t op, mgcr_mvec_t B_full, mgcr_mvec_t X_even, mgcr_mvec_t X_full);
+/* (mgcr_eo_multi_solve is declared below, with the solver entry points) */
 /* HierarchicalSparse<long,int> (block-CSR of dense bs x bs blocks, row-major inside a block,
  * src/HierarchicalSparse.h:22-48) from UNSORTED (block-row, block-col, block) triplets with the
  * constructor's semantics (:58-98): sorted by row*nbcol+col, duplicates of a pair kept and
@@ -187,7 +221,7 @@ int mgcr_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y);
  * mgcr_op_apply on column j: per column the kernels add a row's products in the order mgcr_op_ell_layout documents (block-CSR:
  * per block in column order, blocks in storage order), whichever storage form carries the matrix.  Supported: single-GPU
  * Sparse in every storage form (ELL slab + CSR tail with 1 .. 16 lanes per row, the LDS-window variant, both row-pattern
- * dictionary forms, the stencil view), DiracOp and MultiDiracOp on top of any of them, HierarchicalSparse / Dense.  Distributed operators
+ * dictionary forms, the stencil view), DiracOp and MultiDiracOp on top of any of them, MultiEvenOddDiracOp (blocks of its even half), HierarchicalSparse / Dense.  Distributed operators
  * and GCR / MG objects: MGCR_ERR_UNSUPPORTED.  X == Y, mismatched n or k: MGCR_ERR_INVALID.
  * Block-CSR stages min(k, 64 / bs) (at least 1) columns of products and k columns of accumulators in LDS,
  * 16 (kg bs (bs + 1) + bs k) bytes: block sizes for which that exceeds 160 KiB (bs from about 95, depending on k) are
@@ -296,6 +330,9 @@ int mgcr_gcr_solve(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_vec_t rhs, mgc
 /* The even-odd preconditioned solve of (1 - k D) x_full = b_full: see mgcr_eo_create. */
 int mgcr_eo_solve(mgcr_op_t eo, const mgcr_gcr_param *param, mgcr_vec_t b_full, mgcr_vec_t x_full,
                   double *hist, int32_t hist_cap, int32_t *n_iter, int32_t *converged);
+/* The batched even-odd preconditioned solves of (1 - k_j D) x_full,j = b_full,j: see mgcr_eo_multi_create. */
+int mgcr_eo_multi_solve(mgcr_op_t op, const mgcr_gcr_param *param, mgcr_mvec_t B_full, mgcr_mvec_t X_full,
+                        double *hist /* [nk][hist_cap] */, int32_t hist_cap, int32_t *n_iter, int32_t *converged);
 /* k independent solves A x_j = rhs_j that share every launch (batched restarted GCR, csrc/gcr_multi.hip).
  * hist: [k][hist_cap] (may be NULL), row j as mgcr_gcr_solve fills it for column j; n_iter, converged: [k] (may be NULL).
  * Every column has its own device-resident scalars and stop flag; a column that has stopped (|r|^2/|b|^2 <= tol^2, or

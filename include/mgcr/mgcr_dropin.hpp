@@ -950,6 +950,88 @@ private:
     mgcr_op_t op = nullptr;
 };
 
+// MultiEvenOddDiracOp: the Schur complements Id - ks[j]^2 D_eo D_oe of ONE hopping matrix on column j of a block of ks.size() Fields
+// of the even half — an even-odd hopping-parameter scan as one operator (extension, mgcr_eo_multi_create).  Borrows the halves and
+// index lists of `eo`, which must outlive it; eo's own k is not used.  apply_multi, GCR::solve_multi and the methods below take it,
+// with MultiFields of exactly ncols() columns; column j has the bits of EvenOddDiracOp(D, ks[j]) on that column alone.  solve() runs
+// prepare -> batched GCR -> reconstruct on full-system MultiFields and keeps, per column, the Schur solve's history (relative to
+// |bhat_e,j|), iteration count and flag.
+template <typename num_type>
+class MultiEvenOddDiracOp : public Operator<num_type> {
+public:
+    MultiEvenOddDiracOp(EvenOddDiracOp<num_type> *eo_op, std::vector<std::complex<double>> k_factors) : ks(std::move(k_factors)), eo(eo_op) {
+        mgcr_detail::ok(mgcr_eo_multi_create(eo->handle(), (int32_t)ks.size(), reinterpret_cast<const double *>(ks.data()), &op), "MultiEvenOddDiracOp");
+        this->dim = eo->get_n_even();
+    }
+    MultiEvenOddDiracOp(MultiEvenOddDiracOp const &) = delete;
+    MultiEvenOddDiracOp &operator=(MultiEvenOddDiracOp const &) = delete;
+    ~MultiEvenOddDiracOp() override { if (op) mgcr_op_destroy(op); }
+    int ncols() const { return (int)ks.size(); }
+    std::complex<double> val_at(num_type, num_type) const override { return no_single("val_at"); }
+    std::complex<double> val_at(num_type) const override { return no_single("val_at"); }
+    Field<num_type> operator()(Field<num_type> const &f) override { no_single("operator()"); return f; }
+    mgcr_op_t handle() override { return op; }
+    void set_k(std::vector<std::complex<double>> new_ks) {   // same count; holds for every later call, never for enqueued work
+        if (new_ks.size() != ks.size()) { std::fprintf(stderr, "MultiEvenOddDiracOp::set_k: %zu values for %zu columns\n", new_ks.size(), ks.size()); std::abort(); }
+        ks = std::move(new_ks);
+        mgcr_detail::ok(mgcr_eo_multi_set_k(op, reinterpret_cast<const double *>(ks.data())), "MultiEvenOddDiracOp::set_k");
+    }
+    num_type get_n() const { return eo->get_n(); }
+    num_type get_n_even() const { return eo->get_n_even(); }
+    num_type get_n_odd() const { return eo->get_n_odd(); }
+    void split(const MultiField<num_type> &full, MultiField<num_type> &even, MultiField<num_type> &odd) {
+        mgcr_detail::ok(mgcr_eo_multi_split(op, full.device(), even.device(), odd.device()), "MultiEvenOddDiracOp::split");
+    }
+    void merge(const MultiField<num_type> &even, const MultiField<num_type> &odd, MultiField<num_type> &full) {
+        mgcr_detail::ok(mgcr_eo_multi_merge(op, even.device(), odd.device(), full.device()), "MultiEvenOddDiracOp::merge");
+    }
+    MultiField<num_type> prepare(const MultiField<num_type> &rhs_full) {   // bhat_e,j = b_e,j + ks[j] D_eo b_o,j
+        num_type ne = eo->get_n_even();
+        MultiField<num_type> out(Mesh<num_type>(&ne, 1), ncols());
+        mgcr_detail::ok(mgcr_eo_multi_prepare(op, rhs_full.device(), out.device()), "MultiEvenOddDiracOp::prepare");
+        return out;
+    }
+    MultiField<num_type> reconstruct(const MultiField<num_type> &rhs_full, const MultiField<num_type> &x_even) {   // x_o,j = b_o,j + ks[j] D_oe x_e,j, merged
+        MultiField<num_type> out(rhs_full.get_mesh(), ncols());
+        mgcr_detail::ok(mgcr_eo_multi_reconstruct(op, rhs_full.device(), x_even.device(), out.device()), "MultiEvenOddDiracOp::reconstruct");
+        return out;
+    }
+    // (Id - ks[j] D) x_full,j = rhs_full,j for every column through ONE batched solve of the Schur systems (restart mode, unpreconditioned)
+    void solve(const MultiField<num_type> &rhs_full, MultiField<num_type> &x_full, GCR_Param<num_type> *param) {
+        if (param->truncation != 0 && param->restart != 0) { std::fprintf(stderr, "Do not support concurrent restarting and truncation.\n"); std::abort(); }
+        mgcr_gcr_param p;
+        std::memset(&p, 0, sizeof(p));
+        p.truncation = param->truncation; p.restart = param->restart; p.max_iter = param->max_iter; p.tol = param->tol;
+        p.verbose = param->verbose ? 1 : 0;
+        p.left_precond = param->left_precond ? param->left_precond->handle() : nullptr;
+        p.right_precond = param->right_precond ? param->right_precond->handle() : nullptr;
+        p.use_x0 = param->use_x0; p.flexible = param->flexible;
+        const int k = ncols(), cap = (param->max_iter > 0 ? param->max_iter : 1) + 1;
+        std::vector<double> hist((size_t)k * cap, 0.);
+        std::vector<int32_t> it((size_t)k, 0), conv((size_t)k, 0);
+        mgcr_detail::ok(mgcr_eo_multi_solve(op, &p, rhs_full.device(), x_full.device(), hist.data(), cap, it.data(), conv.data()), "MultiEvenOddDiracOp::solve");
+        last_history.assign((size_t)k, std::vector<double>());
+        last_iterations.assign(it.begin(), it.end());
+        last_converged.assign((size_t)k, false);
+        for (int j = 0; j < k; j++) {
+            last_history[(size_t)j].assign(hist.begin() + (size_t)j * cap, hist.begin() + (size_t)j * cap + it[(size_t)j] + 1);
+            last_converged[(size_t)j] = conv[(size_t)j] != 0;
+        }
+    }
+    std::vector<std::vector<double>> last_history;   // of the Schur solves, column j relative to |bhat_e,j|
+    std::vector<int> last_iterations;
+    std::vector<bool> last_converged;
+
+private:
+    static std::complex<double> no_single(const char *what) {
+        std::fprintf(stderr, "MultiEvenOddDiracOp::%s: one hopping parameter per column of a block; use apply_multi / GCR::solve_multi / solve\n", what);
+        std::abort();
+    }
+    std::vector<std::complex<double>> ks;
+    EvenOddDiracOp<num_type> *eo;
+    mgcr_op_t op = nullptr;
+};
+
 // ------------------------------------------------------------------------------------------------
 // MG — src/MG.h:20-61.  operator() is the corrected V-cycle of DESIGN.md (the reference's returns
 // uninitialised memory, src/MG.h:124-129).

@@ -148,6 +148,13 @@ _SIGS = {
     "mgcr_eo_prepare": (C.c_int, [_vp, _vp, _vp]),
     "mgcr_eo_reconstruct": (C.c_int, [_vp, _vp, _vp, _vp]),
     "mgcr_eo_solve": (C.c_int, [_vp, C.POINTER(GcrParamC), _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mgcr_eo_multi_create": (C.c_int, [_vp, C.c_int32, _dp, C.POINTER(_vp)]),
+    "mgcr_eo_multi_set_k": (C.c_int, [_vp, _dp]),
+    "mgcr_eo_multi_split": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "mgcr_eo_multi_merge": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "mgcr_eo_multi_prepare": (C.c_int, [_vp, _vp, _vp]),
+    "mgcr_eo_multi_reconstruct": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "mgcr_eo_multi_solve": (C.c_int, [_vp, C.POINTER(GcrParamC), _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mgcr_timer_start": (C.c_int, []),
     "mgcr_timer_stop": (C.c_int, [_dp]),
 }

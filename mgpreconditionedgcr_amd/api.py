@@ -513,6 +513,76 @@ class EvenOddDiracOp(Operator):
         return x_full
 
 
+class MultiEvenOddDiracOp(Operator):
+    """The Schur complements Id - ks[j]^2 D_eo D_oe of ONE hopping matrix on column j of a block of len(ks) Fields of the even
+    half: an even-odd hopping-parameter scan as one operator (mgcr_eo_multi_create; no reference counterpart).  Borrows the halves
+    and index lists of `eo`, an EvenOddDiracOp, and keeps it alive; eo's own k is not used.  apply_multi, GCR(...).solve_multi and
+    the methods below take it, with MultiFields of exactly ncols columns; column j has the bits of EvenOddDiracOp(D, ks[j]) on
+    that column alone."""
+
+    def __init__(self, eo, ks):
+        super().__init__()
+        kv = MultiDiracOp._values(ks)
+        h = C.c_void_p()
+        check(_lib.lib().mgcr_eo_multi_create(eo.h, kv.shape[0], kv.ctypes.data_as(C.POINTER(C.c_double)), C.byref(h)))
+        self.h = h
+        self.ncols = int(kv.shape[0])
+        self.eo = eo
+        self._keep.append(eo)
+        self.last_history = None
+        self.last_iterations = None
+        self.last_converged = None
+
+    def set_k(self, ks):
+        """Replace all ncols values; takes effect for every later call, never for work already enqueued."""
+        kv = MultiDiracOp._values(ks)
+        if kv.shape[0] != self.ncols:
+            raise MgcrError(1, "MultiEvenOddDiracOp.set_k: %d values for %d columns" % (kv.shape[0], self.ncols))
+        check(_lib.lib().mgcr_eo_multi_set_k(self.h, kv.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def sizes(self):
+        """(n, n_even, n_odd)"""
+        return self.eo.sizes()
+
+    def split(self, full, even=None, odd=None):
+        _, ne, no = self.sizes()
+        even = MultiField((ne,), self.ncols) if even is None else even
+        odd = MultiField((no,), self.ncols) if odd is None else odd
+        check(_lib.lib().mgcr_eo_multi_split(self.h, full.h, even.h, odd.h))
+        return even, odd
+
+    def merge(self, even, odd, full=None):
+        full = MultiField((self.sizes()[0],), self.ncols) if full is None else full
+        check(_lib.lib().mgcr_eo_multi_merge(self.h, even.h, odd.h, full.h))
+        return full
+
+    def prepare(self, rhs_full, bhat_even=None):
+        """bhat_e,j = b_e,j + ks[j] D_eo b_o,j"""
+        bhat_even = MultiField((self.sizes()[1],), self.ncols) if bhat_even is None else bhat_even
+        check(_lib.lib().mgcr_eo_multi_prepare(self.h, rhs_full.h, bhat_even.h))
+        return bhat_even
+
+    def reconstruct(self, rhs_full, x_even, x_full=None):
+        """x_o,j = b_o,j + ks[j] D_oe x_e,j, merged with x_e,j"""
+        x_full = MultiField(rhs_full.dims, self.ncols) if x_full is None else x_full
+        check(_lib.lib().mgcr_eo_multi_reconstruct(self.h, rhs_full.h, x_even.h, x_full.h))
+        return x_full
+
+    def solve(self, RHS_full, X_full, gcr_param):
+        """(Id - ks[j] D) x_full,j = rhs_full,j for every column through ONE batched solve of the Schur systems; histories (relative
+        to |bhat_e,j|), iteration counts and flags are kept per column in last_history / last_iterations / last_converged."""
+        k = self.ncols
+        cap = max(gcr_param.max_iter, 1) + 1
+        hist = np.zeros((k, cap), np.float64)
+        it, conv = (C.c_int32 * k)(), (C.c_int32 * k)()
+        pc = gcr_param._c()
+        check(_lib.lib().mgcr_eo_multi_solve(self.h, C.byref(pc), RHS_full.h, X_full.h, hist.ctypes.data, cap, it, conv))
+        self.last_iterations = [int(v) for v in it]
+        self.last_converged = [bool(v) for v in conv]
+        self.last_history = [hist[j, : it[j] + 1].copy() for j in range(k)]
+        return X_full
+
+
 class HierarchicalSparse(Operator):
     """HierarchicalSparse<long,int> (src/HierarchicalSparse.h:22-48) from unsorted
     (block_row, block_col, dense block) triplets, duplicates kept (ctor :58-98)."""
@@ -563,6 +633,9 @@ class Dense(HierarchicalSparse):
         return Dense(hostalg.dense_dagger(self.mat))
 
 
+_BLOCK_ONLY = (MultiDiracOp, MultiEvenOddDiracOp)   # operators of the block entry points only
+
+
 class GCR_Param:
     """GCR_Param(trunc, re, max_it, tau, verb, solver_l, solver_r) (src/SolverParam.h:21-35,85-99)."""
 
@@ -593,9 +666,9 @@ class GCR(Operator):
         self.A = M
         h = C.c_void_p()
         pc = gcr_param._c()
-        # (a MultiDiracOp serves solve_multi only, which takes the operator from self.A: the single-Field solver object is made
-        # without one, and solve / operator() answer as the C entry points do)
-        single = M is not None and not isinstance(M, MultiDiracOp)
+        # (a MultiDiracOp or MultiEvenOddDiracOp serves solve_multi only, which takes the operator from self.A: the single-Field
+        # solver object is made without one, and solve / operator() answer as the C entry points do)
+        single = M is not None and not isinstance(M, _BLOCK_ONLY)
         check(_lib.lib().mgcr_gcr_create(M.h if single else None, C.byref(pc), x0_mode, C.byref(h)))
         self.h = h
         self._keep += [M, gcr_param, gcr_param.left_precond, gcr_param.right_precond]
@@ -606,12 +679,12 @@ class GCR(Operator):
     def initialise(self, M):  # src/GCR.h:31
         self.A = M
         self._keep.append(M)
-        if not isinstance(M, MultiDiracOp):
+        if not isinstance(M, _BLOCK_ONLY):
             check(_lib.lib().mgcr_gcr_set_operator(self.h, M.h))
 
     def _single_field_only(self, who):
-        if isinstance(self.A, MultiDiracOp):
-            raise MgcrError(7, "%s: a MultiDiracOp has one hopping parameter per column of a block; use solve_multi" % who)
+        if isinstance(self.A, _BLOCK_ONLY):
+            raise MgcrError(7, "%s: a %s has one hopping parameter per column of a block; use solve_multi" % (who, type(self.A).__name__))
 
     def __call__(self, f, out=None):
         self._single_field_only("GCR as an operator")

@@ -161,6 +161,7 @@ int mgcr_op_destroy(mgcr_op_t op) {
         case OP_GCR: gcr_state_destroy(op->gcr); break;
         case OP_MG: mg_destroy(op->mg); break;
         case OP_DIRAC_EO: eo_destroy(op->eo); break;
+        case OP_DIRAC_EO_MULTI: eo_multi_destroy(op->eom); break;   // (the even-odd operator behind it is borrowed)
         default: break;  // OP_DIRAC and OP_DIRAC_MULTI borrow their Sparse (src/Operator.h:117,555-560)
     }
     delete op;
@@ -177,12 +178,14 @@ int64_t mgcr_op_nnz(mgcr_op_t op) {
         case OP_DIRAC_MULTI: return op->base->csr.nnz;
         case OP_BCSR: return (int64_t)op->bcsr.nblocks * op->bcsr.bs * op->bcsr.bs;  // src/HierarchicalSparse.h:31
         case OP_DIRAC_EO: return eo_nnz(op->eo);   // that of D
+        case OP_DIRAC_EO_MULTI: return eo_multi_nnz(op->eom);
         default: return -1;
     }
 }
 
 int mgcr_op_storage_format(mgcr_op_t op, int32_t *format, int32_t *n_patterns) {
     MGCR_CHECK(op, MGCR_ERR_INVALID, "null operator");
+    MGCR_REFUSE_EVENODD_MULTI(op, "mgcr_op_storage_format");
     const Op *o = op_matrix(op);
     MGCR_CHECK(o->kind == OP_CSR, MGCR_ERR_UNSUPPORTED, "mgcr_op_storage_format: not a Sparse");
     if (format) *format = csr_stencil_active(o->csr) ? 3 : o->csr.pat_mode;
@@ -193,6 +196,7 @@ int mgcr_op_storage_format(mgcr_op_t op, int32_t *format, int32_t *n_patterns) {
 int mgcr_op_ell_layout(mgcr_op_t op, int32_t *ell_width, int32_t *lanes, int64_t *tail_rows, int64_t *reach, int32_t *tail_chunk_cap,
                        int32_t *x_window) {
     MGCR_CHECK(op, MGCR_ERR_INVALID, "null operator");
+    MGCR_REFUSE_EVENODD_MULTI(op, "mgcr_op_ell_layout");
     const Op *o = op_matrix(op);
     MGCR_CHECK(o->kind == OP_CSR, MGCR_ERR_UNSUPPORTED, "mgcr_op_ell_layout: not a Sparse");
     if (ell_width) *ell_width = o->csr.W;
@@ -206,6 +210,7 @@ int mgcr_op_ell_layout(mgcr_op_t op, int32_t *ell_width, int32_t *lanes, int64_t
 
 int mgcr_op_xr_fuse_kind(mgcr_op_t op, int32_t *kind) {
     MGCR_CHECK(op && kind, MGCR_ERR_INVALID, "mgcr_op_xr_fuse_kind: null argument");
+    MGCR_REFUSE_EVENODD_MULTI(op, "mgcr_op_xr_fuse_kind");
     const Op *o = op_matrix(op);
     MGCR_CHECK(o->kind == OP_CSR, MGCR_ERR_UNSUPPORTED, "mgcr_op_xr_fuse_kind: not a Sparse");
     *kind = csr_fusable(o->csr, o->dist) ? csr_xr_fuse_kind(o->csr, o->dist) : 0;
@@ -214,6 +219,7 @@ int mgcr_op_xr_fuse_kind(mgcr_op_t op, int32_t *kind) {
 
 int mgcr_op_halo_kind(mgcr_op_t op, int32_t *kind) {
     MGCR_CHECK(op && kind, MGCR_ERR_INVALID, "mgcr_op_halo_kind: null argument");
+    MGCR_REFUSE_EVENODD_MULTI(op, "mgcr_op_halo_kind");
     const Op *o = op_matrix(op);
     MGCR_CHECK(o->dist, MGCR_ERR_UNSUPPORTED, "mgcr_op_halo_kind: not a distributed Sparse");
     *kind = dist_halo_kind(o->dist);
@@ -277,6 +283,7 @@ int mgcr_selftest_coherence(int32_t steps, int32_t coherent, int64_t *rows_wrong
 
 int mgcr_op_stored_bytes(mgcr_op_t op, int64_t *matrix_bytes, int32_t *ell_width, int64_t *tail_nnz) {
     MGCR_CHECK(op, MGCR_ERR_INVALID, "null operator");
+    MGCR_REFUSE_EVENODD_MULTI(op, "mgcr_op_stored_bytes");
     const Op *o = op_matrix(op);
     if (o->kind == OP_CSR) {
         const CsrDev &A = o->csr;
@@ -305,6 +312,7 @@ int mgcr_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y) {
     MGCR_TRY(require_ctx());
     MGCR_CHECK(op && x && y, MGCR_ERR_INVALID, "mgcr_op_apply: null argument");
     MGCR_REFUSE_MULTI_DIRAC(op, "mgcr_op_apply");
+    MGCR_REFUSE_EVENODD_MULTI(op, "mgcr_op_apply");
     MGCR_CHECK(x->n == op->dim, MGCR_ERR_INVALID, "Sparse matrix dimension does not match Field dimension!");
     int64_t nrow = op->nrow ? op->nrow : op->dim;
     MGCR_CHECK(y->n == nrow, MGCR_ERR_INVALID, "output Field has %lld entries, operator has %lld rows", (long long)y->n, (long long)nrow);
@@ -320,6 +328,7 @@ int mgcr_gcr_solve(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_vec_t rhs, mgc
     MGCR_TRY(require_ctx());
     MGCR_CHECK(A && param && rhs && x, MGCR_ERR_INVALID, "mgcr_gcr_solve: null argument");
     MGCR_REFUSE_MULTI_DIRAC(A, "mgcr_gcr_solve");
+    MGCR_REFUSE_EVENODD_MULTI(A, "mgcr_gcr_solve");
     // assertm(rhs.field_size() == this->dim, ...) src/GCR.h:160-161
     MGCR_CHECK(rhs->n == A->dim, MGCR_ERR_INVALID, "Field dimension does not match with Operator!");
     MGCR_CHECK(x->n == A->dim, MGCR_ERR_INVALID, "x dimension does not match with Operator!");
@@ -340,6 +349,7 @@ int mgcr_gcr_create(mgcr_op_t A, const mgcr_gcr_param *param, int32_t x0_mode, m
     MGCR_TRY(require_ctx());
     MGCR_CHECK(param && out, MGCR_ERR_INVALID, "mgcr_gcr_create: null argument");
     MGCR_REFUSE_MULTI_DIRAC(A, "mgcr_gcr_create");
+    MGCR_REFUSE_EVENODD_MULTI(A, "mgcr_gcr_create");
     LOCK();
     mgcr_op_s *op = new mgcr_op_s();
     op->kind = OP_GCR;
@@ -354,6 +364,7 @@ int mgcr_gcr_create(mgcr_op_t A, const mgcr_gcr_param *param, int32_t x0_mode, m
 int mgcr_gcr_set_operator(mgcr_op_t gcr, mgcr_op_t A) {
     MGCR_CHECK(gcr && A && gcr->kind == OP_GCR, MGCR_ERR_INVALID, "mgcr_gcr_set_operator: not a GCR operator");
     MGCR_REFUSE_MULTI_DIRAC(A, "mgcr_gcr_set_operator");
+    MGCR_REFUSE_EVENODD_MULTI(A, "mgcr_gcr_set_operator");
     LOCK();
     gcr->dim = A->dim;  // GCR::initialise src/GCR.h:31
     gcr->nrow = A->dim;
@@ -408,6 +419,7 @@ int mgcr_bench_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y, int32_t reps, 
     MGCR_TRY(require_ctx());
     MGCR_CHECK(op && x && y && reps > 0 && ms_avg, MGCR_ERR_INVALID, "mgcr_bench_op_apply: bad argument");
     MGCR_REFUSE_MULTI_DIRAC(op, "mgcr_bench_op_apply");
+    MGCR_REFUSE_EVENODD_MULTI(op, "mgcr_bench_op_apply");
     LOCK();
     Context &c = ctx();
     MGCR_TRY(mgcr_op_apply(op, x, y));  // warm-up (and argument checks)
@@ -434,6 +446,8 @@ static int apply_multi_checks(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y, const 
     MGCR_CHECK(x->k == y->k, MGCR_ERR_INVALID, "%s: input has %d columns, output has %d", who, (int)x->k, (int)y->k);
     MGCR_CHECK(op->kind != OP_DIRAC_MULTI || x->k == op->nk, MGCR_ERR_INVALID, "%s: the MultiDiracOp carries %d hopping parameters, the block has %d columns",
                who, op->nk, (int)x->k);
+    MGCR_CHECK(op->kind != OP_DIRAC_EO_MULTI || x->k == op->nk, MGCR_ERR_INVALID,
+               "%s: the MultiEvenOddDiracOp carries %d hopping parameters, the block has %d columns", who, op->nk, (int)x->k);
     MGCR_CHECK(x != y && (x->d != y->d || !x->d), MGCR_ERR_INVALID, "%s: input and output must be different blocks", who);
     return MGCR_OK;
 }
@@ -484,6 +498,8 @@ int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t r
     MGCR_CHECK(rhs != x && (rhs->d != x->d || !x->d), MGCR_ERR_INVALID, "rhs and x must be different blocks");
     MGCR_CHECK(A->kind != OP_DIRAC_MULTI || x->k == A->nk, MGCR_ERR_INVALID,
                "mgcr_gcr_solve_multi: the MultiDiracOp carries %d hopping parameters, the blocks have %d columns", A->nk, (int)x->k);
+    MGCR_CHECK(A->kind != OP_DIRAC_EO_MULTI || x->k == A->nk, MGCR_ERR_INVALID,
+               "mgcr_gcr_solve_multi: the MultiEvenOddDiracOp carries %d hopping parameters, the blocks have %d columns", A->nk, (int)x->k);
     LOCK();
     return gcr_multi_run(A, *param, rhs->d, x->d, x->n, x->k, hist, hist_cap, n_iter, converged);
 }
@@ -494,6 +510,7 @@ int mgcr_gcr_solve_queue(mgcr_op_t A, const mgcr_gcr_param *param, int32_t width
     MGCR_TRY(require_ctx());
     MGCR_CHECK(A && param && rhs && x, MGCR_ERR_INVALID, "%s: null argument", who);
     MGCR_REFUSE_EVENODD(A, who);
+    MGCR_REFUSE_EVENODD_MULTI(A, who);
     MGCR_CHECK(param->truncation >= 0 && param->restart >= 0 && param->max_iter >= 0, MGCR_ERR_INVALID, "negative GCR parameter");
     MGCR_CHECK(param->truncation == 0, MGCR_ERR_UNSUPPORTED, "%s: truncation mode is not supported (restart mode only)", who);
     MGCR_CHECK(param->restart != 0, MGCR_ERR_UNSUPPORTED, "%s: restart mode only (restart != 0)", who);

@@ -712,6 +712,9 @@ int op_apply_raw(Op *op, const cplx *x, cplx *y, int64_t n) {
         case OP_DIRAC_MULTI:   // (reached through a preconditioner slot; the entry points refuse it themselves)
             set_error("a MultiDiracOp has one hopping parameter per column of a block and cannot be applied to a single Field");
             return MGCR_ERR_UNSUPPORTED;
+        case OP_DIRAC_EO_MULTI:   // (likewise)
+            set_error("a MultiEvenOddDiracOp has one hopping parameter per column of a block and cannot be applied to a single Field");
+            return MGCR_ERR_UNSUPPORTED;
         default:
             set_error("operator kind %d cannot be applied", (int)op->kind);
             return MGCR_ERR_UNSUPPORTED;

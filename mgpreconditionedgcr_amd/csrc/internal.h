@@ -83,7 +83,7 @@ struct MVec {
 };
 constexpr int MV_MAX_K = 16;
 
-enum OpKind { OP_CSR = 1, OP_DIRAC = 2, OP_BCSR = 3, OP_GCR = 4, OP_MG = 5, OP_DIRAC_MULTI = 6, OP_DIRAC_EO = 7 };
+enum OpKind { OP_CSR = 1, OP_DIRAC = 2, OP_BCSR = 3, OP_GCR = 4, OP_MG = 5, OP_DIRAC_MULTI = 6, OP_DIRAC_EO = 7, OP_DIRAC_EO_MULTI = 8 };
 
 // ELL slab + CSR tail (int32 indices).
 //   ELL: W = nchunk*L entries per row, L lanes co-operate on a row.
@@ -160,6 +160,7 @@ struct MgState;
 struct Comm;
 struct DistCsr;
 struct EoState;
+struct EoMultiState;
 
 struct Op {
     OpKind kind;
@@ -167,12 +168,14 @@ struct Op {
     CsrDev csr;          // OP_CSR
     Op *base = nullptr;  // OP_DIRAC / OP_DIRAC_MULTI: borrowed CSR
     cplx k = {0., 0.};   // OP_DIRAC
-    int nk = 0;          // OP_DIRAC_MULTI: 1 - ks[j] D on column j of a block of exactly nk columns (block entry points only)
+    int nk = 0;          // OP_DIRAC_MULTI: 1 - ks[j] D on column j of a block of exactly nk columns (block entry points only);
+                         // OP_DIRAC_EO_MULTI: the same count and values for the Schur complements 1 - ks[j]^2 D_eo D_oe
     cplx ks[MV_MAX_K] = {};
     BcsrDev bcsr;        // OP_BCSR
     GcrState *gcr = nullptr;  // OP_GCR
     MgState *mg = nullptr;    // OP_MG
     EoState *eo = nullptr;    // OP_DIRAC_EO: the Schur complement 1 - k^2 D_eo D_oe on the even half (evenodd.hip; owned)
+    EoMultiState *eom = nullptr;   // OP_DIRAC_EO_MULTI: borrows the halves of an OP_DIRAC_EO, owns its work blocks (evenodd_multi.hip)
     DistCsr *dist = nullptr;  // OP_CSR / OP_BCSR row block of a distributed matrix (halo.hip; owned)
     Comm *comm = nullptr;     // communicator the operator's Fields are distributed over (borrowed)
 };
@@ -188,6 +191,12 @@ inline const Op *op_matrix(const Op *op) { return op && (op->kind == OP_DIRAC ||
 #define MGCR_REFUSE_EVENODD(op, who)                                                                                                  \
     MGCR_CHECK(!(op) || (op)->kind != OP_DIRAC_EO, MGCR_ERR_UNSUPPORTED,                                                              \
                "%s: an even-odd preconditioned DiracOp acts on single Fields of its even half only", who)
+
+// ... and every entry point but the block apply, the batched solve and mgcr_eo_multi_*'s answer to a MultiEvenOddDiracOp
+#define MGCR_REFUSE_EVENODD_MULTI(op, who)                                                                                            \
+    MGCR_CHECK(!(op) || (op)->kind != OP_DIRAC_EO_MULTI, MGCR_ERR_UNSUPPORTED,                                                        \
+               "%s: a MultiEvenOddDiracOp has one hopping parameter per column of a block of even halves; only mgcr_op_apply_multi, "  \
+               "mgcr_gcr_solve_multi and the mgcr_eo_multi entry points take it", who)
 
 // ---- blas1.hip -------------------------------------------------------------------------------
 int red_grid(int64_t n);
@@ -416,10 +425,18 @@ bool eo_schur_fusable(const Op *op);
 // t = D_oe x, then y = x - k^2 D_eo t with the partials of <y, vecs_j>, j < nd <= FND, laid out like gcr.hip's partsB
 int eo_schur_step(Op *op, const cplx *x, cplx *y, const cplx *const *vecs, int nd, double *parts, const RowMap &rm);
 
+// ---- evenodd_multi.hip: the Schur complements of a ladder of hopping parameters on a block (OP_DIRAC_EO_MULTI) ----
+void eo_multi_destroy(EoMultiState *m);
+int64_t eo_multi_nnz(const EoMultiState *m);
+int eo_apply_multi(Op *op, const cplx *x, cplx *y, int64_t n, int k);   // Y_j = X_j - k_j^2 D_eo (D_oe X_j), two k-wide applies
+
 // ---- mvec.hip / spmm.hip / gcr_multi.hip: blocks of k Fields ------------------------------------
 int mv_copy(cplx *dst, const cplx *src, int64_t n, int k);
 // y = op(x) for every column (column j bit-identical to op_apply_raw on column j); w != nullptr (plain Sparse only): y = w - op(x)
 int op_apply_multi_raw(Op *op, const cplx *x, cplx *y, int64_t n, int k, const cplx *w = nullptr);
+struct KCols;   // multi_dev.h
+// the k-wide apply of one Sparse.  kc == nullptr: the uniform shift kk; else the shift per column (kk unused); w as in csr_apply
+int csr_apply_multi(const CsrDev &A, const cplx *x, cplx *y, int k, bool shift, cplx kk, const KCols *kc, const cplx *w);
 int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int64_t n, int k, double *hist, int hist_cap, int *n_iter,
                   int *converged);
 int64_t gcr_multi_solve_count();

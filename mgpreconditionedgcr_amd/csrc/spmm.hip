@@ -294,7 +294,7 @@ static KCols kcols_window(const KCols &ks, int c0) {
 }
 
 // kc == nullptr: the uniform shift kk; else the shift per column (kk unused)
-static int csr_apply_multi(const CsrDev &A, const cplx *x, cplx *y, int k, bool shift, cplx kk, const KCols *kc, const cplx *w) {
+int csr_apply_multi(const CsrDev &A, const cplx *x, cplx *y, int k, bool shift, cplx kk, const KCols *kc, const cplx *w) {
     Context &c = ctx();
     if (A.nrow == 0) return MGCR_OK;
     const unsigned rgrid = (unsigned)((A.nrow + 255) / 256);
@@ -498,12 +498,15 @@ int op_apply_multi_raw(Op *op, const cplx *x, cplx *y, int64_t n, int k, const c
             for (int q = 0; q < MV_MAX_K; q++) ks.v[q] = op->ks[q];   // (entries from k on are 0 and are not read)
             return csr_apply_multi(b0->csr, x, y, k, true, op->ks[0], &ks, nullptr);
         }
+        case OP_DIRAC_EO_MULTI:   // the Schur complements on the even half, one k per column (evenodd_multi.hip)
+            MGCR_CHECK(!w, MGCR_ERR_INVALID, "residual form: plain Sparse only");
+            return eo_apply_multi(op, x, y, n, k);
         case OP_BCSR:
             MGCR_CHECK(!w, MGCR_ERR_INVALID, "residual form: plain Sparse only");
             MGCR_CHECK((int64_t)op->bcsr.nbcol * op->bcsr.bs == n, MGCR_ERR_INVALID, "Sparse matrix dimension does not match Field dimension!");
             return bcsr_apply_multi(op->bcsr, x, y, k);
         default:
-            set_error("the k-wide apply supports Sparse, DiracOp, MultiDiracOp and HierarchicalSparse / Dense operators (not GCR or MG objects)");
+            set_error("the k-wide apply supports Sparse, DiracOp, MultiDiracOp, MultiEvenOddDiracOp and HierarchicalSparse / Dense operators (not GCR or MG objects)");
             return MGCR_ERR_UNSUPPORTED;
     }
 }

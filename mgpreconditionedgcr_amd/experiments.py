@@ -15,7 +15,8 @@ import os
 
 import numpy as np
 
-from .api import DiracOp, EvenOddDiracOp, Field, GCR, GCR_Param, MG, MG_Param, Mesh, MultiDiracOp, MultiField, Sparse, read_data
+from .api import (DiracOp, EvenOddDiracOp, Field, GCR, GCR_Param, MG, MG_Param, Mesh, MultiDiracOp, MultiEvenOddDiracOp, MultiField, Sparse,
+                  read_data)
 
 DIMS_4x4 = (4, 4, 4, 4, 4, 3)
 K_CRITICAL = {"4x4parsed.txt": 0.20611, "8x8parsed.txt": 0.17865}  # src/main.cpp:699,722,845
@@ -145,6 +146,25 @@ def test_kcritical_evenodd(D, dims, k_c, k_start, steps=5, restart=10, max_iter=
     return out
 
 
+def test_kcritical_evenodd_batched(D, dims, k_c, k_start, steps=5, restart=10, max_iter=50000, tol=1e-13, seed=42):
+    """test_kcritical_evenodd as ONE batched solve: every k of the ladder is a column of a MultiEvenOddDiracOp, whose solve runs the
+    Schur systems in lockstep — the halves of D are streamed once per step for all of them, a column that has converged is frozen —
+    and reconstructs the full solutions.  At most 16 values.  Prints the same lines and returns the same tuples: column j has the
+    bits of EvenOddDiracOp(D, k_j).solve."""
+    field = Field(dims).fill_rhs(seed)
+    step = (k_c - k_start) / steps
+    ks = [k_start + step * i for i in range(steps)]
+    scan = MultiEvenOddDiracOp(EvenOddDiracOp(D, ks[0]), ks)
+    sol = MultiField(dims, steps).set_zero()
+    scan.solve(MultiField.from_fields([field] * steps), sol, GCR_Param(0, restart, max_iter, tol, False, check_every=50))
+    out = []
+    for j, k in enumerate(ks):
+        print("k = %f: %s after %d steps, residual %.10e" % (k, "converged" if scan.last_converged[j] else "did not converge",
+                                                             scan.last_iterations[j], scan.last_history[j][-1]))
+        out.append((k, scan.last_iterations[j], scan.last_converged[j], float(scan.last_history[j][-1])))
+    return out
+
+
 def test_MG_property(Dirac, dims, subblock=2, n_eigen=2, null_vectors=None, seed=42):
     """src/main.cpp:877-918 and MG::test_MG (src/MG.h:432-512): projector identities
     (R P R = R, P R P R = P R) and coarse-operator consistency P R A v = P A_c R v on span(P)."""
@@ -176,7 +196,7 @@ def main():
     ap.add_argument("args", nargs="*")
     ap.add_argument("--dir", default="../../data/sample_matrix/")
     ap.add_argument("--file", default="4x4parsed.txt")
-    ap.add_argument("--batched", action="store_true", help="kcritical: every k as one column of ONE batched solve")
+    ap.add_argument("--batched", action="store_true", help="kcritical: every k as one column of ONE batched solve (with --evenodd: of the Schur systems)")
     ap.add_argument("--evenodd", action="store_true", help="kcritical: every k through the even-odd preconditioned (Schur) solve")
     ap.add_argument("--queue", type=int, default=0, metavar="WIDTH", help="kcritical: the ladder through WIDTH columns of one queued solve")
     a = ap.parse_args()
@@ -191,7 +211,7 @@ def main():
         kc = K_CRITICAL.get(a.file, 0.20611)
         k0 = kc - 0.00611 if a.file.startswith("4x4") else 0.174
         if a.evenodd:
-            test_kcritical_evenodd(D, dims, kc, k0)
+            (test_kcritical_evenodd_batched if a.batched else test_kcritical_evenodd)(D, dims, kc, k0)
         elif a.queue:
             test_kcritical_queue(D, dims, kc, k0, width=a.queue)
         else:
