@@ -193,7 +193,8 @@ int mgcr_eo_reconstruct(mgcr_op_t eo, mgcr_vec_t b_full, mgcr_vec_t x_even, mgcr
  * the single Schur solve never takes a one-workgroup or one-launch path, so the small-size exception of the MultiDiracOp's Rule 2
  * does not arise.  The batched cycle takes the beta dot products in passes of their own; the single solve's fused second stage
  * has their bits.
- * Out of scope: the queue on the Schur system, distributed halves, operators with a diagonal. */
+ * Ladders of more than 16 values, or of very unequal lengths, go through mgcr_eo_solve_queue (below, with the solver entry points).
+ * Out of scope: distributed halves, operators with a diagonal. */
 int mgcr_eo_multi_create(mgcr_op_t eo, int32_t nk, const double *k_ri /* [nk][2] */, mgcr_op_t *out);
 int mgcr_eo_multi_set_k(mgcr_op_t op, const double *k_ri /* [nk][2] */);
 int mgcr_eo_multi_split(mgcr_op_t op, mgcr_mvec_t full, mgcr_mvec_t even, mgcr_mvec_t odd);
@@ -290,6 +291,7 @@ int mgcr_set_option(const char *name, int value, int *previous);
  * "pw_tail_folds" = reductions folded and summed over the ranks inside their producing kernel, "multi_solves" = batched solves
  * (mgcr_gcr_solve_multi) completed — queued solves are not counted there but in "queue_solves" = mgcr_gcr_solve_queue calls completed,
  * "queue_admissions" = systems those loaded into a slot after step 0, "queue_steps" = lockstep steps they launched,
+ * "eo_queue_solves" / "eo_queue_admissions" / "eo_queue_steps" = the same three for mgcr_eo_solve_queue,
  * "evenodd_fused_steps" = GCR steps on an even-odd preconditioned DiracOp whose second apply stage took the step's beta dot
  * products (mgcr_eo_create, Rule 2). */
 int mgcr_stat(const char *name, int64_t *value);
@@ -374,6 +376,34 @@ int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t r
  * The work storage is mgcr_gcr_solve_multi's at k = min(width, nsys) plus two blocks (x, b), kept and freed likewise. */
 int mgcr_gcr_solve_queue(mgcr_op_t A, const mgcr_gcr_param *param, int32_t width, int32_t nsys, const mgcr_vec_t *rhs, const mgcr_vec_t *x,
                          const double *k_ri, double *hist, int32_t hist_cap, int32_t *n_iter, int32_t *converged);
+/* Queued even-odd scan: nsys systems (1 - k_s D) x_s = rhs_s on FULL Fields of n entries (any nsys) stream through
+ * W = min(width, nsys) columns of ONE batched solve of the Schur systems S_s = 1 - k_s^2 D_eo D_oe on blocks of n_e rows
+ * (csrc/evenodd_queue.hip on the driver of mgcr_gcr_solve_queue; the schedule is csrc/queue_plan.h unchanged).  eo is an even-odd
+ * preconditioned DiracOp (mgcr_eo_create): its halves and index lists are borrowed, its own k is neither used nor changed.
+ * k_ri: [nsys][2], no zero entry.  Admitting system s into slot j forms bhat_e = b_e + k_s D_eo b_o into column j, takes the even
+ * half of x_s as the column's x (the start vector under use_x0, exactly as in mgcr_eo_solve) and keeps b_o in column j of an
+ * [n_o x W] block while the system is in flight; retiring slot j applies the column's pending x updates, forms
+ * x_o = b_o + k_s D_oe x_e and writes both halves into x_s.  An admission point costs a fixed number of passes, one k-wide shifted
+ * D_eo apply and the queue's one (use_x0: two) k-wide Schur applies, a retirement point one k-wide shifted D_oe apply, whatever
+ * the number of columns admitted or retired.  The host drives everything between launches; no kernel waits on another.
+ * rhs handles may repeat; the x handles must be pairwise distinct and none may be a right-hand side.  hist: [nsys][hist_cap] or
+ * NULL, row s relative to |bhat_e,s|; n_iter, converged: [nsys] or NULL — per SYSTEM, in the caller's order.
+ * MGCR_ERR_INVALID (nothing is enqueued or touched): eo is not an EvenOddDiracOp (a MultiEvenOddDiracOp, a Sparse, a DiracOp),
+ * k_ri == NULL, a zero k_s, width outside 1 .. 16, nsys < 1, a null handle, a Field whose length is not n (a Field of n_e
+ * entries is the likely slip), an x that repeats or is a right-hand side.  MGCR_ERR_UNSUPPORTED: every parameter case of
+ * mgcr_eo_multi_solve (truncation != 0, restart == 0, cycles longer than 16, a preconditioner, flexible, profile_spmv).
+ * Rule: history, iteration count, convergence flag and the whole x_full of system s are BIT-IDENTICAL to mgcr_eo_solve on
+ * EvenOddDiracOp(D, k_s) with that system alone — at any size, width, order of the systems and check_every, and on every storage
+ * form of the halves (Rules 1 and 2 of mgcr_eo_multi_create and the rule of mgcr_gcr_solve_queue; a Schur solve never takes a
+ * one-workgroup or one-launch path, so the small-size exception does not arise).
+ * Counters (mgcr_stat): "eo_queue_solves" = calls completed, "eo_queue_admissions" = systems loaded into a slot after step 0,
+ * "eo_queue_steps" = lockstep steps launched; "queue_*" and "multi_solves" do not move.
+ * The work storage is mgcr_gcr_solve_queue's at k = W on n_e rows, plus the slot operator's blocks (b_e, b_o, bhat, x_e, x_o, the
+ * D_oe product between the two stages; one more per half with a CSR tail), kept by the library between calls while n_e, n_o and
+ * W stay the same and freed by mgcr_finalize.  mgcr_gcr_solve_queue itself goes on refusing both even-odd kinds. */
+int mgcr_eo_solve_queue(mgcr_op_t eo, const mgcr_gcr_param *param, int32_t width, int32_t nsys, const mgcr_vec_t *rhs_full,
+                        const mgcr_vec_t *x_full, const double *k_ri /* [nsys][2] */, double *hist /* [nsys][hist_cap] or NULL */,
+                        int32_t hist_cap, int32_t *n_iter, int32_t *converged);
 /* Unpreconditioned solves on a single-GPU Sparse / DiracOp with at most `rows` unknowns (default
  * 1024, $MGCR_SMALL_SOLVE_ROWS; and at most 16*rows stored entries) and <= 8 stored directions run
  * as ONE launch of one workgroup (latency regime: coarsest multigrid levels); 0 disables that path.

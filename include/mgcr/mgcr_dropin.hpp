@@ -939,6 +939,42 @@ public:
     std::vector<double> last_history;   // of the Schur solve, relative to |bhat_e|
     int last_iterations = 0;
     bool last_converged = false;
+    // (Id - ks[s] D) x_s = rhs_s for any number of systems on full-system Fields, through `width` <= 16 columns of ONE batched solve
+    // of the Schur systems (extension, mgcr_eo_solve_queue): a column whose system has stopped is reconstructed into its x Field
+    // and takes the next waiting system at the next boundary of the restart cycle.  This operator's own k is neither used nor
+    // changed.  rhs may repeat, the x Fields are distinct and updated in place; per SYSTEM: queue_history[s] (relative to
+    // |bhat_e,s|), queue_iterations[s], queue_converged[s] — the bits of solve() at ks[s] on that system alone.
+    void solve_queue(const std::vector<const Field<num_type> *> &rhs, const std::vector<Field<num_type> *> &x, const std::vector<std::complex<double>> &ks,
+                     GCR_Param<num_type> *param, int width = 8) {
+        if (rhs.size() != x.size() || ks.size() != rhs.size()) { std::fprintf(stderr, "EvenOddDiracOp::solve_queue: one x and one k per right-hand side\n"); std::abort(); }
+        if (param->truncation != 0 && param->restart != 0) { std::fprintf(stderr, "Do not support concurrent restarting and truncation.\n"); std::abort(); }
+        mgcr_gcr_param p;
+        std::memset(&p, 0, sizeof(p));
+        p.truncation = param->truncation; p.restart = param->restart; p.max_iter = param->max_iter; p.tol = param->tol;
+        p.verbose = param->verbose ? 1 : 0;
+        p.left_precond = param->left_precond ? param->left_precond->handle() : nullptr;
+        p.right_precond = param->right_precond ? param->right_precond->handle() : nullptr;
+        p.use_x0 = param->use_x0; p.flexible = param->flexible;
+        const int nsys = (int)rhs.size(), cap = (param->max_iter > 0 ? param->max_iter : 1) + 1;
+        std::vector<mgcr_vec_t> bh, xh;
+        for (int s = 0; s < nsys; s++) { bh.push_back(rhs[(size_t)s]->device()); xh.push_back(x[(size_t)s]->device()); }
+        std::vector<double> kri, hist((size_t)nsys * cap, 0.);
+        for (const std::complex<double> &kk : ks) { kri.push_back(kk.real()); kri.push_back(kk.imag()); }
+        std::vector<int32_t> it((size_t)nsys, 0), conv((size_t)nsys, 0);
+        mgcr_detail::ok(mgcr_eo_solve_queue(op, &p, width, nsys, bh.data(), xh.data(), kri.data(), hist.data(), cap, it.data(), conv.data()),
+                        "EvenOddDiracOp::solve_queue");
+        queue_history.assign((size_t)nsys, std::vector<double>());
+        queue_iterations.assign(it.begin(), it.end());
+        queue_converged.assign((size_t)nsys, false);
+        for (int s = 0; s < nsys; s++) {
+            x[(size_t)s]->device_written();
+            queue_history[(size_t)s].assign(hist.begin() + (size_t)s * cap, hist.begin() + (size_t)s * cap + it[(size_t)s] + 1);
+            queue_converged[(size_t)s] = conv[(size_t)s] != 0;
+        }
+    }
+    std::vector<std::vector<double>> queue_history;
+    std::vector<int> queue_iterations;
+    std::vector<bool> queue_converged;
 
 private:
     static std::complex<double> not_stored() {

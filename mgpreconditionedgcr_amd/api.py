@@ -512,6 +512,34 @@ class EvenOddDiracOp(Operator):
         self.last_history = hist[: it.value + 1].copy()
         return x_full
 
+    def solve_queue(self, rhs_list, x_list, ks, gcr_param, width=8):
+        """(Id - ks[s] D) x_s = rhs_s for any number of systems on full-system Fields, through `width` <= 16 columns of ONE batched
+        solve of the Schur systems (mgcr_eo_solve_queue): a column whose system has stopped is reconstructed into its x Field and
+        refilled with the next system at the next boundary of the restart cycle.  This operator's own k is neither used nor
+        changed.  rhs Fields may repeat, the x Fields are distinct and updated in place; last_history (relative to |bhat_e,s|),
+        last_iterations and last_converged are kept per system, each with the bits of solve() at ks[s] on that system alone."""
+        nsys = len(rhs_list)
+        if len(x_list) != nsys:
+            raise MgcrError(1, "solve_queue: %d right-hand sides, %d x Fields" % (nsys, len(x_list)))
+        kv = None
+        if ks is not None:
+            kv = MultiDiracOp._values(ks)
+            if kv.shape[0] != nsys:
+                raise MgcrError(1, "solve_queue: %d hopping parameters for %d systems" % (kv.shape[0], nsys))
+        cap = max(gcr_param.max_iter, 1) + 1
+        hist = np.zeros((max(nsys, 1), cap), np.float64)
+        it, conv = (C.c_int32 * max(nsys, 1))(), (C.c_int32 * max(nsys, 1))()
+        bh = (C.c_void_p * max(nsys, 1))(*[f.h if f is not None else None for f in rhs_list])
+        xh = (C.c_void_p * max(nsys, 1))(*[f.h if f is not None else None for f in x_list])
+        pc = gcr_param._c()
+        check(_lib.lib().mgcr_eo_solve_queue(self.h, C.byref(pc), int(width), nsys, bh, xh,
+                                             kv.ctypes.data_as(C.POINTER(C.c_double)) if kv is not None else None,
+                                             hist.ctypes.data, cap, it, conv))
+        self.last_iterations = [int(v) for v in it][:nsys]
+        self.last_converged = [bool(v) for v in conv][:nsys]
+        self.last_history = [hist[j, : it[j] + 1].copy() for j in range(nsys)]
+        return x_list
+
 
 class MultiEvenOddDiracOp(Operator):
     """The Schur complements Id - ks[j]^2 D_eo D_oe of ONE hopping matrix on column j of a block of len(ks) Fields of the even

@@ -270,6 +270,9 @@ int mgcr_stat(const char *name, int64_t *value) {
     else if (!strcmp(name, "queue_solves")) *value = gcr_queue_stat(0);
     else if (!strcmp(name, "queue_admissions")) *value = gcr_queue_stat(1);
     else if (!strcmp(name, "queue_steps")) *value = gcr_queue_stat(2);
+    else if (!strcmp(name, "eo_queue_solves")) *value = gcr_queue_stat(3);
+    else if (!strcmp(name, "eo_queue_admissions")) *value = gcr_queue_stat(4);
+    else if (!strcmp(name, "eo_queue_steps")) *value = gcr_queue_stat(5);
     else if (!strcmp(name, "evenodd_fused_steps")) *value = eo_fused_step_count();
     else { set_error("mgcr_stat: unknown counter '%s'", name); return MGCR_ERR_INVALID; }
     return MGCR_OK;

@@ -17,19 +17,9 @@
 // it produces the bits of the plain stage 2 followed by the dot products, so Rule 2 holds all the same).
 #include <algorithm>
 
-#include "internal.h"
-#include "multi_dev.h"
-#include "evenodd_state.h"
+#include "evenodd_multi.h"
 
 namespace mgcr {
-
-struct EoMultiState {
-    Op *eo = nullptr;   // the OP_DIRAC_EO whose halves and lists are read (borrowed: it outlives this operator)
-    KCols ks2;          // k_j k_j (the k_j themselves are Op::ks); entries from nk on are 0 and are not read
-    cplx *t = nullptr;  // [n_o x nk] D_oe X between the two stages, allocated on first use
-    // work blocks, allocated on first use, the roles of EoState::Work: W_BO, W_XO and W_UO have n_o rows, the others n_e
-    cplx *work[EoState::W_COUNT] = {};
-};
 
 void eo_multi_destroy(EoMultiState *m) {
     if (!m) return;
@@ -47,7 +37,7 @@ static int eom_block(cplx **slot, int64_t rows, int k) {
     }
     return MGCR_OK;
 }
-static int eom_work(Op *op, EoState::Work which, cplx **out) {
+int eom_work(Op *op, EoState::Work which, cplx **out) {
     const EoState *e = op->eom->eo->eo;
     const bool odd = which == EoState::W_BO || which == EoState::W_XO || which == EoState::W_UO;
     MGCR_TRY(eom_block(&op->eom->work[which], odd ? e->no : e->ne, op->nk));
@@ -123,7 +113,7 @@ __global__ void __launch_bounds__(RED_THREADS) eom_sub_scaled_kernel(cplx *__res
 }
 
 // Y_j = W_j - c_j (H X)_j for half H (0: D_eo, 1: D_oe): eo_shift_apply on a block
-static int eom_shift_apply(Op *op, int h, const cplx *x, cplx *y, const KCols &cs, const cplx *w) {
+int eom_shift_apply(Op *op, int h, const cplx *x, cplx *y, const KCols &cs, const cplx *w) {
     const int k = op->nk;
     const CsrDev &A = op->eom->eo->eo->half[h]->csr;
     if (A.nrow == 0) return MGCR_OK;
@@ -152,7 +142,7 @@ int eo_apply_multi(Op *op, const cplx *x, cplx *y, int64_t n, int k) {
 }
 
 // the factors -k_j of prepare and reconstruct
-static KCols eom_negated(const Op *op) {
+KCols eom_negated(const Op *op) {
     KCols out;
     for (int q = 0; q < MV_MAX_K; q++) out.v[q] = make_double2(-op->ks[q].x, -op->ks[q].y);
     return out;

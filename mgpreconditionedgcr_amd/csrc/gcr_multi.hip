@@ -556,6 +556,39 @@ __global__ void __launch_bounds__(256) q_retire_kernel(unsigned mask, const DevS
     }
 }
 
+// ... for a queue whose systems are not whole Fields (QueueHooks: the even-odd queue): the same expression, written to column j of a
+// work block, from where the hooks take it
+template <int KC>
+__global__ void __launch_bounds__(256) hq_retire_kernel(unsigned mask, const DevState *__restrict__ st, const LeanCoef *__restrict__ lc, MPtrs d,
+                                                        const cplx *__restrict__ x, cplx *__restrict__ out, int64_t n, int k) {
+    const int c0 = (int)blockIdx.y * KC;
+    if (((mask >> c0) & ((1u << KC) - 1u)) == 0) return;
+    bool ret[KC];
+    int np[KC];
+    int npmax = 0;
+#pragma unroll
+    for (int c = 0; c < KC; c++) {
+        ret[c] = c0 + c < k && ((mask >> (c0 + c)) & 1u);
+        np[c] = ret[c] ? st[c0 + c].npend : 0;
+        if (np[c] > LND) np[c] = LND;
+        npmax = np[c] > npmax ? np[c] : npmax;
+    }
+    MV_GRID_STRIDE(i, n) {
+        cplx xv[KC];
+        mv_load<KC>(x, i, k, c0, xv);
+        for (int q = 0; q < npmax; q++) {
+            cplx pj[KC];
+            mv_load<KC>(d.ps[q], i, k, c0, pj);
+#pragma unroll
+            for (int c = 0; c < KC; c++)
+                if (q < np[c]) xv[c] = cadd(xv[c], cmul(lc[c0 + c].cx[q], pj[c]));
+        }
+#pragma unroll
+        for (int c = 0; c < KC; c++)
+            if (ret[c]) out[i * k + c0 + c] = xv[c];
+    }
+}
+
 // admit, pass 1: the system's x and b into column blockIdx.y of the x and b blocks; without x0 also r0 = P0 = b
 __global__ void __launch_bounds__(RED_THREADS) q_scatter_kernel(unsigned mask, QFields f, cplx *__restrict__ xb, cplx *__restrict__ bb, cplx *__restrict__ r,
                                                                 cplx *__restrict__ p0, int64_t n, int k, int use_x0) {
@@ -754,6 +787,7 @@ MWork g_work;
 void mvec_release();   // mvec.hip
 void multi_release() {
     g_work.release();
+    eo_queue_release();
     mvec_release();
 }
 
@@ -896,12 +930,19 @@ int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int6
 //   step: gcr_multi_run's, except that a column at its OWN last step takes q_finish_kernel and is left out of what follows.
 // ks != nullptr: system s is (1 - ks[s] D) x = b, D = A a plain Sparse; the slots' shifts live in a MultiDiracOp made here, whose
 // values travel in the kernel arguments of every apply (KCols): admitting system s into slot j sets entry j.
+// hk != nullptr (the even-odd queue, evenodd_queue.hip): the systems are not Fields of n entries.  The hooks fill the admitted
+// columns in place of q_scatter_kernel and take the retiring columns from a work block that hq_retire_kernel writes in place of
+// q_retire_kernel; rhs, x and ks are not read, and the counters that move are the hooks' own.  Without hooks every launch is what it was.
 // ------------------------------------------------------------------------------------------------
 static int64_t g_queue_solves = 0, g_queue_admissions = 0, g_queue_steps = 0;
-int64_t gcr_queue_stat(int which) { return which == 0 ? g_queue_solves : which == 1 ? g_queue_admissions : g_queue_steps; }
+static int64_t g_hooked_solves = 0, g_hooked_admissions = 0, g_hooked_steps = 0;
+int64_t gcr_queue_stat(int which) {
+    return which == 0 ? g_queue_solves : which == 1 ? g_queue_admissions : which == 2 ? g_queue_steps
+         : which == 3 ? g_hooked_solves : which == 4 ? g_hooked_admissions : g_hooked_steps;
+}
 
 int gcr_queue_run(Op *A0, const mgcr_gcr_param &p, int width, int nsys, const cplx *const *rhs, cplx *const *x, const cplx *ks, int64_t n,
-                  double *hist, int hist_cap, int *n_iter, int *converged) {
+                  double *hist, int hist_cap, int *n_iter, int *converged, QueueHooks *hk) {
     Context &c = ctx();
     const int restart = p.restart;
     QueuePlan qp(width < nsys ? width : nsys, nsys, restart, p.max_iter, p.check_every);
@@ -950,6 +991,7 @@ int gcr_queue_run(Op *A0, const mgcr_gcr_param &p, int width, int nsys, const cp
     std::vector<double> row;
     QFields f{};
     int64_t admissions0 = qp.admissions;
+    int64_t &steps = hk ? g_hooked_steps : g_queue_steps;
     for (;;) {
         if (qp.poll_due()) {
             MGCR_HIP(hipMemcpyAsync(hs.data(), st, sizeof(DevState) * MV_MAX_K, hipMemcpyDeviceToHost, c.stream));
@@ -959,7 +1001,8 @@ int gcr_queue_run(Op *A0, const mgcr_gcr_param &p, int width, int nsys, const cp
             for (int j = 0; j < k; j++)
                 if (qp.occupied(j) && hs[(size_t)j].stop_at != INT_MAX) mask |= 1u << j;
             if (mask) {
-                MK_KC(q_retire_kernel, gx, 256, mask, (const DevState *)st, (const LeanCoef *)lc, d, (const cplx *)xb, f, n, k);
+                if (hk) MK_KC(hq_retire_kernel, gx, 256, mask, (const DevState *)st, (const LeanCoef *)lc, d, (const cplx *)xb, hk->retire_block(), n, k);
+                else MK_KC(q_retire_kernel, gx, 256, mask, (const DevState *)st, (const LeanCoef *)lc, d, (const cplx *)xb, f, n, k);
                 for (int j = 0; j < k; j++) {
                     if (!((mask >> j) & 1u)) continue;
                     const int s = qp.sys[j], it = hs[(size_t)j].iter;
@@ -975,6 +1018,7 @@ int gcr_queue_run(Op *A0, const mgcr_gcr_param &p, int width, int nsys, const cp
                     }
                     qp.retire(j);
                 }
+                if (hk) MGCR_TRY(hk->retire(mask));
             }
         }
         int slots[QP_MAX_WIDTH], systems[QP_MAX_WIDTH];
@@ -984,12 +1028,14 @@ int gcr_queue_run(Op *A0, const mgcr_gcr_param &p, int width, int nsys, const cp
             for (int i = 0; i < m; i++) {
                 const int j = slots[i], s = systems[i];
                 mask |= 1u << j;
+                if (hk) continue;
                 f.b[j] = rhs[s];
                 f.x[j] = x[s];
                 if (ks) shifted.ks[j] = ks[s];
             }
             const dim3 cols((unsigned)g, (unsigned)k);
-            MK(q_scatter_kernel, cols, RED_THREADS, mask, f, xb, bb, r, ps[0], n, k, p.use_x0 ? 1 : 0);
+            if (hk) MGCR_TRY(hk->admit(mask, m, slots, systems, xb, bb, r, ps[0], p.use_x0 != 0));
+            else MK(q_scatter_kernel, cols, RED_THREADS, mask, f, xb, bb, r, ps[0], n, k, p.use_x0 ? 1 : 0);
             if (p.use_x0) {
                 if (residual_form) MGCR_TRY(op_apply_multi_raw(A, xb, ar, n, k, bb));
                 else MGCR_TRY(op_apply_multi_raw(A, xb, ar, n, k));
@@ -1003,7 +1049,7 @@ int gcr_queue_run(Op *A0, const mgcr_gcr_param &p, int width, int nsys, const cp
         if (qp.finished()) break;
         MGCR_CHECK(qp.any_running(), MGCR_ERR_HIP, "queued GCR: a column is still marked as running after its last step");
         const QueueStep s = qp.step();
-        g_queue_steps++;
+        steps++;
         const int it = s.it, lim = s.lim;
         const cplx *rin = s.cur >= 1 ? ps[(size_t)s.cur] : r;
         cplx *dslot = s.nxt >= 1 ? ps[(size_t)s.nxt] : r;
@@ -1028,8 +1074,8 @@ int gcr_queue_run(Op *A0, const mgcr_gcr_param &p, int width, int nsys, const cp
               aps[(size_t)s.nxt], n, k, partsA, max_it);
     }
     MGCR_HIP(hipStreamSynchronize(c.stream));   // the last retirement's writes to the systems' Fields
-    g_queue_admissions += qp.admissions - admissions0;
-    g_queue_solves++;
+    (hk ? g_hooked_admissions : g_queue_admissions) += qp.admissions - admissions0;
+    (hk ? g_hooked_solves : g_queue_solves)++;
     return resident_check();
 }
 

@@ -442,10 +442,23 @@ int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int6
 int64_t gcr_multi_solve_count();
 // nsys systems through min(width, nsys) columns of one batched solve (queue_plan.h has the schedule); ks != nullptr: system s is
 // (1 - ks[s] A) x = rhs[s] with A a plain Sparse
+// hk != nullptr: the systems are not whole Fields (the even-odd queue) — the hooks load the admitted columns and unload the retired
+// ones; rhs, x and ks are then not read
+struct QueueHooks {
+    virtual ~QueueHooks() {}
+    // systems[i] enters slot slots[i], i < m (mask: those slots): column slots[i] of the x and b blocks and, without x0, of r and P0
+    // (= b) is filled; every other column of the four blocks stays as it is
+    virtual int admit(unsigned mask, int m, const int *slots, const int *systems, cplx *xb, cplx *bb, cplx *r, cplx *p0, bool use_x0) = 0;
+    // a block of the solve's shape: the driver writes the final x of the retiring slots into their columns of it, then calls retire
+    virtual cplx *retire_block() = 0;
+    virtual int retire(unsigned mask) = 0;
+};
 int gcr_queue_run(Op *A, const mgcr_gcr_param &p, int width, int nsys, const cplx *const *rhs, cplx *const *x, const cplx *ks, int64_t n,
-                  double *hist, int hist_cap, int *n_iter, int *converged);
-int64_t gcr_queue_stat(int which);   // 0: solves completed, 1: systems admitted after step 0, 2: lockstep steps launched
+                  double *hist, int hist_cap, int *n_iter, int *converged, QueueHooks *hk = nullptr);
+// 0: solves completed, 1: systems admitted after step 0, 2: lockstep steps launched; 3 .. 5: the same for the solves run with hooks
+int64_t gcr_queue_stat(int which);
 void multi_release();   // frees the batched solve's cached work storage and the block BLAS-1 buffers (mgcr_finalize)
+void eo_queue_release();   // evenodd_queue.hip: the even-odd queue's slot operator and its work blocks
 
 // ---- gcr_small.hip ---------------------------------------------------------------------------
 void gcr_small_set_limit(int64_t rows);

@@ -6,6 +6,7 @@ either side of the hot path — plus the MatrixMarket 
     python -m mgpreconditionedgcr_amd.experiments kcritical  --dir data/sample_matrix --batched
     python -m mgpreconditionedgcr_amd.experiments kcritical  --dir data/sample_matrix --queue 2
     python -m mgpreconditionedgcr_amd.experiments kcritical  --dir data/sample_matrix --evenodd
+    python -m mgpreconditionedgcr_amd.experiments kcritical  --dir data/sample_matrix --evenodd --queue 2
     python -m mgpreconditionedgcr_amd.experiments mg_property --dir data/sample_matrix
     python -m mgpreconditionedgcr_amd.experiments hermiticity --dir data/sample_matrix
     python -m mgpreconditionedgcr_amd.experiments parse  conf.mtx parsed.txt
@@ -165,6 +166,25 @@ def test_kcritical_evenodd_batched(D, dims, k_c, k_start, steps=5, restart=10, m
     return out
 
 
+def test_kcritical_evenodd_queue(D, dims, k_c, k_start, steps=5, restart=10, max_iter=50000, tol=1e-13, seed=42, width=4):
+    """test_kcritical_evenodd as ONE queued solve: the ladder of k (any length) streams through `width` columns of a batched solve of
+    the Schur systems (EvenOddDiracOp.solve_queue) — a column whose k has stopped is reconstructed and takes the next waiting k at
+    the next boundary of the restart cycle, so the value next to k_c that runs long holds one column only.  Prints the same lines
+    and returns the same tuples: system j has the bits of EvenOddDiracOp(D, k_j).solve."""
+    field = Field(dims).fill_rhs(seed)
+    step = (k_c - k_start) / steps
+    ks = [k_start + step * i for i in range(steps)]
+    sols = [Field(dims).set_zero() for _ in ks]
+    eo = EvenOddDiracOp(D, ks[0])
+    eo.solve_queue([field] * steps, sols, ks, GCR_Param(0, restart, max_iter, tol, False, check_every=50), width=width)
+    out = []
+    for j, k in enumerate(ks):
+        print("k = %f: %s after %d steps, residual %.10e" % (k, "converged" if eo.last_converged[j] else "did not converge",
+                                                             eo.last_iterations[j], eo.last_history[j][-1]))
+        out.append((k, eo.last_iterations[j], eo.last_converged[j], float(eo.last_history[j][-1])))
+    return out
+
+
 def test_MG_property(Dirac, dims, subblock=2, n_eigen=2, null_vectors=None, seed=42):
     """src/main.cpp:877-918 and MG::test_MG (src/MG.h:432-512): projector identities
     (R P R = R, P R P R = P R) and coarse-operator consistency P R A v = P A_c R v on span(P)."""
@@ -198,7 +218,7 @@ def main():
     ap.add_argument("--file", default="4x4parsed.txt")
     ap.add_argument("--batched", action="store_true", help="kcritical: every k as one column of ONE batched solve (with --evenodd: of the Schur systems)")
     ap.add_argument("--evenodd", action="store_true", help="kcritical: every k through the even-odd preconditioned (Schur) solve")
-    ap.add_argument("--queue", type=int, default=0, metavar="WIDTH", help="kcritical: the ladder through WIDTH columns of one queued solve")
+    ap.add_argument("--queue", type=int, default=0, metavar="WIDTH", help="kcritical: the ladder through WIDTH columns of one queued solve (with --evenodd: of the Schur systems)")
     a = ap.parse_args()
     if a.what == "parse":
         parse_data(a.args[0], a.args[1])
@@ -210,7 +230,9 @@ def main():
     elif a.what == "kcritical":
         kc = K_CRITICAL.get(a.file, 0.20611)
         k0 = kc - 0.00611 if a.file.startswith("4x4") else 0.174
-        if a.evenodd:
+        if a.evenodd and a.queue:
+            test_kcritical_evenodd_queue(D, dims, kc, k0, width=a.queue)
+        elif a.evenodd:
             (test_kcritical_evenodd_batched if a.batched else test_kcritical_evenodd)(D, dims, kc, k0)
         elif a.queue:
             test_kcritical_queue(D, dims, kc, k0, width=a.queue)
