@@ -31,8 +31,10 @@ typedef std::complex<double> hc;
 // ------------------------------------------------------------------------------------------------
 
 // (R x)[a*ne + k] = sum over the members of a (ascending) of conj(pv[i][k]) x[i]   (src/MG.h:366-383)
-// one thread per coarse unknown: aggregates are small (2^d sites x dof), neighbouring threads read
-// neighbouring aggregates, and the sum runs in the reference's order (bit-identical to the oracle).
+// one thread per coarse unknown: the workloads' aggregates are small (2^d sites x dof), neighbouring threads read
+// neighbouring aggregates, and the sum runs in the reference's order (bit-identical to the oracle).  Nothing below
+// assumes that size: any member count works — partial last batch, batches whose pairs start on odd rows, one
+// aggregate of thousands of members (tests/test_gpu_mg_shapes.py) — a long member list is only slow.
 __global__ void __launch_bounds__(256) restrict_kernel(int64_t nc, int ne, const int32_t *__restrict__ aptr,
                                                        const int32_t *__restrict__ amem, const cplx *__restrict__ pv,
                                                        const cplx *__restrict__ x, cplx *__restrict__ xc,
@@ -56,7 +58,7 @@ __global__ void __launch_bounds__(256) restrict_kernel(int64_t nc, int ne, const
     int64_t a = c / ne;
     int k = (int)(c - a * ne);
     cplx s = make_double2(0., 0.);
-    // members in batches of 8 (one 2^3 aggregate): the 8 index loads, then the 16 value loads, are issued together
+    // members in batches of 8 (a 2^3 aggregate is one batch): the 8 index loads, then the 16 value loads, are issued together
     // instead of one dependent index -> value chain per member; the sum keeps the members' order
     const int32_t beg = aptr[a], end = aptr[a + 1];
     for (int32_t m0 = beg; m0 < end; m0 += 8) {

@@ -282,8 +282,10 @@ static void case_hsparse() {
     delete[] trip;
 }
 
-// G9: MG pieces on the 4x4 sample, block 2^4, n_eigen 2
-static void case_mg() {
+// G9: MG pieces on the 4x4 sample, block 2^4, n_eigen 2.  `sub` = MG_Param's block edge: 2 is G9 itself (files g9_*);
+// any other edge writes the same pieces as g9e<sub>_* (edge 4: ONE block of all 256 sites, tests/golden/mg_4x4_edge4.npz)
+static void case_mg(int sub = 2) {
+    const std::string tag = sub == 2 ? "g9_" : "g9e" + std::to_string(sub) + "_";
     long dims[6] = {4, 4, 4, 4, 4, 3};
     Mesh<long> mesh(dims, 6);
     auto D = new Sparse<long>(read_data("4x4parsed.txt"));
@@ -293,7 +295,7 @@ static void case_mg() {
     GCR_Param<long> smooth(0, 10, 1, 1e-8, false, nullptr, nullptr);
     auto solver_coarse = new GCR<long>(&coarse);
     auto solver_smooth = new GCR<long>(&smooth);
-    const int n_eigen = 2, ne = 2 * n_eigen, sub = 2;
+    const int n_eigen = 2, ne = 2 * n_eigen;
     MG_Param<long> param(mesh, sub, n_eigen, &eigen, solver_coarse, solver_smooth, 1, nullptr, nullptr);
 
     // the near-null vectors the set-up starts from (Arnoldi, src/MG.h:90-122) and their
@@ -303,8 +305,8 @@ static void case_mg() {
         auto ev = new Field<long>[n_eigen];
         Arnoldi<long> ar(&eigen, n_eigen);
         ar.solve(Dirac, ev, mesh);
-        for (int i = 0; i < n_eigen; i++) dump_field("g9_eigvec" + std::to_string(i), ev[i]);
-        dump_field("g9_gamma5_eigvec0", ev[0].gamma5(4));
+        for (int i = 0; i < n_eigen; i++) dump_field(tag + "eigvec" + std::to_string(i), ev[i]);
+        dump_field(tag + "gamma5_eigvec0", ev[0].gamma5(4));
         delete[] ev;
     }
 
@@ -312,37 +314,37 @@ static void case_mg() {
     long nblocks = param.mesh.get_nblocks();
     long bsz = param.mesh.get_block_size();
     long meta[6] = {nblocks, bsz, ne, sub, 0, 0};
-    dump("g9_meta", meta, sizeof(meta));
+    dump(tag + "meta", meta, sizeof(meta));
     // block map (src/Mesh.h:236-298)
     std::vector<long> bmap((size_t)nblocks * bsz);
     for (long b = 0; b < nblocks; b++) for (long o = 0; o < bsz; o++) bmap[b * bsz + o] = param.mesh.get_block_map(b)[o];
-    dump_vec("g9_block_map", bmap);
+    dump_vec(tag + "block_map", bmap);
     // prolongator columns as full-length fields [block][i][N]
     long N = Dirac->get_dim();
     std::vector<cplx> P((size_t)nblocks * ne * N);
     for (long b = 0; b < nblocks; b++) for (int i = 0; i < ne; i++)
         for (long j = 0; j < N; j++) P[((size_t)b * ne + i) * N + j] = mg->prolongator[b][i].val_at(j);
-    dump_vec("g9_P", P);
+    dump_vec(tag + "P", P);
     // restrict / expand / coarse apply
     Field<long> v(dims, 6);
     v.init_rand(42);
-    dump_field("g9_v", v);
+    dump_field(tag + "v", v);
     Field<long> Rv = mg->restrict(v);
-    dump_field("g9_Rv", Rv);
+    dump_field(tag + "Rv", Rv);
     Field<long> PRv = mg->expand(Rv);
-    dump_field("g9_PRv", PRv);
+    dump_field(tag + "PRv", PRv);
     Field<long> AcRv = (*mg->m_coarse)(Rv);
-    dump_field("g9_AcRv", AcRv);
+    dump_field(tag + "AcRv", AcRv);
     // coarse operator as dense (nb*ne)^2 via val_at(row,col)
     long nc = nblocks * ne;
     std::vector<cplx> Ac((size_t)nc * nc);
     for (long r = 0; r < nc; r++) for (long c = 0; c < nc; c++) Ac[r * nc + c] = mg->m_coarse->val_at(r, c);
-    dump_vec("g9_Ac_dense", Ac);
+    dump_vec(tag + "Ac_dense", Ac);
     // identities of test_MG_property (src/main.cpp:899-909)
     Field<long> i1 = mg->restrict(v), i2 = mg->expand(i1), i3 = mg->restrict(i2);
     Field<long> i11 = mg->restrict(i2), i22 = mg->expand(i11);
     double idn[2] = {(i2 - i22).norm(), (i3 - i1).norm()};
-    dump("g9_identities", idn, sizeof(idn));
+    dump(tag + "identities", idn, sizeof(idn));
     fprintf(stderr, "[mg] RT-Id %.3e  TRTR-TR %.3e\n", idn[0], idn[1]);
     delete mg; delete solver_coarse; delete solver_smooth; delete Dirac; delete D;
 }
@@ -519,7 +521,7 @@ static void case_legacy() {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <outdir> sample|hsparse|mg|arnoldi|legacy|builders [file.mtx]|poisson <n> <iters> <tag> [trunc restart tol]|bench <n> <iters>\n", argv[0]);
+        fprintf(stderr, "usage: %s <outdir> sample|hsparse|mg [edge]|arnoldi|legacy|builders [file.mtx]|poisson <n> <iters> <tag> [trunc restart tol]|bench <n> <iters>\n", argv[0]);
         return 1;
     }
     char absout[4096];
@@ -534,7 +536,7 @@ int main(int argc, char **argv) {
     }
     if (c == "sample") case_sample();
     else if (c == "hsparse") case_hsparse();
-    else if (c == "mg") case_mg();
+    else if (c == "mg") case_mg(argc >= 4 ? atoi(argv[3]) : 2);
     else if (c == "arnoldi") case_arnoldi();
     else if (c == "legacy") case_legacy();
     else if (c == "builders") case_builders(argc >= 4 ? argv[3] : "");

@@ -2,6 +2,7 @@
 // tests/test_spmv_layout.py builds this with the address and undefined-behaviour sanitizers and compares the lines
 // with values worked out by hand.
 #include <cstdio>
+#include <string>
 
 #include "spmv_layout.h"
 
@@ -95,7 +96,32 @@ static StenSlots slots(const std::vector<int32_t> &S, const std::vector<double> 
     return s;
 }
 
-int main() {
+// `spmv_layout_check split <len>:<count> ...`: the ELL width, the lanes and the CSR tail the build gives a matrix with this row-length
+// histogram (spmv_build.hip: a row's entries beyond W go to the tail) — one line, nothing else (tests/test_mg_shape_cases.py)
+static int split(int argc, char **argv) {
+    std::vector<std::pair<int32_t, int64_t>> lens;
+    int32_t maxlen = 0;
+    int64_t nrow = 0;
+    for (int a = 2; a < argc; a++) {
+        long long len = 0, count = 0;
+        if (sscanf(argv[a], "%lld:%lld", &len, &count) != 2 || len < 0 || len >= (1 << 30) || count < 1) return 2;
+        lens.push_back({(int32_t)len, (int64_t)count});
+        maxlen = std::max(maxlen, (int32_t)len);
+        nrow += count;
+    }
+    std::vector<int64_t> hist((size_t)maxlen + 2, 0);
+    for (auto &l : lens) hist[(size_t)l.first] += l.second;
+    const int32_t W = choose_width(hist, nrow, maxlen);
+    int64_t tail_rows = 0, tail_nnz = 0;
+    for (auto &l : lens)
+        if (l.first > W) { tail_rows += l.second; tail_nnz += (int64_t)(l.first - W) * l.second; }
+    printf("split nrow=%lld W=%d lanes=%d tail_rows=%lld tail_nnz=%lld\n", (long long)nrow, W, choose_lanes(nrow, W), (long long)tail_rows,
+           (long long)tail_nnz);
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc >= 3 && std::string(argv[1]) == "split") return split(argc, argv);
     width("skew", 1001, {{5, 1000}, {500, 1}});
     width("flat", 100, {{7, 100}});
     printf("lanes %d %d %d\n", choose_lanes(1000, 12), choose_lanes(1000, 7), choose_lanes((int64_t)1 << 18, 12));

@@ -61,13 +61,27 @@ def legacy(out):
         u_normalised=c(out, "g16_u_normalised"), u_matvec=c(out, "g16_u_matvec"))
 
 
+def mg_edge4(out):
+    """tests/golden/mg_4x4_edge4.npz (harness case `mg 4`): G9's pieces with MG_Param's block edge 4 — ONE block of all 256 sites,
+    3072 unknowns, 4 vectors; `python make_golden.py mg_edge4` regenerates it alone"""
+    run(out, "mg", "4")
+    meta = d(out, "g9e4_meta", np.int64)
+    nblocks, bsz, ne, sub = (int(v) for v in meta[:4])
+    np.savez_compressed(
+        os.path.join(HERE, "mg_4x4_edge4.npz"), nblocks=nblocks, block_size=bsz, ne=ne, sub=sub, k=0.1,
+        block_map=d(out, "g9e4_block_map", np.int64).reshape(nblocks, bsz), P=c(out, "g9e4_P").reshape(nblocks, ne, 3072),
+        eigvec0=c(out, "g9e4_eigvec0"), eigvec1=c(out, "g9e4_eigvec1"),
+        v=c(out, "g9e4_v"), Rv=c(out, "g9e4_Rv"), PRv=c(out, "g9e4_PRv"), AcRv=c(out, "g9e4_AcRv"),
+        Ac_dense=c(out, "g9e4_Ac_dense").reshape(nblocks * ne, nblocks * ne))
+
+
 def main():
     if not os.path.exists(HARNESS):
         sys.exit("build the harness first: make -C oracle _ref")
     out = tempfile.mkdtemp(prefix="mgcr_gold_")
-    if sys.argv[1:] == ["legacy"]:
+    if sys.argv[1:] in (["legacy"], ["mg_edge4"]):
         try:
-            legacy(out)
+            (legacy if sys.argv[1] == "legacy" else mg_edge4)(out)
         finally:
             shutil.rmtree(out, ignore_errors=True)
         return
@@ -115,6 +129,7 @@ def main():
             v=c(out, "g9_v"), Rv=c(out, "g9_Rv"), PRv=c(out, "g9_PRv"), AcRv=c(out, "g9_AcRv"),
             Ac_dense=c(out, "g9_Ac_dense").reshape(nblocks * ne, nblocks * ne),
             identities=d(out, "g9_identities"))
+        mg_edge4(out)
 
         pois = {}
         run(out, "poisson", "32", "10", "p32")
