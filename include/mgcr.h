@@ -167,6 +167,42 @@ int mgcr_eo_merge(mgcr_op_t eo, mgcr_vec_t even, mgcr_vec_t odd, mgcr_vec_t full
 int mgcr_eo_prepare(mgcr_op_t eo, mgcr_vec_t b_full, mgcr_vec_t bhat_even);
 int mgcr_eo_reconstruct(mgcr_op_t eo, mgcr_vec_t b_full, mgcr_vec_t x_even, mgcr_vec_t x_full);
 /* (mgcr_eo_solve is declared below, with the solver entry points) */
+/* EvenOddDiagDiracOp / EvenOddSparse, the even-odd Schur solve for operators with a SITE diagonal (Poisson, a mass term, twisted
+ * mass, a shift): one complex number per row, so the diagonal blocks are scalars and their inverse is element-wise.  Write the full
+ * operator as A = diag(a) - c H with H the stored off-diagonal part; H must be two-colourable exactly as for mgcr_eo_create, and
+ * diagonal entries are ignored by the colouring and by its check (an odd cycle or a wrong caller bit is still MGCR_ERR_INVALID
+ * with the entry named).
+ *     Dirac form  (k_ri != NULL):  A = 1 - k D, D may store a diagonal d:   a = (1, 0) - k d,  c = k;   k = 0: MGCR_ERR_INVALID;
+ *     matrix form (k_ri == NULL):  A = M itself:                            a = d,             c = -1.
+ * d of a row = its stored diagonal entries added in stored order, 0 if it has none.  The Schur system on the even half is
+ *     S x_e = bhat_e,  S = diag(a_e) - c^2 H_eo diag(1/a_o) H_oe,  bhat_e = b_e + c H_eo (b_o / a_o),  x_o = (b_o + c H_oe x_e) / a_o.
+ * Complex products are (ar br - ai bi, ar bi + ai br), 1/a = (ar / den, -ai / den) with den = ar ar + ai ai, nothing is fused, and
+ * c2 = c c and cn = -c are formed once on the host.  a_e may contain zeros; an exactly zero or non-finite 1/a_o is
+ * MGCR_ERR_INVALID and the message names the full-system row.
+ * mgcr_eo_create_diag makes an EvenOddDiracOp (mgcr_op_nnz counts the whole matrix, diagonal included): every entry point that
+ * takes the operator of mgcr_eo_create takes this one — mgcr_op_apply, mgcr_gcr_solve, mgcr_gcr_create / mgcr_gcr_set_operator,
+ * the preconditioner slot, mgcr_eo_split / merge / prepare / reconstruct / solve, mgcr_eo_info / parity / half_op (the halves lent
+ * are the OFF-DIAGONAL halves H_eo, H_oe).  mgcr_eo_diag downloads a_e [n_e][2] and 1/a_o [n_o][2]; for an operator made by
+ * mgcr_eo_create both are all ones.  mgcr_eo_set_k on the Dirac form recomputes a and 1/a_o in stream order (work already
+ * enqueued keeps the old values); the singular check runs on the host first and a refused k leaves the operator at its previous
+ * k.  On the matrix form mgcr_eo_set_k is MGCR_ERR_INVALID.
+ * Refused with MGCR_ERR_UNSUPPORTED: mgcr_eo_multi_create and mgcr_eo_solve_queue on an operator that carries a diagonal (the
+ * diagonal 1 - k_j d would be per column), besides everything mgcr_eo_create's operator is refused by.
+ * Rule 1d (apply): with a_e and inv_o = 1/a_o from mgcr_eo_diag, the halves from mgcr_eo_half_op, and the element-wise products (.)
+ * formed on the host as real and imaginary parts with separate real operations, BIT-IDENTICAL are
+ *     mgcr_op_apply(eo, x, y)                and  u = H_oe(x); t = inv_o (.) u; v = H_eo(t); y = a_e (.) x - c2 v,
+ *     mgcr_eo_prepare                        and  b_e - cn H_eo(inv_o (.) b_o),
+ *     the odd half of mgcr_eo_reconstruct    and  inv_o (.) (b_o - cn H_oe(x_e));
+ * the even half of mgcr_eo_reconstruct is x_e itself.
+ * Rule 2d (solve): history, iteration count, convergence flag and x of a GCR solve on the operator are BIT-IDENTICAL with the
+ * option fused_apply on and off.  On: where H_eo is stored one thread per row, stage 2 of each step's apply takes the step's beta
+ * dot products (the counter "evenodd_diag_fused_steps"; "evenodd_fused_steps" does not move).
+ * Rule 3d (no diagonal): a matrix without any stored diagonal entry, made through mgcr_eo_create_diag in Dirac form, gives exactly
+ * what mgcr_eo_create gives for apply, prepare, reconstruct and solve — it IS that operator, on that code path. */
+int mgcr_eo_create_diag(int64_t n, const int64_t *rowptr, const int64_t *col, const double *val_ri,
+                        const int8_t *parity /* [n] 0 even, 1 odd; NULL: two-colour */, const double *k_ri /* [2]; NULL: matrix form */,
+                        mgcr_op_t *out);
+int mgcr_eo_diag(mgcr_op_t eo, double *a_even_ri /* [n_e][2] */, double *inv_a_odd_ri /* [n_o][2] */);
 /* MultiEvenOddDiracOp, even-odd hopping-parameter scans: the Schur complements S_j = 1 - k_j^2 D_eo D_oe on column j of a block of
  * exactly nk Fields of the even half (mgcr_op_dim = mgcr_op_nrow = n_e, mgcr_op_nnz = that of D).  The fewer steps of the even-odd
  * solve and the shared matrix stream and launches of the batched solve in one operator.  It BORROWS the two half matrices and the
@@ -293,7 +329,8 @@ int mgcr_set_option(const char *name, int value, int *previous);
  * "queue_admissions" = systems those loaded into a slot after step 0, "queue_steps" = lockstep steps they launched,
  * "eo_queue_solves" / "eo_queue_admissions" / "eo_queue_steps" = the same three for mgcr_eo_solve_queue,
  * "evenodd_fused_steps" = GCR steps on an even-odd preconditioned DiracOp whose second apply stage took the step's beta dot
- * products (mgcr_eo_create, Rule 2). */
+ * products (mgcr_eo_create, Rule 2),
+ * "evenodd_diag_fused_steps" = the same on an operator that carries a site diagonal (mgcr_eo_create_diag, Rule 2d). */
 int mgcr_stat(const char *name, int64_t *value);
 
 /* Self-test of the hardware behaviour the one-launch solver paths (csrc/gcr_resident.hip, gcr_stepbuild.hip) build on: inside

@@ -866,6 +866,13 @@ template <typename num_type>
 class EvenOddDiracOp : public Operator<num_type> {
 public:
     EvenOddDiracOp(Sparse<num_type> *mat, std::complex<double> k_factor, const std::vector<int8_t> *parity = nullptr) : k(k_factor) {
+        create(mat, parity, 0);
+    }
+
+protected:
+    // how: 0 mgcr_eo_create; 1 mgcr_eo_create_diag in Dirac form (k); 2 mgcr_eo_create_diag in matrix form (no k)
+    EvenOddDiracOp() {}
+    void create(Sparse<num_type> *mat, const std::vector<int8_t> *parity, int how) {
         mgcr_detail::ensure_init();
         const num_type rows = mat->get_nrow(), nnz = mat->get_nnz();
         if (rows != mat->get_dim()) { std::fprintf(stderr, "EvenOddDiracOp: matrix must be square\n"); std::abort(); }
@@ -875,13 +882,17 @@ public:
         for (num_type i = 0; i <= rows; i++) rp[(size_t)i] = (int64_t)mat->get_ROW(i);
         for (num_type i = 0; i < nnz; i++) { ci[(size_t)i] = (int64_t)mat->get_COL(i); va[(size_t)i] = mat->val_at(i); }
         double v[2] = {k.real(), k.imag()};
-        mgcr_detail::ok(mgcr_eo_create((int64_t)rows, rp.data(), ci.data(), reinterpret_cast<const double *>(va.data()), parity ? parity->data() : nullptr, v, &op),
-                        "EvenOddDiracOp");
+        const double *vals = reinterpret_cast<const double *>(va.data());
+        const int8_t *par = parity ? parity->data() : nullptr;
+        if (how == 0) mgcr_detail::ok(mgcr_eo_create((int64_t)rows, rp.data(), ci.data(), vals, par, v, &op), "EvenOddDiracOp");
+        else mgcr_detail::ok(mgcr_eo_create_diag((int64_t)rows, rp.data(), ci.data(), vals, par, how == 1 ? v : nullptr, &op), "EvenOddDiagDiracOp");
         int64_t nn = 0, ne = 0, no = 0;
         mgcr_detail::ok(mgcr_eo_info(op, &nn, &ne, &no), "EvenOddDiracOp");
         n = (num_type)nn; n_even = (num_type)ne; n_odd = (num_type)no;
         this->dim = n_even;
     }
+
+public:
     EvenOddDiracOp(EvenOddDiracOp const &) = delete;
     EvenOddDiracOp &operator=(EvenOddDiracOp const &) = delete;
     ~EvenOddDiracOp() override { if (op) mgcr_op_destroy(op); }
@@ -976,7 +987,7 @@ public:
     std::vector<int> queue_iterations;
     std::vector<bool> queue_converged;
 
-private:
+protected:
     static std::complex<double> not_stored() {
         std::fprintf(stderr, "EvenOddDiracOp::val_at: the Schur complement is applied, never formed\n");
         std::abort();
@@ -984,6 +995,36 @@ private:
     std::complex<double> k = 0.;
     num_type n = 0, n_even = 0, n_odd = 0;
     mgcr_op_t op = nullptr;
+};
+
+// EvenOddDiagDiracOp: the even-odd preconditioned Id - k D where D may store a SITE diagonal d (extension, mgcr_eo_create_diag in
+// Dirac form): with a = 1 - k d the operator on the even half is S = diag(a_e) - k^2 D_eo diag(1/a_o) D_oe, D_eo / D_oe the
+// off-diagonal halves.  Everything else is EvenOddDiracOp's; solve_queue and MultiEvenOddDiracOp refuse an operator that carries a
+// diagonal.  diag() downloads a_e and 1 / a_o as the device holds them.
+template <typename num_type>
+class EvenOddDiagDiracOp : public EvenOddDiracOp<num_type> {
+public:
+    EvenOddDiagDiracOp(Sparse<num_type> *mat, std::complex<double> k_factor, const std::vector<int8_t> *parity = nullptr) {
+        this->k = k_factor;
+        this->create(mat, parity, 1);
+    }
+    void diag(std::vector<std::complex<double>> &a_even, std::vector<std::complex<double>> &inv_a_odd) {
+        a_even.resize((size_t)this->n_even);
+        inv_a_odd.resize((size_t)this->n_odd);
+        mgcr_detail::ok(mgcr_eo_diag(this->op, reinterpret_cast<double *>(a_even.data()), reinterpret_cast<double *>(inv_a_odd.data())), "EvenOddDiagDiracOp::diag");
+    }
+
+protected:
+    EvenOddDiagDiracOp() {}
+};
+
+// EvenOddSparse: the even-odd preconditioned form of a matrix M ITSELF (extension, mgcr_eo_create_diag in matrix form): a Poisson
+// matrix, a Wilson operator written with its mass term.  S = diag(d_e) - M_eo diag(1/d_o) M_oe on the even half; solve() solves
+// M x_full = rhs_full.  There is no hopping parameter: set_k is refused by the library.
+template <typename num_type>
+class EvenOddSparse : public EvenOddDiagDiracOp<num_type> {
+public:
+    explicit EvenOddSparse(Sparse<num_type> *mat, const std::vector<int8_t> *parity = nullptr) { this->create(mat, parity, 2); }
 };
 
 // MultiEvenOddDiracOp: the Schur complements Id - ks[j]^2 D_eo D_oe of ONE hopping matrix on column j of a block of ks.size() Fields

@@ -141,6 +141,8 @@ _SIGS = {
     "mgcr_eo_solve_queue": (C.c_int, [_vp, C.POINTER(GcrParamC), C.c_int32, C.c_int32, C.POINTER(_vp), C.POINTER(_vp), _dp, _vp, C.c_int32,
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mgcr_eo_create": (C.c_int, [C.c_int64, _vp, _vp, _vp, _vp, _dp, C.POINTER(_vp)]),
+    "mgcr_eo_create_diag": (C.c_int, [C.c_int64, _vp, _vp, _vp, _vp, _dp, C.POINTER(_vp)]),
+    "mgcr_eo_diag": (C.c_int, [_vp, _vp, _vp]),
     "mgcr_eo_set_k": (C.c_int, [_vp, _dp]),
     "mgcr_eo_info": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mgcr_eo_parity": (C.c_int, [_vp, _vp]),

@@ -541,6 +541,55 @@ class EvenOddDiracOp(Operator):
         return x_list
 
 
+class EvenOddDiagDiracOp(EvenOddDiracOp):
+    """The even-odd preconditioned Id - k*D where D may store a SITE diagonal d (mgcr_eo_create_diag, Dirac form): with
+    a = 1 - k d the operator on the even half is S = diag(a_e) - k^2 D_eo diag(1/a_o) D_oe, D_eo / D_oe the off-diagonal halves.
+    Everything else is EvenOddDiracOp's: split / merge / prepare / reconstruct / solve / halves are inherited.  The scans
+    (MultiEvenOddDiracOp, solve_queue) refuse an operator that carries a diagonal.  A matrix without any diagonal entry gives
+    exactly EvenOddDiracOp(mat, k)."""
+
+    _who = "EvenOddDiagDiracOp"
+
+    def __init__(self, mat, k, parity=None):
+        Operator.__init__(self)
+        self._create(mat, _ri(k), parity)
+
+    def _create(self, mat, k_ri, parity):
+        _lib.init()
+        n = int(mat._shape[0])
+        if mat._shape[0] != mat._shape[1]:
+            raise MgcrError(1, "%s: matrix must be square" % self._who)
+        par = None if parity is None else np.ascontiguousarray(parity, np.int8)
+        if par is not None and par.size != n:
+            raise MgcrError(1, "%s: parity has %d entries, the matrix has %d rows" % (self._who, par.size, n))
+        h = C.c_void_p()
+        check(_lib.lib().mgcr_eo_create_diag(n, mat.ROW.ctypes.data, mat.COL.ctypes.data, mat.VAL.ctypes.data,
+                                             par.ctypes.data if par is not None else None, k_ri, C.byref(h)))
+        self.h = h
+        self.last_history = None
+        self.last_iterations = None
+        self.last_converged = None
+
+    def diag(self):
+        """(a_even, 1 / a_odd): the two element-wise factors of the Schur apply as the device holds them"""
+        _, ne, no = self.sizes()
+        a, inv = np.empty(ne, c128), np.empty(no, c128)
+        check(_lib.lib().mgcr_eo_diag(self.h, a.ctypes.data, inv.ctypes.data))
+        return a, inv
+
+
+class EvenOddSparse(EvenOddDiagDiracOp):
+    """The even-odd preconditioned form of a matrix M ITSELF (mgcr_eo_create_diag, matrix form): M = diag(d) + offdiag, a Poisson
+    matrix or a Wilson operator written with its mass term; S = diag(d_e) - M_eo diag(1/d_o) M_oe on the even half, and solve()
+    solves M x_full = rhs_full.  There is no hopping parameter: set_k raises."""
+
+    _who = "EvenOddSparse"
+
+    def __init__(self, mat, parity=None):
+        Operator.__init__(self)
+        self._create(mat, None, parity)
+
+
 class MultiEvenOddDiracOp(Operator):
     """The Schur complements Id - ks[j]^2 D_eo D_oe of ONE hopping matrix on column j of a block of len(ks) Fields of the even
     half: an even-odd hopping-parameter scan as one operator (mgcr_eo_multi_create; no reference counterpart).  Borrows the halves

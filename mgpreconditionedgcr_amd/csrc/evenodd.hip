@@ -27,6 +27,7 @@ void eo_destroy(EoState *e) {
     for (mgcr_op_s *h : e->half)
         if (h) { csr_free(&h->csr); delete h; }
     hipFree(e->d_even); hipFree(e->d_odd); hipFree(e->t);
+    eo_diag_destroy(e);
     gcr_state_destroy(e->solver);
     for (cplx *w : e->work) hipFree(w);
     delete e;
@@ -55,18 +56,18 @@ __global__ void __launch_bounds__(RED_THREADS) eo_merge_kernel(cplx *__restrict_
         else full[od[i - ne]] = odd[i - ne];
     }
 }
-static int eo_split(const EoState *e, const cplx *full, cplx *even, cplx *odd) {
+int eo_split(const EoState *e, const cplx *full, cplx *even, cplx *odd) {
     if (e->n == 0) return MGCR_OK;
     return launch(eo_split_kernel, (unsigned)red_grid(e->n), RED_THREADS, 0, full, even, odd, (const int32_t *)e->d_even, (const int32_t *)e->d_odd,
                   e->ne, e->no);
 }
-static int eo_merge(const EoState *e, cplx *full, const cplx *even, const cplx *odd) {
+int eo_merge(const EoState *e, cplx *full, const cplx *even, const cplx *odd) {
     if (e->n == 0) return MGCR_OK;
     return launch(eo_merge_kernel, (unsigned)red_grid(e->n), RED_THREADS, 0, full, even, odd, (const int32_t *)e->d_even, (const int32_t *)e->d_odd,
                   e->ne, e->no);
 }
 
-static int eo_work(EoState *e, EoState::Work which, cplx **out) {
+int eo_work(EoState *e, EoState::Work which, cplx **out) {
     if (!e->work[which]) {
         const int64_t len = (which == EoState::W_BO || which == EoState::W_XO || which == EoState::W_UO) ? e->no : e->ne;
         hipError_t rc = hipMalloc((void **)&e->work[which], sizeof(cplx) * (size_t)(len ? len : 1));
@@ -86,7 +87,7 @@ __global__ void __launch_bounds__(RED_THREADS) eo_sub_scaled_kernel(cplx *__rest
 // y = w - c (H x) for half H (0: D_eo, 1: D_oe) with the bits of "u = H x, then y = w - c u" (Rule 1 of include/mgcr.h).  The SpMV's
 // shifted epilogue forms exactly that — unless the half keeps long rows in a CSR tail, whose kernels subtract their part of the row in a
 // second step ((w - c s_slab) - c s_tail): such a half is multiplied unshifted into a work Field and subtracted in a launch of its own.
-static int eo_shift_apply(EoState *e, int h, const cplx *x, cplx *y, cplx c, const cplx *w) {
+int eo_shift_apply(EoState *e, int h, const cplx *x, cplx *y, cplx c, const cplx *w) {
     const CsrDev &A = e->half[h]->csr;
     if (A.nrow == 0) return MGCR_OK;
     if (A.n_tail_rows == 0) return csr_apply(A, x, y, true, c, nullptr, w);
@@ -100,6 +101,7 @@ static int eo_shift_apply(EoState *e, int h, const cplx *x, cplx *y, cplx c, con
 int eo_apply(Op *op, const cplx *x, cplx *y, int64_t n) {
     EoState *e = op->eo;
     MGCR_CHECK(e && n == e->ne, MGCR_ERR_INVALID, "even-odd DiracOp: the Field must have the %lld entries of the even half", (long long)(e ? e->ne : 0));
+    if (e->has_diag) return eo_diag_apply(e, x, y);   // a site diagonal: evenodd_diag.hip
     MGCR_CHECK(e->k.x != 0. || e->k.y != 0., MGCR_ERR_INVALID, "No k value supplied for Dirac Operator!");
     MGCR_TRY(csr_apply(e->half[1]->csr, x, e->t, false, make_double2(0., 0.)));
     return eo_shift_apply(e, 0, e->t, y, e->k2, x);
@@ -163,6 +165,7 @@ __global__ void __launch_bounds__(RED_THREADS, ((MODE == 1 || (MODE == 3 && WT <
 
 bool eo_schur_fusable(const Op *op) {
     if (!op || op->kind != OP_DIRAC_EO || !op->eo || !fuse_enabled()) return false;
+    if (op->eo->has_diag) return eo_diag_schur_fusable(op->eo);
     const CsrDev &A = op->eo->half[0]->csr;
     if (A.pat_mode == 1 && (int64_t)A.npat * A.W * 20 > 48 * 1024) return false;   // the pattern table must fit LDS
     if (csr_stencil_active(A) && A.sten_rare) return false;                        // (no rare-tail form: see the kernel)
@@ -174,6 +177,7 @@ int eo_schur_step(Op *op, const cplx *x, cplx *y, const cplx *const *vecs, int n
     MGCR_CHECK(x != y, MGCR_ERR_INVALID, "SpMV cannot run in place");
     MGCR_CHECK(nd >= 1 && nd <= FND, MGCR_ERR_INVALID, "eo_schur_step: 1..%d vectors", FND);
     MGCR_CHECK(rm.band == 0, MGCR_ERR_INVALID, "eo_schur_step: plain row map only");
+    if (e->has_diag) return eo_diag_schur_step(e, x, y, vecs, nd, parts, rm);
     MGCR_CHECK(e->k.x != 0. || e->k.y != 0., MGCR_ERR_INVALID, "No k value supplied for Dirac Operator!");
     MGCR_TRY(csr_apply(e->half[1]->csr, x, e->t, false, make_double2(0., 0.)));
     const CsrDev &A = e->half[0]->csr;
@@ -207,8 +211,30 @@ int eo_schur_step(Op *op, const cplx *x, cplx *y, const cplx *const *vecs, int n
     });
 }
 
+// the two halves as Sparse operators, the index lists and t on the device; e->ne / e->no must be set.  On failure the caller destroys e.
+int eo_build_halves(EoState *e, const EvenOddPlan &plan, const char *who) {
+    const HalfCsr *hc[2] = {&plan.eo, &plan.oe};
+    for (int h = 0; h < 2; h++) {
+        mgcr_op_s *op = new mgcr_op_s();
+        op->kind = OP_CSR;
+        op->dim = hc[h]->ncol;
+        op->nrow = hc[h]->nrow;
+        e->half[h] = op;
+        MGCR_TRY(csr_build_device(hc[h]->nrow, hc[h]->ncol, hc[h]->rowptr.data(), hc[h]->col.data(), hc[h]->val_ri.data(), &op->csr));
+    }
+    std::vector<int32_t> ev(plan.even.begin(), plan.even.end()), od(plan.odd.begin(), plan.odd.end());
+    hipError_t rc = hipMalloc((void **)&e->d_even, sizeof(int32_t) * (ev.size() ? ev.size() : 1));
+    if (rc == hipSuccess) rc = hipMalloc((void **)&e->d_odd, sizeof(int32_t) * (od.size() ? od.size() : 1));
+    if (rc == hipSuccess) rc = hipMalloc((void **)&e->t, sizeof(cplx) * (size_t)(e->no ? e->no : 1));
+    if (rc == hipSuccess && !ev.empty()) rc = hipMemcpy(e->d_even, ev.data(), sizeof(int32_t) * ev.size(), hipMemcpyHostToDevice);
+    if (rc == hipSuccess && !od.empty()) rc = hipMemcpy(e->d_odd, od.data(), sizeof(int32_t) * od.size(), hipMemcpyHostToDevice);
+    MGCR_CHECK(rc == hipSuccess, MGCR_ERR_ALLOC, "%s: device allocation failed: %s", who, hipGetErrorString(rc));
+    return MGCR_OK;
+}
+
 // bhat = b_e - (-k) (D_eo b_o); the halves of b stay in W_BE, W_BO
 static int eo_prepare(EoState *e, const cplx *b_full, cplx *bhat) {
+    if (e->has_diag) return eo_diag_prepare(e, b_full, bhat);
     cplx *be, *bo;
     MGCR_TRY(eo_work(e, EoState::W_BE, &be));
     MGCR_TRY(eo_work(e, EoState::W_BO, &bo));
@@ -217,6 +243,7 @@ static int eo_prepare(EoState *e, const cplx *b_full, cplx *bhat) {
 }
 // x_o = b_o - (-k) (D_oe x_e), then x_full = merge(x_e, x_o)
 static int eo_reconstruct(EoState *e, const cplx *b_full, const cplx *xe, cplx *x_full) {
+    if (e->has_diag) return eo_diag_reconstruct(e, b_full, xe, x_full);
     cplx *bo, *xo;
     MGCR_TRY(eo_work(e, EoState::W_BO, &bo));
     MGCR_TRY(eo_work(e, EoState::W_XO, &xo));
@@ -254,27 +281,8 @@ int mgcr_eo_create(int64_t n, const int64_t *rowptr, const int64_t *col, const d
     e->parity = plan.parity;
     e->k = make_double2(k_ri[0], k_ri[1]);
     e->k2 = host_cmul(e->k, e->k);
-    auto fail = [&](int rc) { eo_destroy(e); return rc; };
-    const HalfCsr *hc[2] = {&plan.eo, &plan.oe};
-    for (int h = 0; h < 2; h++) {
-        mgcr_op_s *op = new mgcr_op_s();
-        op->kind = OP_CSR;
-        op->dim = hc[h]->ncol;
-        op->nrow = hc[h]->nrow;
-        e->half[h] = op;
-        int rc = csr_build_device(hc[h]->nrow, hc[h]->ncol, hc[h]->rowptr.data(), hc[h]->col.data(), hc[h]->val_ri.data(), &op->csr);
-        if (rc != MGCR_OK) return fail(rc);
-    }
-    std::vector<int32_t> ev(plan.even.begin(), plan.even.end()), od(plan.odd.begin(), plan.odd.end());
-    hipError_t rc = hipMalloc((void **)&e->d_even, sizeof(int32_t) * (ev.size() ? ev.size() : 1));
-    if (rc == hipSuccess) rc = hipMalloc((void **)&e->d_odd, sizeof(int32_t) * (od.size() ? od.size() : 1));
-    if (rc == hipSuccess) rc = hipMalloc((void **)&e->t, sizeof(cplx) * (size_t)(e->no ? e->no : 1));
-    if (rc == hipSuccess && !ev.empty()) rc = hipMemcpy(e->d_even, ev.data(), sizeof(int32_t) * ev.size(), hipMemcpyHostToDevice);
-    if (rc == hipSuccess && !od.empty()) rc = hipMemcpy(e->d_odd, od.data(), sizeof(int32_t) * od.size(), hipMemcpyHostToDevice);
-    if (rc != hipSuccess) {
-        set_error("mgcr_eo_create: device allocation failed: %s", hipGetErrorString(rc));
-        return fail(MGCR_ERR_ALLOC);
-    }
+    int brc = eo_build_halves(e, plan, "mgcr_eo_create");
+    if (brc != MGCR_OK) { eo_destroy(e); return brc; }
     mgcr_op_s *op = new mgcr_op_s();
     op->kind = OP_DIRAC_EO;
     op->dim = op->nrow = e->ne;
@@ -290,6 +298,7 @@ int mgcr_eo_set_k(mgcr_op_t eo, const double k_ri[2]) {
     MGCR_CHECK(k_ri, MGCR_ERR_INVALID, "mgcr_eo_set_k: null argument");
     MGCR_CHECK(k_ri[0] != 0. || k_ri[1] != 0., MGCR_ERR_INVALID, "mgcr_eo_set_k: No k value supplied for Dirac Operator!");
     LOCK();
+    if (eo->eo->has_diag) return eo_diag_set_k(eo, make_double2(k_ri[0], k_ri[1]));
     eo->eo->k = eo->k = make_double2(k_ri[0], k_ri[1]);
     eo->eo->k2 = host_cmul(eo->k, eo->k);
     return MGCR_OK;

@@ -136,4 +136,46 @@ inline bool evenodd_plan_build(int64_t n, const int64_t *rowptr, const int64_t *
     return true;
 }
 
+// The plan of a matrix that may store a site diagonal (evenodd_diag.hip): the diagonal entries are taken out and added up per row,
+// in stored order, into d[n] (interleaved (re, im); 0 for a row without one) — *n_diag counts them —, and evenodd_plan_build runs
+// on what is left: the colouring and its check never see a diagonal entry, an odd cycle or a wrong caller bit is refused with the
+// message above, and the halves hold the off-diagonal entries in stored order.
+inline bool evenodd_plan_build_diag(int64_t n, const int64_t *rowptr, const int64_t *col, const double *val_ri, const int8_t *parity_in,
+                                    EvenOddPlan *out, std::vector<double> *d, int64_t *n_diag, std::string *err) {
+    auto fail = [&](const char *m) { if (err) *err = m; return false; };
+    if (n < 0 || !rowptr || !out || !d) return fail("even-odd plan: bad argument");
+    // (everything else about the arrays is checked by evenodd_plan_build, on the copy; what must hold before the copy is made:)
+    if (rowptr[0] != 0) return fail("even-odd plan: rowptr[0] must be 0");
+    for (int64_t r = 0; r < n; r++)
+        if (rowptr[r + 1] < rowptr[r]) {
+            char msg[256];
+            snprintf(msg, sizeof msg, "even-odd plan: rowptr is not non-decreasing at row %lld", (long long)r);
+            return fail(msg);
+        }
+    const int64_t nnz = rowptr[n];
+    if (nnz > 0 && (!col || !val_ri)) return fail("even-odd plan: null column or value array");
+    d->assign(2 * (size_t)n, 0.);
+    std::vector<int64_t> rp((size_t)n + 1, 0), cc;
+    std::vector<double> vv;
+    cc.reserve((size_t)nnz);
+    vv.reserve(2 * (size_t)nnz);
+    int64_t nd = 0;
+    for (int64_t r = 0; r < n; r++) {
+        for (int64_t e = rowptr[r]; e < rowptr[r + 1]; e++) {
+            if (col[e] == r) {
+                (*d)[2 * (size_t)r] += val_ri[2 * e];
+                (*d)[2 * (size_t)r + 1] += val_ri[2 * e + 1];
+                nd++;
+            } else {
+                cc.push_back(col[e]);
+                vv.push_back(val_ri[2 * e]);
+                vv.push_back(val_ri[2 * e + 1]);
+            }
+        }
+        rp[(size_t)r + 1] = (int64_t)cc.size();
+    }
+    if (n_diag) *n_diag = nd;
+    return evenodd_plan_build(n, rp.data(), cc.data(), vv.data(), parity_in, out, err);
+}
+
 }  // namespace mgcr

@@ -192,6 +192,9 @@ int mgcr_eo_solve_queue(mgcr_op_t eo, const mgcr_gcr_param *param, int32_t width
     MGCR_CHECK(eo && param && rhs_full && x_full && k_ri, MGCR_ERR_INVALID, "%s: null argument", who);
     MGCR_CHECK(eo->kind == OP_DIRAC_EO && eo->eo, MGCR_ERR_INVALID,
                "%s: the operator must be an even-odd preconditioned DiracOp (its halves carry the queue; the hopping parameters come per system)", who);
+    MGCR_CHECK(!eo->eo->has_diag, MGCR_ERR_UNSUPPORTED,
+               "%s: the operator carries a site diagonal (mgcr_eo_create_diag): 1 - k_s d would differ from column to column, which the scans "
+               "do not support; solve one k at a time with mgcr_eo_solve", who);
     MGCR_CHECK(width >= 1 && width <= MV_MAX_K, MGCR_ERR_INVALID, "%s: width = %d slots, 1 .. %d are supported", who, (int)width, MV_MAX_K);
     MGCR_CHECK(nsys >= 1, MGCR_ERR_INVALID, "%s: nsys = %d systems", who, (int)nsys);
     // (the restrictions of mgcr_eo_multi_solve, checked before anything is enqueued)

@@ -7,6 +7,8 @@
 
 namespace mgcr {
 
+struct EvenOddPlan;   // evenodd_plan.h
+
 struct EoState {
     int64_t n = 0, ne = 0, no = 0, nnz = 0;
     std::vector<int8_t> parity;
@@ -21,9 +23,32 @@ struct EoState {
     cplx *work[W_COUNT] = {};
     // the solver of mgcr_eo_solve: kept between calls with its Krylov vectors, like a GCR object's (a k ladder allocates once)
     GcrState *solver = nullptr;
+    // The site diagonal (evenodd_diag.hip, mgcr_eo_create_diag): A = diag(a) - c H with H the two halves.  Dirac form: a = 1 - k d,
+    // c = k; matrix form: a = d, c = -1.  has_diag false: everything below is unused and every call takes evenodd.hip's own path.
+    bool has_diag = false, matrix_form = false;
+    std::vector<cplx> h_d_even, h_d_odd;               // d in list order, on the host (the singular check of set_k)
+    cplx *dd_even = nullptr, *dd_odd = nullptr;        // ... and on the device
+    cplx *a_even = nullptr, *inv_a_odd = nullptr;      // [n_e] a, [n_o] 1 / a: written in stream order by diag_coeff_kernel
+    cplx c = {0., 0.}, c2 = {0., 0.}, cn = {0., 0.};   // c, c c and -c, formed once on the host
 };
 
 // k k as mgcr_eo_set_k forms it: on the host, un-fused
 inline cplx host_cmul(cplx a, cplx b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+
+// ---- evenodd.hip's host pieces that evenodd_diag.hip builds on ---------------------------------------------------------------
+int eo_split(const EoState *e, const cplx *full, cplx *even, cplx *odd);
+int eo_merge(const EoState *e, cplx *full, const cplx *even, const cplx *odd);
+int eo_work(EoState *e, EoState::Work which, cplx **out);
+int eo_shift_apply(EoState *e, int h, const cplx *x, cplx *y, cplx c, const cplx *w);   // y = w - c (H x), bits of "u = H x; y = w - c u"
+int eo_build_halves(EoState *e, const EvenOddPlan &plan, const char *who);   // the two Sparse halves, the index lists and t
+
+// ---- evenodd_diag.hip: the same four operations on an operator with a site diagonal (EoState::has_diag) ------------------------
+void eo_diag_destroy(EoState *e);
+int eo_diag_set_k(Op *op, cplx k);
+int eo_diag_apply(EoState *e, const cplx *x, cplx *y);
+bool eo_diag_schur_fusable(const EoState *e);
+int eo_diag_schur_step(EoState *e, const cplx *x, cplx *y, const cplx *const *vecs, int nd, double *parts, const RowMap &rm);
+int eo_diag_prepare(EoState *e, const cplx *b_full, cplx *bhat);
+int eo_diag_reconstruct(EoState *e, const cplx *b_full, const cplx *xe, cplx *x_full);
 
 }  // namespace mgcr
