@@ -203,6 +203,57 @@ int mgcr_eo_create_diag(int64_t n, const int64_t *rowptr, const int64_t *col, co
                         const int8_t *parity /* [n] 0 even, 1 odd; NULL: two-colour */, const double *k_ri /* [2]; NULL: matrix form */,
                         mgcr_op_t *out);
 int mgcr_eo_diag(mgcr_op_t eo, double *a_even_ri /* [n_e][2] */, double *inv_a_odd_ri /* [n_o][2] */);
+/* EvenOddBlockDiracOp / EvenOddBlockSparse, the even-odd Schur solve for operators with a dense BLOCK PER SITE on the diagonal
+ * (clover-type operators, a mass matrix, a local potential, block Poisson).  Sites are runs of bs consecutive rows: row r belongs
+ * to site r / bs, n % bs == 0, 1 <= bs <= 16.  Write the full operator as A = B - c H: H the stored entries between different
+ * sites, B block diagonal, one bs x bs complex block per site built from the stored entries inside the site.
+ *     Dirac form  (k_ri != NULL):  A = 1 - k D:   B_s = I - k D_ss ((1, 0) - k d on the diagonal, (0, 0) - k d off it),  c = k;
+ *     matrix form (k_ri == NULL):  A = M itself:  B_s = D_ss,                                                             c = -1.
+ * Entry (i, j) of D_ss = the stored entries at that position added in stored order, 0 if none is stored.  The rows of a site
+ * share one colour: the colouring runs on the SITE graph of H (as mgcr_eo_create colours rows), a caller parity [n] must be
+ * constant inside every site, and the index lists stay ascending, so half-site s' occupies the half rows s' bs .. s' bs + bs - 1.
+ *     S x_e = bhat_e,  S = B_e - c^2 H_eo B_o^-1 H_oe,  bhat_e = b_e + c H_eo (B_o^-1 b_o),  x_o = B_o^-1 (b_o + c H_oe x_e).
+ * Complex products are (ar br - ai bi, ar bi + ai br), 1/a = (ar / den, -ai / den) with den = ar ar + ai ai, nothing is fused,
+ * c2 = c c and cn = -c are formed once on the host, and a block-vector product (B (.) x)_i is B_i0 x_0, then + B_ij x_j for
+ * j = 1 .. bs - 1 ascending, real and imaginary parts accumulated separately.  B_o^-1 is formed on the device by Gauss-Jordan
+ * elimination with partial pivoting on [B | I]: for each pivot column p = 0 .. bs - 1 the row i >= p with the largest re^2 + im^2
+ * in column p (the first maximum wins) is swapped into row p, piv = 1 / a_pp, every entry of row p is multiplied by piv, and every
+ * other row i, with f = a_ip, becomes row_i - f (.) row_p entry by entry; the right half is then B^-1.
+ * mgcr_eo_create_block makes an EvenOddDiracOp (mgcr_op_nnz counts the whole matrix): every entry point that takes the operator
+ * of mgcr_eo_create_diag takes this one — mgcr_op_apply, mgcr_gcr_solve, mgcr_gcr_create / mgcr_gcr_set_operator, the
+ * preconditioner slot, mgcr_eo_split / merge / prepare / reconstruct / solve, mgcr_eo_info / parity / half_op (the halves lent are
+ * the INTER-SITE halves H_eo, H_oe).  mgcr_eo_block_info gives bs and the number of even and odd sites; mgcr_eo_block_diag
+ * downloads B of the even sites [sites_e][bs][bs][2] and B^-1 of the odd sites [sites_o][bs][bs][2], row-major (for an operator
+ * without blocks: bs = 1 and what mgcr_eo_diag gives).  On an operator with blocks mgcr_eo_diag is MGCR_ERR_INVALID.
+ * mgcr_eo_set_k on the Dirac form recomputes the blocks in stream order (work already enqueued keeps the old ones); it inverts
+ * into a spare buffer and the host reads one status word — ONE synchronisation per call — before the buffers are swapped, so a
+ * refused k leaves the operator at its previous k, blocks included.  On the matrix form mgcr_eo_set_k is MGCR_ERR_INVALID.
+ * MGCR_ERR_INVALID, with the entry, site or row named: bs outside 1 .. 16; n % bs != 0; k = 0; an odd cycle in the site graph (one
+ * inter-site entry (row, column) on it is named); a caller parity that differs inside a site; a caller parity that gives both
+ * ends of an inter-site entry one colour; an odd block whose elimination meets an exactly zero or non-finite pivot (den): the
+ * message names the site and the full-system row of the pivot column — at creation and in mgcr_eo_set_k.  Even blocks may be
+ * singular.
+ * Refused with MGCR_ERR_UNSUPPORTED: mgcr_eo_multi_create and mgcr_eo_solve_queue on an operator with blocks (dense site blocks
+ * would be per column), besides everything mgcr_eo_create's operator is refused by.
+ * Rule 1b (blocks): what mgcr_eo_block_diag downloads is BIT-IDENTICAL to the entry-by-entry formulas and the elimination above.
+ * Rule 2b (apply): with B_e and invB_o from mgcr_eo_block_diag, the halves from mgcr_eo_half_op, and the block products (.)
+ * formed on the host in the stated order, BIT-IDENTICAL are
+ *     mgcr_op_apply(eo, x, y)                and  y = B_e (.) x - c2 H_eo(invB_o (.) H_oe(x)),
+ *     mgcr_eo_prepare                        and  b_e - cn H_eo(invB_o (.) b_o),
+ *     the odd half of mgcr_eo_reconstruct    and  invB_o (.) (b_o - cn H_oe(x_e));
+ * the even half of mgcr_eo_reconstruct is x_e itself.
+ * Rule 3b (solve): history, iteration count, convergence flag and x of a GCR solve on the operator are BIT-IDENTICAL with the
+ * option fused_apply on and off.  On: the last launch of each step's apply takes the step's beta dot products (the counter
+ * "evenodd_block_fused_steps"; "evenodd_fused_steps" and "evenodd_diag_fused_steps" do not move).  mgcr_eo_solve equals
+ * mgcr_eo_prepare + mgcr_gcr_solve on the operator + mgcr_eo_reconstruct, bit for bit.
+ * Rule 4b (bs = 1): mgcr_eo_create_block with bs = 1 gives exactly what mgcr_eo_create_diag gives for apply, prepare,
+ * reconstruct and solve — it IS that operator, on that code path ("evenodd_diag_fused_steps" moves, the block counters do not). */
+int mgcr_eo_create_block(int64_t n, const int64_t *rowptr, const int64_t *col, const double *val_ri, int32_t bs,
+                         const int8_t *parity /* [n]; NULL: two-colour the sites */, const double *k_ri /* [2]; NULL: matrix form */,
+                         mgcr_op_t *out);
+int mgcr_eo_block_info(mgcr_op_t eo, int32_t *bs, int64_t *sites_even, int64_t *sites_odd);
+int mgcr_eo_block_diag(mgcr_op_t eo, double *B_even_ri /* [sites_e][bs][bs][2], row-major */,
+                       double *invB_odd_ri /* [sites_o][bs][bs][2] */);
 /* MultiEvenOddDiracOp, even-odd hopping-parameter scans: the Schur complements S_j = 1 - k_j^2 D_eo D_oe on column j of a block of
  * exactly nk Fields of the even half (mgcr_op_dim = mgcr_op_nrow = n_e, mgcr_op_nnz = that of D).  The fewer steps of the even-odd
  * solve and the shared matrix stream and launches of the batched solve in one operator.  It BORROWS the two half matrices and the
@@ -330,7 +381,9 @@ int mgcr_set_option(const char *name, int value, int *previous);
  * "eo_queue_solves" / "eo_queue_admissions" / "eo_queue_steps" = the same three for mgcr_eo_solve_queue,
  * "evenodd_fused_steps" = GCR steps on an even-odd preconditioned DiracOp whose second apply stage took the step's beta dot
  * products (mgcr_eo_create, Rule 2),
- * "evenodd_diag_fused_steps" = the same on an operator that carries a site diagonal (mgcr_eo_create_diag, Rule 2d). */
+ * "evenodd_diag_fused_steps" = the same on an operator that carries a site diagonal (mgcr_eo_create_diag, Rule 2d),
+ * "evenodd_block_applies" = Schur applies of an operator with a dense block per site (mgcr_eo_create_block), inside GCR steps or
+ * not, "evenodd_block_fused_steps" = its GCR steps whose last apply launch took the step's beta dot products (Rule 3b). */
 int mgcr_stat(const char *name, int64_t *value);
 
 /* Self-test of the hardware behaviour the one-launch solver paths (csrc/gcr_resident.hip, gcr_stepbuild.hip) build on: inside

@@ -870,9 +870,10 @@ public:
     }
 
 protected:
-    // how: 0 mgcr_eo_create; 1 mgcr_eo_create_diag in Dirac form (k); 2 mgcr_eo_create_diag in matrix form (no k)
+    // how: 0 mgcr_eo_create; 1 mgcr_eo_create_diag in Dirac form (k); 2 mgcr_eo_create_diag in matrix form (no k);
+    // 3 / 4 mgcr_eo_create_block in Dirac / matrix form with sites of bs rows
     EvenOddDiracOp() {}
-    void create(Sparse<num_type> *mat, const std::vector<int8_t> *parity, int how) {
+    void create(Sparse<num_type> *mat, const std::vector<int8_t> *parity, int how, int bs = 1) {
         mgcr_detail::ensure_init();
         const num_type rows = mat->get_nrow(), nnz = mat->get_nnz();
         if (rows != mat->get_dim()) { std::fprintf(stderr, "EvenOddDiracOp: matrix must be square\n"); std::abort(); }
@@ -885,7 +886,8 @@ protected:
         const double *vals = reinterpret_cast<const double *>(va.data());
         const int8_t *par = parity ? parity->data() : nullptr;
         if (how == 0) mgcr_detail::ok(mgcr_eo_create((int64_t)rows, rp.data(), ci.data(), vals, par, v, &op), "EvenOddDiracOp");
-        else mgcr_detail::ok(mgcr_eo_create_diag((int64_t)rows, rp.data(), ci.data(), vals, par, how == 1 ? v : nullptr, &op), "EvenOddDiagDiracOp");
+        else if (how <= 2) mgcr_detail::ok(mgcr_eo_create_diag((int64_t)rows, rp.data(), ci.data(), vals, par, how == 1 ? v : nullptr, &op), "EvenOddDiagDiracOp");
+        else mgcr_detail::ok(mgcr_eo_create_block((int64_t)rows, rp.data(), ci.data(), vals, (int32_t)bs, par, how == 3 ? v : nullptr, &op), "EvenOddBlockDiracOp");
         int64_t nn = 0, ne = 0, no = 0;
         mgcr_detail::ok(mgcr_eo_info(op, &nn, &ne, &no), "EvenOddDiracOp");
         n = (num_type)nn; n_even = (num_type)ne; n_odd = (num_type)no;
@@ -1025,6 +1027,45 @@ template <typename num_type>
 class EvenOddSparse : public EvenOddDiagDiracOp<num_type> {
 public:
     explicit EvenOddSparse(Sparse<num_type> *mat, const std::vector<int8_t> *parity = nullptr) { this->create(mat, parity, 2); }
+};
+
+// EvenOddBlockDiracOp: the even-odd preconditioned Id - k D where D couples the bs consecutive rows of a SITE (extension,
+// mgcr_eo_create_block in Dirac form; a clover-type operator): with B_s = I - k D_ss the operator on the even half is
+// S = B_e - k^2 D_eo B_o^-1 D_oe, D_eo / D_oe the inter-site halves.  Everything else is EvenOddDiracOp's; solve_queue and
+// MultiEvenOddDiracOp refuse an operator with blocks.  block_diag() downloads B_e and B_o^-1 as the device holds them, row-major.
+template <typename num_type>
+class EvenOddBlockDiracOp : public EvenOddDiracOp<num_type> {
+public:
+    EvenOddBlockDiracOp(Sparse<num_type> *mat, std::complex<double> k_factor, int bs, const std::vector<int8_t> *parity = nullptr) {
+        this->k = k_factor;
+        this->create(mat, parity, 3, bs);
+    }
+    void block_info(int &bs, num_type &sites_even, num_type &sites_odd) {
+        int32_t b = 0;
+        int64_t se = 0, so = 0;
+        mgcr_detail::ok(mgcr_eo_block_info(this->op, &b, &se, &so), "EvenOddBlockDiracOp::block_info");
+        bs = (int)b; sites_even = (num_type)se; sites_odd = (num_type)so;
+    }
+    void block_diag(std::vector<std::complex<double>> &B_even, std::vector<std::complex<double>> &invB_odd) {
+        int bs = 0;
+        num_type se = 0, so = 0;
+        block_info(bs, se, so);
+        B_even.resize((size_t)se * bs * bs);
+        invB_odd.resize((size_t)so * bs * bs);
+        mgcr_detail::ok(mgcr_eo_block_diag(this->op, reinterpret_cast<double *>(B_even.data()), reinterpret_cast<double *>(invB_odd.data())),
+                        "EvenOddBlockDiracOp::block_diag");
+    }
+
+protected:
+    EvenOddBlockDiracOp() {}
+};
+
+// EvenOddBlockSparse: the even-odd preconditioned form of a matrix M ITSELF whose diagonal is a dense block per site (extension,
+// mgcr_eo_create_block in matrix form): S = M_ee - M_eo M_oo^-1 M_oe on the even half; solve() solves M x_full = rhs_full.
+template <typename num_type>
+class EvenOddBlockSparse : public EvenOddBlockDiracOp<num_type> {
+public:
+    EvenOddBlockSparse(Sparse<num_type> *mat, int bs, const std::vector<int8_t> *parity = nullptr) { this->create(mat, parity, 4, bs); }
 };
 
 // MultiEvenOddDiracOp: the Schur complements Id - ks[j]^2 D_eo D_oe of ONE hopping matrix on column j of a block of ks.size() Fields

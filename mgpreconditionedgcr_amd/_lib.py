@@ -143,6 +143,9 @@ _SIGS = {
     "mgcr_eo_create": (C.c_int, [C.c_int64, _vp, _vp, _vp, _vp, _dp, C.POINTER(_vp)]),
     "mgcr_eo_create_diag": (C.c_int, [C.c_int64, _vp, _vp, _vp, _vp, _dp, C.POINTER(_vp)]),
     "mgcr_eo_diag": (C.c_int, [_vp, _vp, _vp]),
+    "mgcr_eo_create_block": (C.c_int, [C.c_int64, _vp, _vp, _vp, C.c_int32, _vp, _dp, C.POINTER(_vp)]),
+    "mgcr_eo_block_info": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mgcr_eo_block_diag": (C.c_int, [_vp, _vp, _vp]),
     "mgcr_eo_set_k": (C.c_int, [_vp, _dp]),
     "mgcr_eo_info": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mgcr_eo_parity": (C.c_int, [_vp, _vp]),

@@ -590,6 +590,60 @@ class EvenOddSparse(EvenOddDiagDiracOp):
         self._create(mat, None, parity)
 
 
+class EvenOddBlockDiracOp(EvenOddDiracOp):
+    """The even-odd preconditioned Id - k*D where D couples the bs consecutive rows of a SITE (mgcr_eo_create_block, Dirac form; a
+    clover-type operator): with B_s = I - k D_ss the operator on the even half is S = B_e - k^2 D_eo B_o^-1 D_oe, D_eo / D_oe the
+    inter-site halves.  Everything else is EvenOddDiracOp's: split / merge / prepare / reconstruct / solve / halves are inherited.
+    The scans (MultiEvenOddDiracOp, solve_queue) refuse an operator with blocks.  bs = 1 gives exactly EvenOddDiagDiracOp(mat, k)."""
+
+    _who = "EvenOddBlockDiracOp"
+
+    def __init__(self, mat, k, bs, parity=None):
+        Operator.__init__(self)
+        self._create(mat, _ri(k), bs, parity)
+
+    def _create(self, mat, k_ri, bs, parity):
+        _lib.init()
+        n = int(mat._shape[0])
+        if mat._shape[0] != mat._shape[1]:
+            raise MgcrError(1, "%s: matrix must be square" % self._who)
+        par = None if parity is None else np.ascontiguousarray(parity, np.int8)
+        if par is not None and par.size != n:
+            raise MgcrError(1, "%s: parity has %d entries, the matrix has %d rows" % (self._who, par.size, n))
+        h = C.c_void_p()
+        check(_lib.lib().mgcr_eo_create_block(n, mat.ROW.ctypes.data, mat.COL.ctypes.data, mat.VAL.ctypes.data, int(bs),
+                                              par.ctypes.data if par is not None else None, k_ri, C.byref(h)))
+        self.h = h
+        self.last_history = None
+        self.last_iterations = None
+        self.last_converged = None
+
+    def block_info(self):
+        """(bs, number of even sites, number of odd sites)"""
+        bs, se, so = C.c_int32(), C.c_int64(), C.c_int64()
+        check(_lib.lib().mgcr_eo_block_info(self.h, C.byref(bs), C.byref(se), C.byref(so)))
+        return bs.value, se.value, so.value
+
+    def block_diag(self):
+        """(B_even[sites_e, bs, bs], invB_odd[sites_o, bs, bs]): the two block factors of the Schur apply as the device holds them"""
+        bs, se, so = self.block_info()
+        B, inv = np.empty((se, bs, bs), c128), np.empty((so, bs, bs), c128)
+        check(_lib.lib().mgcr_eo_block_diag(self.h, B.ctypes.data, inv.ctypes.data))
+        return B, inv
+
+
+class EvenOddBlockSparse(EvenOddBlockDiracOp):
+    """The even-odd preconditioned form of a matrix M ITSELF whose diagonal is a dense block per site of bs consecutive rows
+    (mgcr_eo_create_block, matrix form): S = M_ee - M_eo M_oo^-1 M_oe on the even half, and solve() solves M x_full = rhs_full.
+    There is no hopping parameter: set_k raises."""
+
+    _who = "EvenOddBlockSparse"
+
+    def __init__(self, mat, bs, parity=None):
+        Operator.__init__(self)
+        self._create(mat, None, bs, parity)
+
+
 class MultiEvenOddDiracOp(Operator):
     """The Schur complements Id - ks[j]^2 D_eo D_oe of ONE hopping matrix on column j of a block of len(ks) Fields of the even
     half: an even-odd hopping-parameter scan as one operator (mgcr_eo_multi_create; no reference counterpart).  Borrows the halves

@@ -275,6 +275,8 @@ int mgcr_stat(const char *name, int64_t *value) {
     else if (!strcmp(name, "eo_queue_steps")) *value = gcr_queue_stat(5);
     else if (!strcmp(name, "evenodd_fused_steps")) *value = eo_fused_step_count();
     else if (!strcmp(name, "evenodd_diag_fused_steps")) *value = eo_diag_fused_step_count();
+    else if (!strcmp(name, "evenodd_block_applies")) *value = eo_block_apply_count();
+    else if (!strcmp(name, "evenodd_block_fused_steps")) *value = eo_block_fused_step_count();
     else { set_error("mgcr_stat: unknown counter '%s'", name); return MGCR_ERR_INVALID; }
     return MGCR_OK;
 }

@@ -28,6 +28,7 @@ void eo_destroy(EoState *e) {
         if (h) { csr_free(&h->csr); delete h; }
     hipFree(e->d_even); hipFree(e->d_odd); hipFree(e->t);
     eo_diag_destroy(e);
+    eo_block_destroy(e);
     gcr_state_destroy(e->solver);
     for (cplx *w : e->work) hipFree(w);
     delete e;
@@ -102,6 +103,7 @@ int eo_apply(Op *op, const cplx *x, cplx *y, int64_t n) {
     EoState *e = op->eo;
     MGCR_CHECK(e && n == e->ne, MGCR_ERR_INVALID, "even-odd DiracOp: the Field must have the %lld entries of the even half", (long long)(e ? e->ne : 0));
     if (e->has_diag) return eo_diag_apply(e, x, y);   // a site diagonal: evenodd_diag.hip
+    if (e->has_block) return eo_block_apply(e, x, y);   // a dense block per site: evenodd_block.hip
     MGCR_CHECK(e->k.x != 0. || e->k.y != 0., MGCR_ERR_INVALID, "No k value supplied for Dirac Operator!");
     MGCR_TRY(csr_apply(e->half[1]->csr, x, e->t, false, make_double2(0., 0.)));
     return eo_shift_apply(e, 0, e->t, y, e->k2, x);
@@ -166,6 +168,7 @@ __global__ void __launch_bounds__(RED_THREADS, ((MODE == 1 || (MODE == 3 && WT <
 bool eo_schur_fusable(const Op *op) {
     if (!op || op->kind != OP_DIRAC_EO || !op->eo || !fuse_enabled()) return false;
     if (op->eo->has_diag) return eo_diag_schur_fusable(op->eo);
+    if (op->eo->has_block) return eo_block_schur_fusable(op->eo);
     const CsrDev &A = op->eo->half[0]->csr;
     if (A.pat_mode == 1 && (int64_t)A.npat * A.W * 20 > 48 * 1024) return false;   // the pattern table must fit LDS
     if (csr_stencil_active(A) && A.sten_rare) return false;                        // (no rare-tail form: see the kernel)
@@ -178,6 +181,7 @@ int eo_schur_step(Op *op, const cplx *x, cplx *y, const cplx *const *vecs, int n
     MGCR_CHECK(nd >= 1 && nd <= FND, MGCR_ERR_INVALID, "eo_schur_step: 1..%d vectors", FND);
     MGCR_CHECK(rm.band == 0, MGCR_ERR_INVALID, "eo_schur_step: plain row map only");
     if (e->has_diag) return eo_diag_schur_step(e, x, y, vecs, nd, parts, rm);
+    if (e->has_block) return eo_block_schur_step(e, x, y, vecs, nd, parts, rm);
     MGCR_CHECK(e->k.x != 0. || e->k.y != 0., MGCR_ERR_INVALID, "No k value supplied for Dirac Operator!");
     MGCR_TRY(csr_apply(e->half[1]->csr, x, e->t, false, make_double2(0., 0.)));
     const CsrDev &A = e->half[0]->csr;
@@ -235,6 +239,7 @@ int eo_build_halves(EoState *e, const EvenOddPlan &plan, const char *who) {
 // bhat = b_e - (-k) (D_eo b_o); the halves of b stay in W_BE, W_BO
 static int eo_prepare(EoState *e, const cplx *b_full, cplx *bhat) {
     if (e->has_diag) return eo_diag_prepare(e, b_full, bhat);
+    if (e->has_block) return eo_block_prepare(e, b_full, bhat);
     cplx *be, *bo;
     MGCR_TRY(eo_work(e, EoState::W_BE, &be));
     MGCR_TRY(eo_work(e, EoState::W_BO, &bo));
@@ -244,6 +249,7 @@ static int eo_prepare(EoState *e, const cplx *b_full, cplx *bhat) {
 // x_o = b_o - (-k) (D_oe x_e), then x_full = merge(x_e, x_o)
 static int eo_reconstruct(EoState *e, const cplx *b_full, const cplx *xe, cplx *x_full) {
     if (e->has_diag) return eo_diag_reconstruct(e, b_full, xe, x_full);
+    if (e->has_block) return eo_block_reconstruct(e, b_full, xe, x_full);
     cplx *bo, *xo;
     MGCR_TRY(eo_work(e, EoState::W_BO, &bo));
     MGCR_TRY(eo_work(e, EoState::W_XO, &xo));
@@ -299,6 +305,7 @@ int mgcr_eo_set_k(mgcr_op_t eo, const double k_ri[2]) {
     MGCR_CHECK(k_ri[0] != 0. || k_ri[1] != 0., MGCR_ERR_INVALID, "mgcr_eo_set_k: No k value supplied for Dirac Operator!");
     LOCK();
     if (eo->eo->has_diag) return eo_diag_set_k(eo, make_double2(k_ri[0], k_ri[1]));
+    if (eo->eo->has_block) return eo_block_set_k(eo, make_double2(k_ri[0], k_ri[1]));
     eo->eo->k = eo->k = make_double2(k_ri[0], k_ri[1]);
     eo->eo->k2 = host_cmul(eo->k, eo->k);
     return MGCR_OK;

@@ -415,6 +415,7 @@ int mgcr_eo_diag(mgcr_op_t eo, double *a_even_ri, double *inv_a_odd_ri) {
     MGCR_CHECK(eo && eo->kind == OP_DIRAC_EO && eo->eo, MGCR_ERR_INVALID, "%s: not an even-odd preconditioned DiracOp", who);
     LOCK();
     const EoState *e = eo->eo;
+    MGCR_CHECK(!e->has_block, MGCR_ERR_INVALID, "%s: the operator carries a dense block per site (mgcr_eo_create_block): mgcr_eo_block_diag downloads the blocks", who);
     MGCR_CHECK((a_even_ri || e->ne == 0) && (inv_a_odd_ri || e->no == 0), MGCR_ERR_INVALID, "%s: null argument", who);
     if (!e->has_diag) {
         for (int64_t i = 0; i < e->ne; i++) { a_even_ri[2 * i] = 1.; a_even_ri[2 * i + 1] = 0.; }

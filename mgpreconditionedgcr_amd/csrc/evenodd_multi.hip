@@ -207,6 +207,9 @@ int mgcr_eo_multi_create(mgcr_op_t eo, int32_t nk, const double *k_ri, mgcr_op_t
     MGCR_CHECK(!eo->eo->has_diag, MGCR_ERR_UNSUPPORTED,
                "%s: the operator carries a site diagonal (mgcr_eo_create_diag): 1 - k_j d would differ from column to column, which the scans "
                "do not support; solve one k at a time with mgcr_eo_solve", who);
+    MGCR_CHECK(!eo->eo->has_block, MGCR_ERR_UNSUPPORTED,
+               "%s: the operator carries a dense block per site (mgcr_eo_create_block): dense site blocks would be per column, which the scans "
+               "do not support; solve one k at a time with mgcr_eo_solve", who);
     MGCR_CHECK(nk >= 1 && nk <= MV_MAX_K, MGCR_ERR_INVALID, "%s: nk = %d hopping parameters, 1 .. %d are supported", who, (int)nk, MV_MAX_K);
     KCols ks, ks2;
     MGCR_TRY(eom_values(k_ri, nk, &ks, &ks2, who));

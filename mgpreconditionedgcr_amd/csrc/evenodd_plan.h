@@ -13,6 +13,7 @@
 //   * D_eo (n_e x n_o) holds the even rows, D_oe (n_o x n_e) the odd ones, both CSR: rows in list order, columns renumbered by
 //     index[], a row's entries IN STORED ORDER — the half applies then sum a row in the order the full apply does.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -176,6 +177,100 @@ inline bool evenodd_plan_build_diag(int64_t n, const int64_t *rowptr, const int6
     }
     if (n_diag) *n_diag = nd;
     return evenodd_plan_build(n, rp.data(), cc.data(), vv.data(), parity_in, out, err);
+}
+
+// The plan of a matrix with a dense block per SITE on its diagonal (evenodd_block.hip): sites are runs of bs consecutive rows, row r
+// belongs to site r / bs.  The stored entries inside a site are taken out and added up, in stored order, into that site's bs x bs
+// block (row-major, interleaved (re, im); 0 where nothing is stored) — *n_in_site counts them —, and what is left, the entries
+// between different sites, is coloured and split as above.  The rows of a site share one colour: without a caller parity the SITE
+// graph is two-coloured by evenodd_colour (components in order of their smallest site, the root even) and the colour expanded to
+// the rows; a caller parity must be constant inside every site (the first row that differs from its site's first row is named).
+// evenodd_plan_build then checks the row parity against the inter-site entries — an odd cycle of sites or a wrong caller bit is
+// refused with the entry named — and makes the halves.  The lists stay ascending, so half-site s' occupies the half rows
+// s' bs .. s' bs + bs - 1, and blocks_even / blocks_odd hold the blocks of the even / odd sites in that order.
+constexpr int32_t EO_BLOCK_MAX = 16;
+inline bool evenodd_plan_build_block(int64_t n, const int64_t *rowptr, const int64_t *col, const double *val_ri, int32_t bs,
+                                     const int8_t *parity_in, EvenOddPlan *out, std::vector<double> *blocks_even,
+                                     std::vector<double> *blocks_odd, int64_t *n_in_site, std::string *err) {
+    char msg[256];
+    auto fail = [&](const char *m) { if (err) *err = m; return false; };
+    if (n < 0 || !rowptr || !out || !blocks_even || !blocks_odd) return fail("even-odd plan: bad argument");
+    if (bs < 1 || bs > EO_BLOCK_MAX) {
+        snprintf(msg, sizeof msg, "even-odd plan: block size bs = %d, 1 .. %d are supported", (int)bs, (int)EO_BLOCK_MAX);
+        return fail(msg);
+    }
+    if (n % bs != 0) {
+        snprintf(msg, sizeof msg, "even-odd plan: n = %lld rows are no whole number of sites of bs = %d rows", (long long)n, (int)bs);
+        return fail(msg);
+    }
+    if (rowptr[0] != 0) return fail("even-odd plan: rowptr[0] must be 0");
+    for (int64_t r = 0; r < n; r++)
+        if (rowptr[r + 1] < rowptr[r]) {
+            snprintf(msg, sizeof msg, "even-odd plan: rowptr is not non-decreasing at row %lld", (long long)r);
+            return fail(msg);
+        }
+    const int64_t nnz = rowptr[n];
+    if (nnz > 0 && (!col || !val_ri)) return fail("even-odd plan: null column or value array");
+    for (int64_t e = 0; e < nnz; e++)
+        if (col[e] < 0 || col[e] >= n) {
+            snprintf(msg, sizeof msg, "even-odd plan: column index %lld is outside [0, %lld)", (long long)col[e], (long long)n);
+            return fail(msg);
+        }
+    const int64_t ns = n / bs;
+    const size_t bb = 2 * (size_t)bs * (size_t)bs;
+    std::vector<double> blocks(bb * (size_t)ns, 0.);
+    std::vector<int64_t> rp((size_t)n + 1, 0), cc, sp((size_t)ns + 1, 0), sc;
+    std::vector<double> vv;
+    cc.reserve((size_t)nnz);
+    sc.reserve((size_t)nnz);
+    vv.reserve(2 * (size_t)nnz);
+    int64_t nin = 0;
+    for (int64_t r = 0; r < n; r++) {
+        const int64_t s = r / bs;
+        for (int64_t e = rowptr[r]; e < rowptr[r + 1]; e++) {
+            if (col[e] / bs == s) {
+                const size_t at = bb * (size_t)s + 2 * ((size_t)(r - s * bs) * (size_t)bs + (size_t)(col[e] - s * bs));
+                blocks[at] += val_ri[2 * e];
+                blocks[at + 1] += val_ri[2 * e + 1];
+                nin++;
+            } else {
+                cc.push_back(col[e]);
+                sc.push_back(col[e] / bs);
+                vv.push_back(val_ri[2 * e]);
+                vv.push_back(val_ri[2 * e + 1]);
+            }
+        }
+        rp[(size_t)r + 1] = (int64_t)cc.size();
+        sp[(size_t)s + 1] = (int64_t)sc.size();
+    }
+    if (n_in_site) *n_in_site = nin;
+    std::vector<int8_t> par((size_t)n, 0);
+    if (parity_in) {
+        for (int64_t r = 0; r < n; r++) {
+            if (parity_in[r] != 0 && parity_in[r] != 1) {
+                snprintf(msg, sizeof msg, "even-odd plan: parity[%lld] = %d is neither 0 (even) nor 1 (odd)", (long long)r, (int)parity_in[r]);
+                return fail(msg);
+            }
+            if (parity_in[r] != parity_in[r / bs * bs]) {
+                snprintf(msg, sizeof msg, "even-odd plan: parity[%lld] differs from parity[%lld] inside site %lld: the rows of a site share one colour",
+                         (long long)r, (long long)(r / bs * bs), (long long)(r / bs));
+                return fail(msg);
+            }
+            par[(size_t)r] = parity_in[r];
+        }
+    } else {
+        std::vector<int8_t> site_par;
+        evenodd_colour(ns, sp.data(), sc.data(), site_par);
+        for (int64_t r = 0; r < n; r++) par[(size_t)r] = site_par[(size_t)(r / bs)];
+    }
+    if (!evenodd_plan_build(n, rp.data(), cc.data(), vv.data(), par.data(), out, err)) return false;
+    blocks_even->clear();
+    blocks_odd->clear();
+    for (int64_t s = 0; s < ns; s++) {
+        std::vector<double> &dst = par[(size_t)(s * bs)] ? *blocks_odd : *blocks_even;
+        dst.insert(dst.end(), blocks.begin() + (ptrdiff_t)(bb * (size_t)s), blocks.begin() + (ptrdiff_t)(bb * (size_t)(s + 1)));
+    }
+    return true;
 }
 
 }  // namespace mgcr

@@ -195,6 +195,9 @@ int mgcr_eo_solve_queue(mgcr_op_t eo, const mgcr_gcr_param *param, int32_t width
     MGCR_CHECK(!eo->eo->has_diag, MGCR_ERR_UNSUPPORTED,
                "%s: the operator carries a site diagonal (mgcr_eo_create_diag): 1 - k_s d would differ from column to column, which the scans "
                "do not support; solve one k at a time with mgcr_eo_solve", who);
+    MGCR_CHECK(!eo->eo->has_block, MGCR_ERR_UNSUPPORTED,
+               "%s: the operator carries a dense block per site (mgcr_eo_create_block): dense site blocks would be per column, which the scans "
+               "do not support; solve one k at a time with mgcr_eo_solve", who);
     MGCR_CHECK(width >= 1 && width <= MV_MAX_K, MGCR_ERR_INVALID, "%s: width = %d slots, 1 .. %d are supported", who, (int)width, MV_MAX_K);
     MGCR_CHECK(nsys >= 1, MGCR_ERR_INVALID, "%s: nsys = %d systems", who, (int)nsys);
     // (the restrictions of mgcr_eo_multi_solve, checked before anything is enqueued)

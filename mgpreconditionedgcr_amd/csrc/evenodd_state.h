@@ -30,6 +30,17 @@ struct EoState {
     cplx *dd_even = nullptr, *dd_odd = nullptr;        // ... and on the device
     cplx *a_even = nullptr, *inv_a_odd = nullptr;      // [n_e] a, [n_o] 1 / a: written in stream order by diag_coeff_kernel
     cplx c = {0., 0.}, c2 = {0., 0.}, cn = {0., 0.};   // c, c c and -c, formed once on the host
+    // The site blocks (evenodd_block.hip, mgcr_eo_create_block): A = B - c H, B one dense bs x bs block per site of bs consecutive rows,
+    // H the entries between different sites.  Dirac form: B_s = I - k D_ss, c = k; matrix form: B_s = D_ss, c = -1 (matrix_form, c, c2
+    // and cn above are shared with the site diagonal; has_diag stays false).  has_block false: everything below is unused.
+    bool has_block = false;
+    int32_t bs = 0;
+    int64_t sites_e = 0, sites_o = 0;
+    cplx *dblk_even = nullptr, *dblk_odd = nullptr;    // [sites][bs][bs] D_ss as stored, in list order
+    cplx *B_even = nullptr, *invB_odd = nullptr;       // B of the even sites, B^-1 of the odd ones: what the applies read (block column
+                                                       // outermost: entry (r, c) of half-site s at [c * n_half + s * bs + r])
+    cplx *invB_spare = nullptr;                        // where blk_invert_kernel works: swapped with invB_odd once the host has seen it succeed
+    unsigned long long *blk_status = nullptr;          // the status word of blk_invert_kernel (one per operator)
 };
 
 // k k as mgcr_eo_set_k forms it: on the host, un-fused
@@ -50,5 +61,14 @@ bool eo_diag_schur_fusable(const EoState *e);
 int eo_diag_schur_step(EoState *e, const cplx *x, cplx *y, const cplx *const *vecs, int nd, double *parts, const RowMap &rm);
 int eo_diag_prepare(EoState *e, const cplx *b_full, cplx *bhat);
 int eo_diag_reconstruct(EoState *e, const cplx *b_full, const cplx *xe, cplx *x_full);
+
+// ---- evenodd_block.hip: ... and on an operator with a dense block per site (EoState::has_block) ---------------------------------
+void eo_block_destroy(EoState *e);
+int eo_block_set_k(Op *op, cplx k);
+int eo_block_apply(EoState *e, const cplx *x, cplx *y);
+bool eo_block_schur_fusable(const EoState *e);
+int eo_block_schur_step(EoState *e, const cplx *x, cplx *y, const cplx *const *vecs, int nd, double *parts, const RowMap &rm);
+int eo_block_prepare(EoState *e, const cplx *b_full, cplx *bhat);
+int eo_block_reconstruct(EoState *e, const cplx *b_full, const cplx *xe, cplx *x_full);
 
 }  // namespace mgcr

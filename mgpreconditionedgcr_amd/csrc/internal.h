@@ -420,6 +420,8 @@ void eo_destroy(EoState *e);
 int64_t eo_nnz(const EoState *e);
 int64_t eo_fused_step_count();   // GCR steps whose stage 2 took the beta dot products (schur_step_apply_kernel)
 int64_t eo_diag_fused_step_count();   // ... on an operator with a site diagonal (evenodd_diag.hip diag_stage2_kernel)
+int64_t eo_block_apply_count();        // Schur applies of an operator with a dense block per site (evenodd_block.hip), inside GCR steps or not
+int64_t eo_block_fused_step_count();   // ... GCR steps of them whose blk_combine_kernel took the beta dot products
 int eo_apply(Op *op, const cplx *x, cplx *y, int64_t n);   // y = S x = x - k^2 D_eo (D_oe x), two launches
 // stage 2 of a GCR step fused with the step's beta dot products (schur_step_apply_kernel): exists for a D_eo stored one thread per row
 bool eo_schur_fusable(const Op *op);
