@@ -23,10 +23,13 @@
 // The body is a text included into the two kernel templates, not a __device__ function template: called through a forceinline
 // function (by value or by reference, its LDS declared inside or handed in) step_keep_kernel<3, true, false, false> needs 8 B of
 // scratch per lane and step_keep_kernel<2, true, true, false> 64 instead of 61 VGPRs; included, the old name's code is what it was.
-// Neither reads from memory what it holds: step_keep_kernel's build takes its first Ap_0 rows from the registers of the pass-1
-// dots (sb_keep_rows), and the closing step_build_kernel at 4 and 5 directions loads a row's r once for the close pass and the
+// Neither reads from memory what it holds: the keep body's build takes its first Ap_0 rows from the registers of the pass-1
+// dots (sb_kept_rows: per form as many as fit, step_keep_wide_kernel included), and the closing step_build_kernel at 4 and 5 directions loads a row's r once for the close pass and the
 // build, which are one loop there, the thread's last close row behind the exchange-2 publish (sb_close_merged;
 // tests/test_gpu_stepbuild_reuse.py: the same bits, tests/test_stepbuild_reuse_regs.py: the same registers class).
+// The keep body's scalar stage behind exchange 1 reads nothing from memory either: its operands are fetched behind the apply and
+// parked in LDS, the |r|^2 fold and the stop decision are made ahead of the poll (tests/test_gpu_stepbuild_scalar_stage.py,
+// tests/test_stepbuild_scalar_stage_regs.py).
 // The keep forms for real coefficients do not load a row's own r either: it IS the diagonal slot's gather (sb_apply_form; a trip of
 // their apply is 7 loads and one round trip where it was 8 and two; 34.8 against 36.7 us at 1 direction, +1.5 % on the headline).
 // Taking r[i - 1] and r[i + 1] from the neighbouring lanes on top of that (6 loads per trip) gives the same bits and was measured
@@ -53,14 +56,40 @@ namespace mgcr {
 constexpr int SB_MAX_TRIPS = 4;     // rows per thread whose Ar stays in LDS (4 x 1024 x 16 B = 64 KB per workgroup)
 constexpr int SB_MAX_ND = 5;
 constexpr int SB_KEEP_TB = 2;      // step_keep_kernel: trips whose streams are in registers at a time
-// step_keep_kernel: rows of Ap_0 that stay in registers from the pass-1 dots to the build (4 at 1 direction, 3 or 4 at 2 spill)
-template <int NDT> constexpr int sb_keep_rows() { return NDT == 1 ? 3 : 2; }
+// The keep body: rows of Ap_0 (the thread's first trips) that stay in registers from the pass-1 dots to the build.  Per form, the
+// most with which it compiles to 0 scratch and 8 waves per SIMD, the scalar stage's early loads in place (one row more needs 8 to
+// 48 B per lane everywhere; tests/test_stepbuild_scalar_stage_regs.py pins the table and the resources).  At 1 direction with
+// the next residual update, 3: tests/test_stepbuild_apply_lanes_regs.py pins that form's loads; 4 has not been tried in the others.
+// The forms for complex coefficients keep what they had (2, none in step_keep_wide_kernel): three of them need scratch for one more.
+// -DMGCR_SB_KEEP_MORE=0 builds those counts for every form, for a measurement.
+#ifndef MGCR_SB_KEEP_MORE
+#define MGCR_SB_KEEP_MORE 1
+#endif
+template <bool WIDE, int NDT, bool XR, bool CLOSE, bool REALC> constexpr int sb_kept_rows() {
+    if (NDT == 1) return 3;
+    if (!REALC || !MGCR_SB_KEEP_MORE) return WIDE ? 0 : 2;
+    if (!WIDE) return !XR && CLOSE ? 4 : 3;   // 2 and 3 directions
+    if (NDT == 4) return CLOSE ? 4 : 1;
+    return XR ? 2 : 3;                        // the close at 5
+}
+// The rows of Ap_0 that are NOT kept are the last stream pass 1 loads and the first the build loads (<= 1 MB per XCD and row):
+// loaded temporally in pass 1, the build's re-read can hit the XCD's L2.  Built in the three forms of the headline whose own
+// trace showed it faster; at 2 and 3 directions the mixed loads cost 20-24 B of scratch and time, the other
+// forms were not measured.  -DMGCR_SB_TEMPORAL_TAIL=1 / 0 builds it in every form / in none, for a measurement.
+#ifndef MGCR_SB_TEMPORAL_TAIL
+#define MGCR_SB_TEMPORAL_TAIL -1
+#endif
+template <bool WIDE, int NDT, bool XR, bool CLOSE, bool REALC> constexpr bool sb_temporal_tail() {
+    if (MGCR_SB_TEMPORAL_TAIL >= 0) return MGCR_SB_TEMPORAL_TAIL != 0;
+    return REALC && XR && (WIDE ? (NDT == 4 && !CLOSE) || (NDT == 5 && CLOSE) : NDT == 1 && !CLOSE);
+}
 // The compile-time policy of the keep body (gcr_stepbuild_keep_body.h): trips per batch of the build and the close pass, rows of Ap_0 kept across exchange 1, and
 // whether the trips' byte offsets are formed on the fly (trip 0's + t x the row step) instead of held, one register per trip
-// ... and how the apply gets the thread's own r and its two neighbours in the row (sb_apply_form)
-template <int TB_, int KT_, bool OTF_, int APPLY_> struct SbKeepPolicy {
+// ... how the apply gets the thread's own r and its two neighbours in the row (sb_apply_form), and whether pass 1 loads the rows
+// of Ap_0 it does not keep temporally (sb_temporal_tail)
+template <int TB_, int KT_, bool OTF_, int APPLY_, bool TAIL_> struct SbKeepPolicy {
     static constexpr int TB = TB_, KT = KT_;
-    static constexpr bool OTF = OTF_;
+    static constexpr bool OTF = OTF_, TAIL = TAIL_;   // TAIL: sb_temporal_tail
     static constexpr bool OWN = APPLY_ >= 1, LANES = APPLY_ >= 2;
 };
 // The apply of a keep form: 0 the seven gathers and a load of the row's own r behind them; 1 the own r IS the diagonal slot's
@@ -361,20 +390,58 @@ __device__ __forceinline__ double sb_block_owner_from_lds(double *lds) {
     return t;
 }
 
+// The keep body's scalar stage in two halves (gcr_stepbuild_keep_body.h: its operands are fetched behind the apply).
+// Slot i of the staged operands: den[i] | lc->cx[i - nd] | entry j of column m of the coefficient table, i - 2 nd = m nd + j — the
+// operand lean_close_coef multiplies beta_j by for cp_m (j > m; the other entries of the square are loaded and never used:
+// they lie inside the table).
+template <int NDT>
+__device__ __forceinline__ const cplx *sb_stage_src(const cplx *den, const LeanCoef *lc, int i) {
+    if (i < NDT) return den + i;
+    if (i < 2 * NDT) return lc->cx + (i - NDT);
+    const int m = (i - 2 * NDT) / NDT, j = (i - 2 * NDT) % NDT;
+    return m == 0 ? lc->t + j : lc->T + j * LND + m;
+}
+// lean_close_coef (gcr_dev.h) on such a column: the same operands in the same order
+template <int NDT>
+__device__ __forceinline__ cplx sb_stage_close_coef(const cplx *col, const cplx *sbeta, int m) {
+    cplx c = make_double2(0., 0.);
+    for (int j = m; j < NDT; j++) c = cadd(c, cmul(sbeta[j], j == m ? make_double2(1., 0.) : col[j]));
+    return c;
+}
+// fold_partials<1> (reduce.h) in two halves.  First: v = the thread's partial (0. beyond nblk), every wave's tree, lane 0 stores
+// its wave's sum; nblk == 1 (a value that is already folded): thread 0 holds parts[0] + 0. and parks it.  Behind a barrier, any
+// thread: the waves' sums added in wave order from 0. — block_sum_bcast's total, which it then hands to every thread.
+__device__ __forceinline__ void sb_stage_rr_waves(double v, int nblk, double *lds_rr) {
+    if (nblk == 1) {
+        if (threadIdx.x == 0) lds_rr[16] = v;
+        return;
+    }
+    double w[1] = {v}, s;
+    wave_multi_sum<1>(w, s);
+    if ((threadIdx.x & 63) == 0) lds_rr[threadIdx.x >> 6] = s;
+}
+__device__ __forceinline__ double sb_stage_rr(int nblk, const double *lds_rr) {
+    if (nblk == 1) return lds_rr[16];
+    const int nwave = (blockDim.x + 63) >> 6;
+    double t = 0.;
+    for (int w = 0; w < nwave; w++) t += lds_rr[w];
+    return t;
+}
+
 // KEEP-ALL (the body is gcr_stepbuild_keep_body.h): step_build_kernel's step (in-cycle / closing, with / without XR) with r read
 // ONCE per launch: the thread's residual rows ARE the apply's diagonal gathers (sb_apply_form; the forms for complex coefficients
 // load them again behind the gathers: the same lines, a cache hit) and stay in registers (SB_MAX_TRIPS x
 // 16 B) for the shift epilogue, the build's <r,Ap'>, the close pass's P0' and XR; no later pass loads a.x.
 // Register use: the pass-1 dots walk one direction (all trips) at a time, the last direction first, and hand its two sums to the
 // wave trees as soon as they are final (sb_wave_pair_to_lds: the bits of block_sum_owner<2 NDT>, whatever the order of the
-// directions); the first sb_keep_rows rows of Ap_0, which the dots load last, stay in registers across exchange 1 for the build
+// directions); the first sb_kept_rows rows of Ap_0, which the dots load last, stay in registers across exchange 1 for the build
 // (no stream is requested ahead of that exchange's polls any more); the build and the close pass walk SB_KEEP_TB trips at a
 // time, one direction after the other; every stream is addressed as scalar base + one 32-bit offset per trip.  Every element sees
 // the same operations in the same order as in step_build_kernel (ac -= beta_j Ap_j in j order, each per-thread accumulator adds
 // the rows in trip order): the same bits.  Only the forms that fit 64 VGPRs without scratch are launched (sb_keep_fits).
 // With 4 and 5 directions that policy spills (48 B at 4); step_keep_wide_kernel's does not: the build and the close pass walk ONE
-// trip at a time, no row of Ap_0 is kept across exchange 1 (the build loads all of them: a pass-1 line it re-reads directly behind
-// pass 1), and at 5 with XR only trip 0's offset is held, the others formed as off[0] + t x (row step in bytes, a scalar register)
+// trip at a time, 1 to 4 rows of Ap_0 are kept across exchange 1 (sb_kept_rows; the build loads the others: a pass-1 line it
+// re-reads directly behind pass 1, from the XCD's L2 where sb_temporal_tail says so), and at 5 with XR only trip 0's offset is held, the others formed as off[0] + t x (row step in bytes, a scalar register)
 // where they are used — written as that one sum: added to the scalar base first, the form costs 20 B.  The policies are
 // `if constexpr` on POL only: forming the offsets on the fly in step_keep_kernel<3, true, false, *> costs it 20 B.
 // CLOSE runs build | publish exchange 2 | close pass | poll 2 | XR: the build's Ap_j re-reads follow pass 1 closely, and the close
@@ -383,13 +450,15 @@ __device__ __forceinline__ double sb_block_owner_from_lds(double *lds) {
 // which workgroup 0 updates behind poll 2, is read before this workgroup publishes.
 template <int NDT, bool XR, bool CLOSE, bool REALC>
 __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_kernel(StepBuildArgs a) {
-    using POL = SbKeepPolicy<SB_KEEP_TB, sb_keep_rows<NDT>(), false, sb_apply_form<false, NDT, XR, CLOSE, REALC>()>;
+    using POL = SbKeepPolicy<SB_KEEP_TB, sb_kept_rows<false, NDT, XR, CLOSE, REALC>(), false, sb_apply_form<false, NDT, XR, CLOSE, REALC>(),
+                             sb_temporal_tail<false, NDT, XR, CLOSE, REALC>()>;
 #include "gcr_stepbuild_keep_body.h"
 }
-// 4 stored directions with XR, 5 at the close (sb_keep_wide_fits): one trip at a time, no kept row, at 5 with XR the offsets on the fly
+// 4 stored directions with XR, 5 at the close (sb_keep_wide_fits): one trip at a time, at 5 with XR the offsets on the fly
 template <int NDT, bool XR, bool CLOSE, bool REALC>
 __global__ void __launch_bounds__(RED_THREADS, 8) step_keep_wide_kernel(StepBuildArgs a) {
-    using POL = SbKeepPolicy<1, 0, NDT == 5 && XR, sb_apply_form<true, NDT, XR, CLOSE, REALC>()>;
+    using POL = SbKeepPolicy<1, sb_kept_rows<true, NDT, XR, CLOSE, REALC>(), NDT == 5 && XR, sb_apply_form<true, NDT, XR, CLOSE, REALC>(),
+                             sb_temporal_tail<true, NDT, XR, CLOSE, REALC>()>;
 #include "gcr_stepbuild_keep_body.h"
 }
 
@@ -520,7 +589,7 @@ template <int NDT, bool XR, bool CLOSE, bool R> const void *sb_keep(int *form) {
     if constexpr (sb_keep_fits<NDT, XR, CLOSE>()) return (const void *)step_keep_kernel<NDT, XR, CLOSE, R>;
     else return nullptr;
 }
-// ... and step_keep_wide_kernel — the same body one trip at a time, no kept row — where it has 0 scratch and 8 waves per SIMD
+// ... and step_keep_wide_kernel — the same body one trip at a time — where it has 0 scratch and 8 waves per SIMD
 // (tests/test_stepbuild_keep_wide_regs.py) AND was measured faster than the step_build_kernel form it replaces: 4 stored directions
 // with XR, inside a cycle and closing one (restart 4), and the close at 5 with and without XR.  At 4 directions without XR the
 // in-cycle form was measured no faster (62.1 against 61.7 us at 128^3) and the closing one not at all: step_build_kernel, as for

@@ -1,12 +1,20 @@
 // The body of gcr_stepbuild.hip's step_keep_kernel and step_keep_wide_kernel (see there): included INSIDE each of the two kernel
 // templates, behind `using POL = SbKeepPolicy<...>`, with the template parameters NDT, XR, CLOSE, REALC and the argument `a` in scope.
 // One text, two kernel names; not a header to include anywhere else.
+// apply (Ar to LDS, r kept) | the scalar stage's operands requested and parked in LDS | pass-1 dots, the first KT rows of Ap_0
+// kept | publish exchange 1, |r|^2 fold and stop decision | poll 1 | the stage's arithmetic and writes | build | CLOSE: close pass
+// | XR: poll 2, residual update.
     constexpr int TB = POL::TB, KT = POL::KT;
+    constexpr int SB_STAGE_N = CLOSE ? 2 * NDT + NDT * NDT : NDT;
     constexpr bool OTF = POL::OTF;
     __shared__ double lds[(2 * NDT > 4 ? 2 * NDT : 4) * 17];
     __shared__ double lds_pw[2 * SB_MAX_ND * 17], lds_ws[2 * SB_MAX_ND * RES_GRP];
     __shared__ int gave_up;
-    __shared__ cplx sbeta[NDT], scp[NDT], scx[NDT];
+    __shared__ cplx sbeta[NDT], scp[NDT];
+    // the scalar stage's operands, fetched behind the apply (below): the |r|^2 partials' wave sums (+ the value that needs no
+    // fold), and den[0..NDT) | CLOSE: lc->cx[0..NDT) | CLOSE: column m of the coefficient table, the entries lean_close_coef reads
+    __shared__ double lds_rr[17];
+    __shared__ cplx sstg[SB_STAGE_N];
     extern __shared__ __attribute__((aligned(16))) unsigned char sb_smem[];   // Ar of this workgroup's rows: [trip][thread]
     if (a.st->stop_at < a.st->base + a.it) return;
     const int lb = logical_workgroup(a.rm, (int)blockIdx.x, (int)gridDim.x);
@@ -64,15 +72,40 @@
     // ---- <Ar, Ap_j>, one direction (all trips) at a time: its two sums go through the wave trees as soon as they are final ----
     // The directions are walked LAST TO FIRST (every direction's pair of sums has its own LDS slots, so their order enters no
     // sum): Ap_0 comes last and its first KT rows stay in registers for the build, which starts with Ap_0 — those rows are not
-    // read again (the streams are non-temporal and a vector is an XCD's whole L2: a re-read is a trip to memory).
+    // read again (the streams are non-temporal and a vector is an XCD's whole L2: a re-read is a trip to memory).  POL::TAIL: the
+    // rows of Ap_0 that are not kept (<= 1 MB per XCD each) are loaded temporally, for the build's re-read to hit that L2.
     cplx pre[KT > 0 ? KT : 1];
+    // The scalar stage behind exchange 1 needs, besides the exchanged sums, only values that were in memory when the launch began:
+    // the |r|^2 partials and den[] (written behind poll 2 of the launch before, or by the kernels before), bnorm2 and tol2 (the
+    // solve's start), and at the close lc->cx, lc->t and lc->T (poll 2 of the launch before, lean_table_row of earlier launches).
+    // Loaded behind that exchange they are three dependent round trips to memory at the one moment when the whole grid has no
+    // load in flight.  Here they are requested behind the apply, in one round trip while the workgroup's other waves still
+    // stream, and parked in LDS — the |r|^2 partials as fold_partials' wave sums — so that behind the poll only LDS reads, the
+    // divisions and the coefficient arithmetic are left.  (Held in registers over pass 1's first direction and parked behind it,
+    // or requested ahead of the apply, the close at 5 directions and two forms for complex coefficients need scratch.)
+    // Reads only: every write of the stage stays behind the poll (other workgroups may still be in their prologue), and lc->cx
+    // and den[], which workgroup 0 rewrites behind poll 2, are read before this workgroup publishes exchange 2, as before.  No
+    // vector register lives across a poll for it.  The last wave fetches den / cx / the table: the first waves hold the
+    // exchange's hop-1 tasks.
+    const bool folds = XR || lb == 0;
+    double stg_r = 0.;
+    cplx stg_c = make_double2(0., 0.);
+    const int stg_i = tid - (RED_THREADS - 64);
+    if (folds) stg_r = a.nblkR == 1 ? (tid == 0 ? a.partsR[0] + 0. : 0.) : (tid < a.nblkR ? a.partsR[tid] : 0.);
+    if (stg_i >= 0 && stg_i < SB_STAGE_N) stg_c = *sb_stage_src<NDT>(a.den, a.lc, stg_i);
+    if (folds) sb_stage_rr_waves(stg_r, a.nblkR, lds_rr);
+    if (stg_i >= 0 && stg_i < SB_STAGE_N) sstg[stg_i] = stg_c;
+    __builtin_amdgcn_sched_barrier(0);
     {
 #pragma unroll
         for (int jj = 0; jj < NDT; jj++) {
             const int j = NDT - 1 - jj;
             cplx b[SB_MAX_TRIPS];
 #pragma unroll
-            for (int t = 0; t < SB_MAX_TRIPS; t++) b[t] = row(t) < end ? ld_stream<true>(at(a.aps[j], t)) : make_double2(0., 0.);
+            for (int t = 0; t < SB_MAX_TRIPS; t++) {
+                if (POL::TAIL && j == 0 && t >= KT) b[t] = row(t) < end ? ld_stream<false>(at(a.aps[j], t)) : make_double2(0., 0.);
+                else b[t] = row(t) < end ? ld_stream<true>(at(a.aps[j], t)) : make_double2(0., 0.);
+            }
             double v[2] = {0., 0.};
 #pragma unroll
             for (int t = 0; t < SB_MAX_TRIPS; t++) {
@@ -97,6 +130,9 @@
             __builtin_amdgcn_raw_buffer_store_b128(w4, sy.slots, ((1 * RES_NV + tid) * RES_BLK + lb) * 16, 0, RES_SC1);
         }
     }
+    // the stop decision, ahead of the poll as well (the barrier above has made lds_rr visible); in a scalar register from here on
+    bool ends_here = false;
+    if (folds) ends_here = __builtin_amdgcn_readfirstlane(!((sb_stage_rr(a.nblkR, lds_rr) / a.st->bnorm2) > a.st->tol2)) != 0;
     if (!res_collect<2 * NDT>(sy, 1)) {
         res_abort(a.abort_dev, a.abort_host);
         for (int64_t i = i0; i < end; i += stride) a.ap_out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
@@ -104,23 +140,15 @@
         return;
     }
     // ---- direction build (as in step_build_kernel) ----
-    bool ends_here = false;
-    if (XR || lb == 0) {
-        double rr[1];
-        fold_partials<1>(a.partsR, a.nblkR, a.strideR, rr, lds);
-        if (lb == 0 && threadIdx.x == 0) {
-            close_step(a.st, a.it, rr[0], a.hist, a.hist_cap, CLOSE);
-            if (CLOSE) a.st->closed = 1;
-        }
-        ends_here = __builtin_amdgcn_readfirstlane(!((rr[0] / a.st->bnorm2) > a.st->tol2)) != 0;   // (decided here: not sunk to XR)
+    // (the scalar stage's operands are in LDS, its |r|^2 fold and stop decision made: see pass 1; the writes are here)
+    if (lb == 0 && tid == 0) {
+        close_step(a.st, a.it, sb_stage_rr(a.nblkR, lds_rr), a.hist, a.hist_cap, CLOSE);
+        if (CLOSE) a.st->closed = 1;
     }
-    if (tid < NDT) sbeta[tid] = cdiv(make_double2(res_total(sy, 2 * tid), res_total(sy, 2 * tid + 1)), a.den[tid]);
+    if (tid < NDT) sbeta[tid] = cdiv(make_double2(res_total(sy, 2 * tid), res_total(sy, 2 * tid + 1)), sstg[tid]);
     __syncthreads();
     if constexpr (CLOSE) {
-        if (tid < NDT) {
-            scp[tid] = lean_close_coef(a.lc, sbeta, NDT, tid);
-            scx[tid] = a.lc->cx[tid];
-        }
+        if (tid < NDT) scp[tid] = sb_stage_close_coef<NDT>(sstg + 2 * NDT + tid * NDT, sbeta, tid);
         __syncthreads();
     }
     if (!CLOSE && lb == 0 && tid <= NDT) lean_table_row<NDT>(a.lc, sbeta, tid);
@@ -173,7 +201,7 @@
         cplx cx[NDT], cp[NDT];
 #pragma unroll
         for (int j = 0; j < NDT; j++) {
-            cx[j] = to_sgpr(scx[j]);
+            cx[j] = to_sgpr(sstg[NDT + j]);
             cp[j] = to_sgpr(scp[j]);
         }
 #pragma unroll
