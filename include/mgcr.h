@@ -383,7 +383,9 @@ int mgcr_set_option(const char *name, int value, int *previous);
  * products (mgcr_eo_create, Rule 2),
  * "evenodd_diag_fused_steps" = the same on an operator that carries a site diagonal (mgcr_eo_create_diag, Rule 2d),
  * "evenodd_block_applies" = Schur applies of an operator with a dense block per site (mgcr_eo_create_block), inside GCR steps or
- * not, "evenodd_block_fused_steps" = its GCR steps whose last apply launch took the step's beta dot products (Rule 3b). */
+ * not, "evenodd_block_fused_steps" = its GCR steps whose last apply launch took the step's beta dot products (Rule 3b),
+ * "gcr32_applies" = applies of a low-precision GCR (mgcr_gcr32_create) that ran on the device, "gcr32_steps" = the inner steps those
+ * enqueued (both kept on the device: one synchronisation per query). */
 int mgcr_stat(const char *name, int64_t *value);
 
 /* Self-test of the hardware behaviour the one-launch solver paths (csrc/gcr_resident.hip, gcr_stepbuild.hip) build on: inside
@@ -514,6 +516,57 @@ int mgcr_gcr_set_param(mgcr_op_t gcr, const mgcr_gcr_param *param);
 int mgcr_gcr_solve_op(mgcr_op_t gcr, mgcr_vec_t rhs, mgcr_vec_t x, double *hist, int32_t hist_cap,
                       int32_t *n_iter, int32_t *converged);
 int mgcr_gcr_set_x0(mgcr_op_t gcr, mgcr_vec_t x0);
+
+/* LowPrecisionGCR: mixed precision (new — every other object of the library is complex fp64).  The operator owns an fp32 copy of a
+ * matrix; applied to an fp64 Field f (mgcr_op_apply) it returns y ~ A^-1 f from a restarted GCR that runs entirely in fp32 on the
+ * device, from x0 = 0, with no host round trip (csrc/gcr32.hip).  Its place is the right_precond slot of an fp64 solve with
+ * flexible = 1: the cheap inexact inner solve does most of the work, the fp64 outer GCR keeps the true residual.
+ * The host CSR (int64 indices) is copied like mgcr_eo_create's.  k_ri != NULL: Dirac form, A = 1 - k D; k_ri == NULL: matrix form,
+ * A = the matrix.  `inner` reads restart (1 .. 16 slots), max_iter (>= 1: the steps enqueued per apply, 3 launches each, plus an
+ * entry and an exit launch) and tol (relative: the solve stops when |r|^2 <= tol^2 |f|^2; a tol below fp32's reach is accepted
+ * and simply runs max_iter steps).
+ * Arithmetic.  fp32 complex is float2.  A value is (float)re, (float)im, round to nearest; k32 = (float)k.  Products are
+ * (ar br - ai bi, ar bi + ai br) in float, nothing is fused.  Row sum: the first W entries of a row (the ELL part, W from
+ * mgcr_gcr32_info, the plain Sparse slab's pick) are added in stored order into an accumulator that starts at +0; a row's remaining
+ * entries (the tail) are added in stored order into a second accumulator, which is then added to the first.  When every stored
+ * imaginary part is zero the slab is real (4 B per value) and a product is (a br, a bi).  Dirac form: y = x - k32 s.  Dot products
+ * and norms: every fp32 operand is converted to double, products and sums are fp64, per-workgroup partial slabs folded by the
+ * consumer in a fixed order (csrc/reduce.h) — no atomics, an apply is bit-reproducible run to run.  Scalars: alpha and the beta_j are
+ * formed in fp64 from the fp64 sums (a complex sum divided by a real one, component by component) and rounded to float once.  The
+ * iteration is the classic restarted GCR: r = fp32(f), x = 0; per step p = r, Ap = A r; beta_j = <Ap_j, Ap> / <Ap_j, Ap_j> and
+ * p -= beta_j p_j, Ap -= beta_j Ap_j over the stored directions in slot order (<a, b> = sum conj(a) b); alpha = <Ap, r> / <Ap, Ap>;
+ * x += alpha p, r -= alpha Ap; all slots are wiped every `restart` steps.  The tolerance is tested at the start of a step, on the
+ * |r|^2 the step before left and |f|^2 = |fp32(f)|^2.  f = 0, or an exactly zero <Ap, Ap>, stops the solve with what x holds: f = 0
+ * gives y = 0, never NaN.  y = fp64(x).
+ * MGCR_ERR_UNSUPPORTED, with a message: truncation != 0, restart == 0 or restart > 16, any preconditioner, use_x0, flexible or
+ * profile_spmv in `inner`.  MGCR_ERR_INVALID: max_iter < 1, a negative tol, a non-square matrix (a column outside 0 .. n-1) or
+ * inconsistent CSR, k = 0, mgcr_gcr32_set_k on the matrix form, a stored value or a k that is not finite or becomes infinite when
+ * rounded to float (the message names the row).  A refused mgcr_gcr32_set_k / mgcr_gcr32_set_param leaves the operator as it was.
+ * Accepted by mgcr_op_apply (fp64 Fields of n entries), mgcr_op_destroy, mgcr_op_dim / nrow / nnz, and by the right_precond slot of
+ * mgcr_gcr_solve, mgcr_gcr_create (+ mgcr_gcr_set_param) and mgcr_gcr_solve_op — but only with flexible = 1: the inner solve stops
+ * on a tolerance, so it is not a linear map.  With flexible = 0, or in the left_precond slot: MGCR_ERR_UNSUPPORTED; a dimension that
+ * differs from the outer operator's: MGCR_ERR_INVALID; a distributed outer operator: MGCR_ERR_UNSUPPORTED.
+ * Refused with MGCR_ERR_UNSUPPORTED: as the system operator of any solve (mgcr_gcr_solve, mgcr_gcr_create, mgcr_gcr_set_operator),
+ * mgcr_mg_create, mgcr_op_apply_multi, mgcr_gcr_solve_multi, mgcr_gcr_solve_queue, mgcr_eo_solve_queue and the storage queries
+ * (mgcr_op_stored_bytes / storage_format / ell_layout / xr_fuse_kind / halo_kind; ask mgcr_gcr32_info).
+ * All storage (r, Ar, x, 2 * restart slots, slabs, state) belongs to the operator: allocated here or by mgcr_gcr32_set_param, freed by
+ * mgcr_op_destroy.  k travels in the kernel arguments of every launch: what is already enqueued keeps the old value.
+ * In the right_precond slot the apply that follows an outer step's residual update is handed that solve's own stopping test (the
+ * |r|^2 partials, |b|^2, tol^2) and evaluates it with the solver's fold and expression: behind the LAST update — the outer solver
+ * enqueues its preconditioner before the step's test — the inner solve is cut to 0 steps and y = 0, which nothing reads.
+ * Counters (mgcr_stat, one synchronisation each): "gcr32_applies" = applies that ran on the device, "gcr32_steps" = the inner steps
+ * those enqueued (max_iter per apply); an apply silenced because its outer solve was over, or cut as above, counts in neither: a
+ * mixed solve of N outer steps moves them by N and max_iter N. */
+int mgcr_gcr32_create(int64_t n, const int64_t *rowptr, const int64_t *col, const double *val_ri, const double *k_ri,
+                      const mgcr_gcr_param *inner, mgcr_op_t *out);
+int mgcr_gcr32_set_k(mgcr_op_t op, const double k_ri[2]);          /* Dirac form only */
+int mgcr_gcr32_set_param(mgcr_op_t op, const mgcr_gcr_param *inner);
+/* stored_bytes: the fp32 matrix copy (slab, tail, their index tables) */
+int mgcr_gcr32_info(mgcr_op_t op, int64_t *n, int32_t *ell_width, int64_t *tail_rows, int32_t *real_slab, int64_t *stored_bytes);
+/* test hook: y = fp64(A32 fp32(x)), one matrix apply in fp32 (BIT-IDENTICAL to the arithmetic above; uses the operator's r and Ar) */
+int mgcr_gcr32_apply_matrix(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y);
+/* ONE synchronisation: steps the last apply performed and its last fp32 |r| / |f| */
+int mgcr_gcr32_last(mgcr_op_t op, int32_t *n_iter, double *rel_res);
 
 /* ---- MG: src/MG.h, src/Mesh.h, src/SolverParam.h:38-59 ------------------------------------ */
 typedef struct mgcr_mg_param {

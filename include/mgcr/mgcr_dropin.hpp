@@ -857,6 +857,75 @@ private:
     mgcr_op_t dense_op = nullptr;
 };
 
+// LowPrecisionGCR: mixed precision (extension, mgcr_gcr32_create) — an fp32 copy of a Sparse (its arrays are copied, so later changes of
+// the Sparse are not seen) and a restarted GCR that runs in fp32 on the device, from x0 = 0, without host round trips.  With k:
+// A = Id - k*D (Dirac form); without: A = the matrix.  inner: restart (1 .. 16), max_iter (steps enqueued per apply), tol (relative).
+// operator()(f) returns y ~ A^-1 f.  Its place is GCR_Param::right_precond of an fp64 solve with flexible = true: the inner solve
+// stops on a tolerance, so it is not a linear map, and every other slot refuses it.
+template <typename num_type>
+class LowPrecisionGCR : public Operator<num_type> {
+public:
+    LowPrecisionGCR(Sparse<num_type> *mat, std::complex<double> k_factor, const GCR_Param<num_type> *inner) : k(k_factor) { create(mat, true, inner); }
+    LowPrecisionGCR(Sparse<num_type> *mat, const GCR_Param<num_type> *inner) { create(mat, false, inner); }
+    LowPrecisionGCR(LowPrecisionGCR const &) = delete;
+    LowPrecisionGCR &operator=(LowPrecisionGCR const &) = delete;
+    ~LowPrecisionGCR() override { if (op) mgcr_op_destroy(op); }
+    std::complex<double> val_at(num_type, num_type) const override { return not_stored(); }
+    std::complex<double> val_at(num_type) const override { return not_stored(); }
+    Field<num_type> operator()(Field<num_type> const &f) override { return this->apply_handle(f, op, this->dim); }
+    mgcr_op_t handle() override { return op; }
+    void set_k(std::complex<double> new_k) { double v[2] = {new_k.real(), new_k.imag()}; mgcr_detail::ok(mgcr_gcr32_set_k(op, v), "LowPrecisionGCR::set_k"); k = new_k; }
+    void set_param(const GCR_Param<num_type> *inner) { mgcr_gcr_param p = cparam(inner); mgcr_detail::ok(mgcr_gcr32_set_param(op, &p), "LowPrecisionGCR::set_param"); }
+    // y = fp64(A32 fp32(x)): one matrix apply in fp32
+    void apply_matrix(const Field<num_type> &x, Field<num_type> &y) {
+        mgcr_detail::ok(mgcr_gcr32_apply_matrix(op, x.device(), y.device()), "LowPrecisionGCR::apply_matrix");
+        y.device_written();
+    }
+    // steps the last apply performed and its last fp32 |r| / |f| (one synchronisation)
+    int last(double *rel_res = nullptr) {
+        int32_t it = 0;
+        double rel = 0.;
+        mgcr_detail::ok(mgcr_gcr32_last(op, &it, &rel), "LowPrecisionGCR::last");
+        if (rel_res) *rel_res = rel;
+        return (int)it;
+    }
+    struct Info { int64_t n; int32_t ell_width; int64_t tail_rows; bool real_slab; int64_t stored_bytes; };
+    Info info() {
+        Info i{};
+        int32_t real = 0;
+        mgcr_detail::ok(mgcr_gcr32_info(op, &i.n, &i.ell_width, &i.tail_rows, &real, &i.stored_bytes), "LowPrecisionGCR::info");
+        i.real_slab = real != 0;
+        return i;
+    }
+
+private:
+    static std::complex<double> not_stored() { std::fprintf(stderr, "LowPrecisionGCR stores an fp32 copy on the device only\n"); std::abort(); }
+    static mgcr_gcr_param cparam(const GCR_Param<num_type> *inner) {
+        mgcr_gcr_param p;
+        std::memset(&p, 0, sizeof(p));
+        p.truncation = inner->truncation; p.restart = inner->restart; p.max_iter = inner->max_iter; p.tol = inner->tol;
+        p.left_precond = inner->left_precond ? inner->left_precond->handle() : nullptr;
+        p.right_precond = inner->right_precond ? inner->right_precond->handle() : nullptr;
+        p.use_x0 = inner->use_x0; p.flexible = inner->flexible;
+        return p;
+    }
+    void create(Sparse<num_type> *mat, bool dirac, const GCR_Param<num_type> *inner) {
+        mgcr_detail::ensure_init();
+        const num_type rows = mat->get_nrow(), nnz = mat->get_nnz();
+        std::vector<int64_t> rp((size_t)rows + 1), ci((size_t)nnz);
+        std::vector<std::complex<double>> va((size_t)nnz);
+        for (num_type i = 0; i <= rows; i++) rp[(size_t)i] = (int64_t)mat->get_ROW(i);
+        for (num_type i = 0; i < nnz; i++) { ci[(size_t)i] = (int64_t)mat->get_COL(i); va[(size_t)i] = mat->val_at(i); }
+        double v[2] = {k.real(), k.imag()};
+        mgcr_gcr_param p = cparam(inner);
+        mgcr_detail::ok(mgcr_gcr32_create((int64_t)rows, rp.data(), ci.data(), reinterpret_cast<const double *>(va.data()), dirac ? v : nullptr, &p, &op),
+                        "LowPrecisionGCR");
+        this->dim = rows;
+    }
+    std::complex<double> k{0., 0.};
+    mgcr_op_t op = nullptr;
+};
+
 // EvenOddDiracOp: the even-odd (red-black) preconditioned Id - k*D (extension, mgcr_eo_create) — an Operator on the EVEN half of the
 // rows, S = Id - k^2 D_eo D_oe.  D is a Sparse holding a pure hopping matrix (square, no diagonal, even rows coupled to odd rows
 // only; its arrays are copied, so later changes of the Sparse are not seen).  GCR(&op, &param) solves the Schur system like any other

@@ -162,6 +162,12 @@ _SIGS = {
     "mgcr_eo_multi_prepare": (C.c_int, [_vp, _vp, _vp]),
     "mgcr_eo_multi_reconstruct": (C.c_int, [_vp, _vp, _vp, _vp]),
     "mgcr_eo_multi_solve": (C.c_int, [_vp, C.POINTER(GcrParamC), _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mgcr_gcr32_create": (C.c_int, [C.c_int64, _vp, _vp, _vp, _dp, C.POINTER(GcrParamC), C.POINTER(_vp)]),
+    "mgcr_gcr32_set_k": (C.c_int, [_vp, _dp]),
+    "mgcr_gcr32_set_param": (C.c_int, [_vp, C.POINTER(GcrParamC)]),
+    "mgcr_gcr32_info": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "mgcr_gcr32_apply_matrix": (C.c_int, [_vp, _vp, _vp]),
+    "mgcr_gcr32_last": (C.c_int, [_vp, C.POINTER(C.c_int32), _dp]),
     "mgcr_timer_start": (C.c_int, []),
     "mgcr_timer_stop": (C.c_int, [_dp]),
 }

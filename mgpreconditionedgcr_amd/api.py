@@ -886,6 +886,54 @@ class GCR(Operator):
         return x_list
 
 
+class LowPrecisionGCR(Operator):
+    """Mixed precision: an fp32 copy of `mat` (a Sparse; its host arrays ROW, COL, VAL are used) and a restarted GCR that runs in
+    fp32 on the device, from x0 = 0, without host round trips (mgcr_gcr32_create).  k given: A = 1 - k D (Dirac form); k None: A = the
+    matrix.  gcr_param: restart (1 .. 16), max_it (steps enqueued per apply), tau (relative tolerance).  operator()(f) returns
+    y ~ A^-1 f; its place is GCR_Param(solver_r=..., flexible=True) of an fp64 solve."""
+
+    def __init__(self, mat, k=None, gcr_param=None):
+        super().__init__()
+        _lib.init()
+        if gcr_param is None:
+            gcr_param = GCR_Param(0, 8, 8, 0.1, False)
+        self.param = gcr_param
+        self.k = None if k is None else complex(k)
+        h = C.c_void_p()
+        pc = gcr_param._c()
+        n = int(mat.ROW.size - 1)
+        check(_lib.lib().mgcr_gcr32_create(n, mat.ROW.ctypes.data, mat.COL.ctypes.data, mat.VAL.ctypes.data,
+                                           _ri(k) if k is not None else None, C.byref(pc), C.byref(h)))
+        self.h = h
+
+    def set_k(self, k):
+        check(_lib.lib().mgcr_gcr32_set_k(self.h, _ri(k)))
+        self.k = complex(k)
+
+    def set_param(self, gcr_param):
+        pc = gcr_param._c()
+        check(_lib.lib().mgcr_gcr32_set_param(self.h, C.byref(pc)))
+        self.param = gcr_param
+
+    def apply_matrix(self, x, out=None):
+        """y = fp64(A32 fp32(x)): one matrix apply in fp32 (the test hook of the arithmetic)."""
+        if out is None:
+            out = Field(x.dims)
+        check(_lib.lib().mgcr_gcr32_apply_matrix(self.h, x.h, out.h))
+        return out
+
+    def last(self):
+        """(steps the last apply performed, its last fp32 |r| / |f|): one synchronisation."""
+        it, rel = C.c_int32(), C.c_double()
+        check(_lib.lib().mgcr_gcr32_last(self.h, C.byref(it), C.byref(rel)))
+        return it.value, rel.value
+
+    def info(self):
+        n, w, t, real, b = C.c_int64(), C.c_int32(), C.c_int64(), C.c_int32(), C.c_int64()
+        check(_lib.lib().mgcr_gcr32_info(self.h, C.byref(n), C.byref(w), C.byref(t), C.byref(real), C.byref(b)))
+        return dict(n=n.value, ell_width=w.value, tail_rows=t.value, real_slab=bool(real.value), stored_bytes=b.value)
+
+
 def legacy_dense_gcr(matrix, rhs, x, tol, max_iter, truncation, verbose=True):
     """GCR(matrix, dimension).solve(rhs, x, tol, max_iter, truncation) — the reference's legacy raw-pointer dense solve
     (src/GCR.h:70-156): r0 = rhs - A x (x0 honoured), directions truncated to the last `truncation`, stops when

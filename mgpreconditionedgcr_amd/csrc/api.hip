@@ -161,6 +161,7 @@ int mgcr_op_destroy(mgcr_op_t op) {
         case OP_GCR: gcr_state_destroy(op->gcr); break;
         case OP_MG: mg_destroy(op->mg); break;
         case OP_DIRAC_EO: eo_destroy(op->eo); break;
+        case OP_GCR32: gcr32_destroy(op->g32); break;
         case OP_DIRAC_EO_MULTI: eo_multi_destroy(op->eom); break;   // (the even-odd operator behind it is borrowed)
         default: break;  // OP_DIRAC and OP_DIRAC_MULTI borrow their Sparse (src/Operator.h:117,555-560)
     }
@@ -179,6 +180,7 @@ int64_t mgcr_op_nnz(mgcr_op_t op) {
         case OP_BCSR: return (int64_t)op->bcsr.nblocks * op->bcsr.bs * op->bcsr.bs;  // src/HierarchicalSparse.h:31
         case OP_DIRAC_EO: return eo_nnz(op->eo);   // that of D
         case OP_DIRAC_EO_MULTI: return eo_multi_nnz(op->eom);
+        case OP_GCR32: return gcr32_nnz(op->g32);   // that of the matrix it copied
         default: return -1;
     }
 }
@@ -186,6 +188,7 @@ int64_t mgcr_op_nnz(mgcr_op_t op) {
 int mgcr_op_storage_format(mgcr_op_t op, int32_t *format, int32_t *n_patterns) {
     MGCR_CHECK(op, MGCR_ERR_INVALID, "null operator");
     MGCR_REFUSE_EVENODD_MULTI(op, "mgcr_op_storage_format");
+    MGCR_REFUSE_GCR32(op, "mgcr_op_storage_format");
     const Op *o = op_matrix(op);
     MGCR_CHECK(o->kind == OP_CSR, MGCR_ERR_UNSUPPORTED, "mgcr_op_storage_format: not a Sparse");
     if (format) *format = csr_stencil_active(o->csr) ? 3 : o->csr.pat_mode;
@@ -197,6 +200,7 @@ int mgcr_op_ell_layout(mgcr_op_t op, int32_t *ell_width, int32_t *lanes, int64_t
                        int32_t *x_window) {
     MGCR_CHECK(op, MGCR_ERR_INVALID, "null operator");
     MGCR_REFUSE_EVENODD_MULTI(op, "mgcr_op_ell_layout");
+    MGCR_REFUSE_GCR32(op, "mgcr_op_ell_layout");
     const Op *o = op_matrix(op);
     MGCR_CHECK(o->kind == OP_CSR, MGCR_ERR_UNSUPPORTED, "mgcr_op_ell_layout: not a Sparse");
     if (ell_width) *ell_width = o->csr.W;
@@ -211,6 +215,7 @@ int mgcr_op_ell_layout(mgcr_op_t op, int32_t *ell_width, int32_t *lanes, int64_t
 int mgcr_op_xr_fuse_kind(mgcr_op_t op, int32_t *kind) {
     MGCR_CHECK(op && kind, MGCR_ERR_INVALID, "mgcr_op_xr_fuse_kind: null argument");
     MGCR_REFUSE_EVENODD_MULTI(op, "mgcr_op_xr_fuse_kind");
+    MGCR_REFUSE_GCR32(op, "mgcr_op_xr_fuse_kind");
     const Op *o = op_matrix(op);
     MGCR_CHECK(o->kind == OP_CSR, MGCR_ERR_UNSUPPORTED, "mgcr_op_xr_fuse_kind: not a Sparse");
     *kind = csr_fusable(o->csr, o->dist) ? csr_xr_fuse_kind(o->csr, o->dist) : 0;
@@ -220,6 +225,7 @@ int mgcr_op_xr_fuse_kind(mgcr_op_t op, int32_t *kind) {
 int mgcr_op_halo_kind(mgcr_op_t op, int32_t *kind) {
     MGCR_CHECK(op && kind, MGCR_ERR_INVALID, "mgcr_op_halo_kind: null argument");
     MGCR_REFUSE_EVENODD_MULTI(op, "mgcr_op_halo_kind");
+    MGCR_REFUSE_GCR32(op, "mgcr_op_halo_kind");
     const Op *o = op_matrix(op);
     MGCR_CHECK(o->dist, MGCR_ERR_UNSUPPORTED, "mgcr_op_halo_kind: not a distributed Sparse");
     *kind = dist_halo_kind(o->dist);
@@ -277,6 +283,8 @@ int mgcr_stat(const char *name, int64_t *value) {
     else if (!strcmp(name, "evenodd_diag_fused_steps")) *value = eo_diag_fused_step_count();
     else if (!strcmp(name, "evenodd_block_applies")) *value = eo_block_apply_count();
     else if (!strcmp(name, "evenodd_block_fused_steps")) *value = eo_block_fused_step_count();
+    else if (!strcmp(name, "gcr32_applies")) *value = gcr32_apply_count();
+    else if (!strcmp(name, "gcr32_steps")) *value = gcr32_step_count();
     else { set_error("mgcr_stat: unknown counter '%s'", name); return MGCR_ERR_INVALID; }
     return MGCR_OK;
 }
@@ -290,6 +298,7 @@ int mgcr_selftest_coherence(int32_t steps, int32_t coherent, int64_t *rows_wrong
 int mgcr_op_stored_bytes(mgcr_op_t op, int64_t *matrix_bytes, int32_t *ell_width, int64_t *tail_nnz) {
     MGCR_CHECK(op, MGCR_ERR_INVALID, "null operator");
     MGCR_REFUSE_EVENODD_MULTI(op, "mgcr_op_stored_bytes");
+    MGCR_REFUSE_GCR32(op, "mgcr_op_stored_bytes");
     const Op *o = op_matrix(op);
     if (o->kind == OP_CSR) {
         const CsrDev &A = o->csr;
@@ -335,6 +344,7 @@ int mgcr_gcr_solve(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_vec_t rhs, mgc
     MGCR_CHECK(A && param && rhs && x, MGCR_ERR_INVALID, "mgcr_gcr_solve: null argument");
     MGCR_REFUSE_MULTI_DIRAC(A, "mgcr_gcr_solve");
     MGCR_REFUSE_EVENODD_MULTI(A, "mgcr_gcr_solve");
+    MGCR_REFUSE_GCR32(A, "mgcr_gcr_solve");
     // assertm(rhs.field_size() == this->dim, ...) src/GCR.h:160-161
     MGCR_CHECK(rhs->n == A->dim, MGCR_ERR_INVALID, "Field dimension does not match with Operator!");
     MGCR_CHECK(x->n == A->dim, MGCR_ERR_INVALID, "x dimension does not match with Operator!");
@@ -356,6 +366,7 @@ int mgcr_gcr_create(mgcr_op_t A, const mgcr_gcr_param *param, int32_t x0_mode, m
     MGCR_CHECK(param && out, MGCR_ERR_INVALID, "mgcr_gcr_create: null argument");
     MGCR_REFUSE_MULTI_DIRAC(A, "mgcr_gcr_create");
     MGCR_REFUSE_EVENODD_MULTI(A, "mgcr_gcr_create");
+    MGCR_REFUSE_GCR32(A, "mgcr_gcr_create");
     LOCK();
     mgcr_op_s *op = new mgcr_op_s();
     op->kind = OP_GCR;
@@ -371,6 +382,7 @@ int mgcr_gcr_set_operator(mgcr_op_t gcr, mgcr_op_t A) {
     MGCR_CHECK(gcr && A && gcr->kind == OP_GCR, MGCR_ERR_INVALID, "mgcr_gcr_set_operator: not a GCR operator");
     MGCR_REFUSE_MULTI_DIRAC(A, "mgcr_gcr_set_operator");
     MGCR_REFUSE_EVENODD_MULTI(A, "mgcr_gcr_set_operator");
+    MGCR_REFUSE_GCR32(A, "mgcr_gcr_set_operator");
     LOCK();
     gcr->dim = A->dim;  // GCR::initialise src/GCR.h:31
     gcr->nrow = A->dim;
@@ -443,6 +455,7 @@ int mgcr_bench_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y, int32_t reps, 
 static int apply_multi_checks(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y, const char *who) {
     MGCR_CHECK(op && x && y, MGCR_ERR_INVALID, "%s: null argument", who);
     MGCR_REFUSE_EVENODD(op, who);
+    MGCR_REFUSE_GCR32(op, who);
     MGCR_CHECK(op->kind != OP_GCR && op->kind != OP_MG, MGCR_ERR_UNSUPPORTED, "%s: GCR and MG objects cannot be applied to a block of Fields", who);
     const Op *b0 = op_matrix(op);
     MGCR_CHECK(!op->dist && !op->comm && !b0->dist && !b0->comm, MGCR_ERR_UNSUPPORTED, "%s: distributed operators are not supported", who);
@@ -487,6 +500,7 @@ int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t r
     MGCR_TRY(require_ctx());
     MGCR_CHECK(A && param && rhs && x, MGCR_ERR_INVALID, "mgcr_gcr_solve_multi: null argument");
     MGCR_REFUSE_EVENODD(A, "mgcr_gcr_solve_multi");
+    MGCR_REFUSE_GCR32(A, "mgcr_gcr_solve_multi");
     MGCR_CHECK(param->truncation >= 0 && param->restart >= 0 && param->max_iter >= 0, MGCR_ERR_INVALID, "negative GCR parameter");
     MGCR_CHECK(param->truncation == 0, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: truncation mode is not supported (restart mode only)");
     MGCR_CHECK(param->restart != 0, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: restart mode only (restart != 0)");
@@ -517,6 +531,7 @@ int mgcr_gcr_solve_queue(mgcr_op_t A, const mgcr_gcr_param *param, int32_t width
     MGCR_CHECK(A && param && rhs && x, MGCR_ERR_INVALID, "%s: null argument", who);
     MGCR_REFUSE_EVENODD(A, who);
     MGCR_REFUSE_EVENODD_MULTI(A, who);
+    MGCR_REFUSE_GCR32(A, who);
     MGCR_CHECK(param->truncation >= 0 && param->restart >= 0 && param->max_iter >= 0, MGCR_ERR_INVALID, "negative GCR parameter");
     MGCR_CHECK(param->truncation == 0, MGCR_ERR_UNSUPPORTED, "%s: truncation mode is not supported (restart mode only)", who);
     MGCR_CHECK(param->restart != 0, MGCR_ERR_UNSUPPORTED, "%s: restart mode only (restart != 0)", who);

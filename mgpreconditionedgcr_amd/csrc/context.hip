@@ -79,6 +79,7 @@ int mgcr_finalize(void) {
     hipStreamSynchronize(c.stream);
     resident_shutdown();
     multi_release();
+    gcr32_release();
     hipEventDestroy(c.ev0);
     hipEventDestroy(c.ev1);
     hipHostFree(c.h_mail);

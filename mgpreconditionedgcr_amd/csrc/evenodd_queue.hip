@@ -190,6 +190,7 @@ int mgcr_eo_solve_queue(mgcr_op_t eo, const mgcr_gcr_param *param, int32_t width
     const char *who = "mgcr_eo_solve_queue";
     MGCR_TRY(require_ctx());
     MGCR_CHECK(eo && param && rhs_full && x_full && k_ri, MGCR_ERR_INVALID, "%s: null argument", who);
+    MGCR_REFUSE_GCR32(eo, who);
     MGCR_CHECK(eo->kind == OP_DIRAC_EO && eo->eo, MGCR_ERR_INVALID,
                "%s: the operator must be an even-odd preconditioned DiracOp (its halves carry the queue; the hopping parameters come per system)", who);
     MGCR_CHECK(!eo->eo->has_diag, MGCR_ERR_UNSUPPORTED,

@@ -381,7 +381,7 @@ __global__ void __launch_bounds__(RED_THREADS) build_kernel(DevState *__restrict
             st->rr = rr[0];
             if (git < hist_cap) hist[git] = sqrt(rr[0]) / sqrt(st->bnorm2);
             // continue while |r|^2/|b|^2 > tol^2 (src/GCR.h:288); NaN compares false -> stop, like the reference
-            if (!((rr[0] / st->bnorm2) > st->tol2)) st->stop_at = git;
+            if (gcr_solve_ends(rr[0], st->bnorm2, st->tol2)) st->stop_at = git;
             if (XUPD) st->npend = 0;
         }
     }
@@ -709,6 +709,8 @@ int op_apply_raw(Op *op, const cplx *x, cplx *y, int64_t n) {
             return mg_apply(op->mg, x, y);
         case OP_DIRAC_EO:   // the Schur complement on the even half: two launches (evenodd.hip)
             return eo_apply(op, x, y, n);
+        case OP_GCR32:   // the fp32 inner solve (gcr32.hip)
+            return gcr32_apply(op, x, y, n);
         case OP_DIRAC_MULTI:   // (reached through a preconditioner slot; the entry points refuse it themselves)
             set_error("a MultiDiracOp has one hopping parameter per column of a block and cannot be applied to a single Field");
             return MGCR_ERR_UNSUPPORTED;
@@ -766,6 +768,8 @@ int gcr_state_create(Op *A, const mgcr_gcr_param *p, int x0_mode, GcrState **out
     // assertm(param->truncation==0 || param->restart==0, ...) src/GCR.h:165
     MGCR_CHECK(p->truncation == 0 || p->restart == 0, MGCR_ERR_INVALID, "Do not support concurrent restarting and truncation.");
     MGCR_CHECK(p->truncation >= 0 && p->restart >= 0 && p->max_iter >= 0, MGCR_ERR_INVALID, "negative GCR parameter");
+    MGCR_REFUSE_GCR32(A, "GCR");
+    MGCR_TRY(gcr32_slot_check(p, A));
     GcrState *s = new GcrState();
     s->A = A;
     s->p = *p;
@@ -787,11 +791,14 @@ void gcr_state_set_use_x0(GcrState *s, bool use_x0) { s->p.use_x0 = use_x0 ? 1 :
 int gcr_state_set_param(GcrState *s, const mgcr_gcr_param *p) {
     MGCR_CHECK(p->truncation == 0 || p->restart == 0, MGCR_ERR_INVALID, "Do not support concurrent restarting and truncation.");
     MGCR_CHECK(p->truncation >= 0 && p->restart >= 0 && p->max_iter >= 0, MGCR_ERR_INVALID, "negative GCR parameter");
+    MGCR_TRY(gcr32_slot_check(p, s->A));
     s->p = *p;
     return MGCR_OK;
 }
 
 int gcr_state_set_operator(GcrState *s, Op *A) {
+    MGCR_REFUSE_GCR32(A, "GCR");
+    MGCR_TRY(gcr32_slot_check(&s->p, A));
     s->A = A;
     return MGCR_OK;
 }
@@ -1233,6 +1240,18 @@ struct Step {
     bool ended = false;            // the residual update was all this step had to do (alpha_only_kernel)
 };
 
+// M r behind a step's residual update (flexible mode).  The step's stopping test comes only with its build, so this apply is
+// enqueued whether or not the solve ends on r, and behind the last update its result is never used.  A low-precision GCR — an
+// expensive apply — is handed the test itself (Gcr32Gate) and does not run then; every other operator is applied as before.
+// (In flexible mode the update that precedes this is always xr_update_kernel, which leaves the step's |r|^2 partials in s->partsR:
+// the residual update fused into an apply and the one-launch steps exclude a preconditioner.)
+static int flex_precond_apply(GcrState *s, const SolvePlan &pl, cplx *out) {
+    Op *M = (Op *)s->p.right_precond;
+    if (M->kind == OP_GCR32 && !pl.multi)
+        return gcr32_apply(M, s->r, out, pl.n, Gcr32Gate{s->partsR, pl.g, RED_MAX_BLOCKS, &s->st->bnorm2, &s->st->tol2});
+    return op_apply_raw(M, s->r, out, pl.n);
+}
+
 // alpha, x, r of a lean step (r goes to the residual ring); with both endings of a nested solve whose caller does not want the last residual
 static int step_residual_lean(GcrState *s, const SolvePlan &pl, StepCursor &c, Step &st) {
     const int cur = c.cur;
@@ -1263,7 +1282,7 @@ static int step_residual_lean(GcrState *s, const SolvePlan &pl, StepCursor &c, S
     c.rcur = r_out;
     st.dir = r_out;
     if (pl.flex && !st.tail) {
-        MGCR_TRY(op_apply_raw((Op *)s->p.right_precond, s->r, dslot, pl.n));
+        MGCR_TRY(flex_precond_apply(s, pl, dslot));
         st.dir = dslot;
     }
     return MGCR_OK;
@@ -1281,7 +1300,7 @@ static int step_residual_classic(GcrState *s, const SolvePlan &pl, StepCursor &c
     }));
     st.dir = s->r;
     if (pl.flex && !st.tail) {
-        MGCR_TRY(op_apply_raw((Op *)p.right_precond, s->r, s->z, pl.n));
+        MGCR_TRY(flex_precond_apply(s, pl, s->z));
         st.dir = s->z;
     } else if (p.right_precond && !pl.flex) {  // src/GCR.h:236-238
         MGCR_TRY(op_apply_raw((Op *)p.right_precond, s->r, s->tmp, pl.n));

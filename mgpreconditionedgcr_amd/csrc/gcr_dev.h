@@ -208,8 +208,7 @@ __device__ __forceinline__ void close_step(DevState *st, int it, double rr, doub
     st->iter = git;
     st->rr = rr;
     if (git < hist_cap) hist[git] = sqrt(rr) / sqrt(st->bnorm2);
-    // continue while |r|^2/|b|^2 > tol^2 (src/GCR.h:288); NaN compares false -> stop, like the reference
-    if (!((rr / st->bnorm2) > st->tol2)) st->stop_at = git;
+    if (gcr_solve_ends(rr, st->bnorm2, st->tol2)) st->stop_at = git;
     if (clear_pending) st->npend = 0;
 }
 

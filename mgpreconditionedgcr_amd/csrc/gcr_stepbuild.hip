@@ -230,7 +230,7 @@ __global__ void __launch_bounds__(RED_THREADS, 8) step_build_kernel(StepBuildArg
             close_step(a.st, a.it, rr[0], a.hist, a.hist_cap, CLOSE);
             if (CLOSE) a.st->closed = 1;   // (P0' is written below, by every workgroup that reaches the close pass)
         }
-        ends_here = !((rr[0] / a.st->bnorm2) > a.st->tol2);
+        ends_here = gcr_solve_ends(rr[0], a.st->bnorm2, a.st->tol2);
     }
     if ((int)threadIdx.x < NDT) sbeta[threadIdx.x] = cdiv(make_double2(res_total(sy, 2 * threadIdx.x), res_total(sy, 2 * threadIdx.x + 1)), a.den[threadIdx.x]);
     __syncthreads();

@@ -83,7 +83,7 @@ struct MVec {
 };
 constexpr int MV_MAX_K = 16;
 
-enum OpKind { OP_CSR = 1, OP_DIRAC = 2, OP_BCSR = 3, OP_GCR = 4, OP_MG = 5, OP_DIRAC_MULTI = 6, OP_DIRAC_EO = 7, OP_DIRAC_EO_MULTI = 8 };
+enum OpKind { OP_CSR = 1, OP_DIRAC = 2, OP_BCSR = 3, OP_GCR = 4, OP_MG = 5, OP_DIRAC_MULTI = 6, OP_DIRAC_EO = 7, OP_DIRAC_EO_MULTI = 8, OP_GCR32 = 9 };
 
 // ELL slab + CSR tail (int32 indices).
 //   ELL: W = nchunk*L entries per row, L lanes co-operate on a row.
@@ -161,6 +161,7 @@ struct Comm;
 struct DistCsr;
 struct EoState;
 struct EoMultiState;
+struct Gcr32State;
 
 struct Op {
     OpKind kind;
@@ -176,6 +177,7 @@ struct Op {
     MgState *mg = nullptr;    // OP_MG
     EoState *eo = nullptr;    // OP_DIRAC_EO: the Schur complement 1 - k^2 D_eo D_oe on the even half (evenodd.hip; owned)
     EoMultiState *eom = nullptr;   // OP_DIRAC_EO_MULTI: borrows the halves of an OP_DIRAC_EO, owns its work blocks (evenodd_multi.hip)
+    Gcr32State *g32 = nullptr;     // OP_GCR32: the low-precision GCR — an fp32 matrix copy and its inner solve's storage (gcr32.hip; owned)
     DistCsr *dist = nullptr;  // OP_CSR / OP_BCSR row block of a distributed matrix (halo.hip; owned)
     Comm *comm = nullptr;     // communicator the operator's Fields are distributed over (borrowed)
 };
@@ -197,6 +199,12 @@ inline const Op *op_matrix(const Op *op) { return op && (op->kind == OP_DIRAC ||
     MGCR_CHECK(!(op) || (op)->kind != OP_DIRAC_EO_MULTI, MGCR_ERR_UNSUPPORTED,                                                        \
                "%s: a MultiEvenOddDiracOp has one hopping parameter per column of a block of even halves; only mgcr_op_apply_multi, "  \
                "mgcr_gcr_solve_multi and the mgcr_eo_multi entry points take it", who)
+
+// ... and every entry point but mgcr_op_apply, the queries of dim / nrow / nnz and the right_precond slot's answer to a low-precision GCR
+#define MGCR_REFUSE_GCR32(op, who)                                                                                                    \
+    MGCR_CHECK(!(op) || (op)->kind != OP_GCR32, MGCR_ERR_UNSUPPORTED,                                                                 \
+               "%s: a low-precision GCR is an inexact inverse; it is applied (mgcr_op_apply) or goes into the right_precond slot of a "   \
+               "flexible solve", who)
 
 // ---- blas1.hip -------------------------------------------------------------------------------
 int red_grid(int64_t n);
@@ -432,6 +440,28 @@ int eo_schur_step(Op *op, const cplx *x, cplx *y, const cplx *const *vecs, int n
 void eo_multi_destroy(EoMultiState *m);
 int64_t eo_multi_nnz(const EoMultiState *m);
 int eo_apply_multi(Op *op, const cplx *x, cplx *y, int64_t n, int k);   // Y_j = X_j - k_j^2 D_eo (D_oe X_j), two k-wide applies
+
+// ---- gcr32.hip: the low-precision GCR (OP_GCR32) -------------------------------------------------
+void gcr32_destroy(Gcr32State *g);
+int64_t gcr32_nnz(const Gcr32State *g);
+// THE stopping test of a GCR solve (src/GCR.h:288: continue while |r|^2 / |b|^2 > tol^2; NaN compares false -> stop, like the
+// reference).  One copy for the step bookkeeping (gcr_dev.h close_step, gcr_stepbuild.hip) and for the gate below, which must agree
+// bit for bit.
+__host__ __device__ inline bool gcr_solve_ends(double rr, double bnorm2, double tol2) { return !((rr / bnorm2) > tol2); }
+
+// The outer solve's own stopping test, handed to an apply that follows a residual update: the partials of |r|^2 that update wrote and
+// the solve's |b|^2 and tol^2.  The apply's entry kernel evaluates gcr_solve_ends on them, with close_step's fold and so its bits:
+// when the outer solve is about to end on this residual, the inner solve is not run and y = 0 (nobody reads it)
+struct Gcr32Gate {
+    const double *partsR = nullptr;
+    int nblk = 0, stride = 0;
+    const double *bnorm2 = nullptr, *tol2 = nullptr;
+};
+int gcr32_apply(Op *op, const cplx *f, cplx *y, int64_t n, Gcr32Gate gate = Gcr32Gate());   // y ~ A^-1 f: 3 * max_iter + 2 launches, no host round trip
+void gcr32_release();   // the device-side counters (mgcr_finalize)
+int gcr32_slot_check(const mgcr_gcr_param *p, const Op *A);   // the preconditioner slots of an fp64 solve on A (A may be null)
+int64_t gcr32_apply_count();  // applies that ran on the device (not silenced by an outer solve that was over): one synchronisation
+int64_t gcr32_step_count();   // the inner steps those enqueued
 
 // ---- mvec.hip / spmm.hip / gcr_multi.hip: blocks of k Fields ------------------------------------
 int mv_copy(cplx *dst, const cplx *src, int64_t n, int k);

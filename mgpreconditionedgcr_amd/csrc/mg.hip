@@ -394,6 +394,7 @@ int mgcr_mg_create(mgcr_op_t A, const mgcr_mg_param *param, mgcr_op_t *out) {
     MGCR_REFUSE_MULTI_DIRAC(A, "mgcr_mg_create");
     MGCR_REFUSE_EVENODD(A, "mgcr_mg_create");
     MGCR_REFUSE_EVENODD_MULTI(A, "mgcr_mg_create");
+    MGCR_REFUSE_GCR32(A, "mgcr_mg_create");
     LOCK();
     MgState *m = nullptr;
     MGCR_TRY(mg_create(A, param, &m));
