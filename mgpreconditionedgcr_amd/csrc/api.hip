@@ -254,6 +254,7 @@ int mgcr_set_option(const char *name, int value, int *previous) {
         last = value != 0;
     }
     else if (!strcmp(name, "step_build_keep_all")) prev = set_stepbuild_keep_all_enabled(value != 0);
+    else if (!strcmp(name, "step_build_pair")) prev = set_stepbuild_pair_enabled(value != 0);
     else if (!strcmp(name, "halo_split")) prev = set_halo_split(value != 0);
     else if (!strcmp(name, "pw_tail")) prev = set_pw_tail_enabled(value != 0);
     else { set_error("mgcr_set_option: unknown option '%s'", name); return MGCR_ERR_INVALID; }
@@ -264,9 +265,13 @@ int mgcr_set_option(const char *name, int value, int *previous) {
 int mgcr_stat(const char *name, int64_t *value) {
     MGCR_CHECK(name && value, MGCR_ERR_INVALID, "mgcr_stat: null argument");
     if (!strcmp(name, "resident_solves")) *value = resident_solve_count();
+    // The three step counters count steps by FORM, not by kernel symbol: every one-launch step | those at >= 4 directions that read
+    // r once | those whose apply takes its own r from the diagonal gather.  A step that runs as step_pair_kernel (gcr_steppair.hip)
+    // is counted by each of them it belongs to, and by step_pair_launches, which alone says which kernel ran.
     else if (!strcmp(name, "step_build_launches")) *value = stepbuild_launch_count();
     else if (!strcmp(name, "step_keep_wide_launches")) *value = stepbuild_keep_wide_launch_count();
     else if (!strcmp(name, "step_apply_own_launches")) *value = stepbuild_apply_own_launch_count();
+    else if (!strcmp(name, "step_pair_launches")) *value = stepbuild_pair_launch_count();
     else if (!strcmp(name, "start_build_launches")) *value = start_build_launch_count();
     else if (!strcmp(name, "small_solves")) *value = gcr_small_solve_count();
     else if (!strcmp(name, "one_launch_fallbacks")) *value = gcr_fallback_count();

@@ -313,6 +313,8 @@ int64_t stepbuild_apply_own_launch_count();    // ... of them, keep forms whose 
 bool set_start_build_enabled(bool on);         // ... and the start of a solve as one launch
 int64_t start_build_launch_count();
 bool set_stepbuild_keep_all_enabled(bool on);  // ... every one-launch step reads r once (step_keep_kernel)
+bool set_stepbuild_pair_enabled(bool on);      // gcr_steppair.hip: one workgroup per CU carries two logical ones (step_pair_kernel)
+int64_t stepbuild_pair_launch_count();         // one-launch steps that ran as step_pair_kernel
 int coherence_selftest(int steps, int coherent, int64_t *rows_wrong);   // gcr_resident.hip
 bool stepbuild_is_enabled();
 bool launch_is_coresident(const void *kernel, int threads, size_t dyn_lds, int grid);   // gcr_stepbuild.hip: asks the runtime
