@@ -568,6 +568,41 @@ int mgcr_gcr32_apply_matrix(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y);
 /* ONE synchronisation: steps the last apply performed and its last fp32 |r| / |f| */
 int mgcr_gcr32_last(mgcr_op_t op, int32_t *n_iter, double *rel_res);
 
+/* LowPrecisionEvenOddGCR: the low-precision GCR on the EVEN-ODD Schur system (csrc/gcr32_eo.hip).  The operator is an OP_GCR32 like
+ * the one above, with dim = nrow = n_e, whose matrix is the fp32 copy of
+ *     S = diag(a_e) - c^2 H_eo diag(1 / a_o) H_oe
+ * for the scalar forms of the even-odd operators: k_ri != NULL, Dirac form (a = 1 - k d, c = k; a matrix without a stored diagonal
+ * entry is the pure hopping operator of mgcr_eo_create and stores no a); k_ri == NULL, matrix form (a = d, c = -1).  Dense site
+ * blocks (mgcr_eo_create_block) are not covered.  Its place is the right_precond slot, flexible = 1, of mgcr_eo_solve, of
+ * mgcr_gcr_solve on an even-odd operator and of a GCR object; the inner GCR, its parameters, counters, mgcr_gcr32_set_k (Dirac form
+ * only), mgcr_gcr32_set_param, mgcr_gcr32_last and mgcr_gcr32_apply_matrix (Fields of n_e entries) are those of mgcr_gcr32_create;
+ * mgcr_op_nnz returns that of the stored matrix; mgcr_gcr32_info returns MGCR_ERR_UNSUPPORTED (ask mgcr_gcr32_eo_info).
+ * Colouring and refusals are mgcr_eo_create_diag's: the same host plan, the same message for a conflicting entry, k = 0 and a 1 / a_o
+ * that is exactly zero or not finite are MGCR_ERR_INVALID (the message names the full-system row); and so is a stored value, an a, a
+ * 1 / a_o, a k or a c^2 that is not finite in float.  A refused mgcr_gcr32_set_k leaves the operator as it was.
+ * Arithmetic (everything not said here is mgcr_gcr32_create's).  a and 1 / a_o are formed in fp64 by the operations
+ * mgcr_eo_create_diag documents (Rule 1d) and then rounded, (float)re, (float)im: mgcr_gcr32_eo_diag returns float32 of what
+ * mgcr_eo_diag returns for the same matrix and k, bit for bit.  c2_32 = (float) of c c, the product formed un-fused in fp64.  An
+ * off-diagonal value is (float)re, (float)im; the slabs are real when every stored off-diagonal imaginary part is zero — one flag
+ * for both halves.  Each half has the layout of the square form (its own W, slab [W][npad], tail with its own accumulator), and a
+ * row of either half is summed exactly as a row of the square form.
+ *   stage 1, odd rows:    u = H_oe32 r;  t = inv_o32 (.) u, an un-fused complex product  (t = u when no diagonal is stored)
+ *   stage 2, even rows:   v = H_eo32 t;  w = c2_32 v (un-fused);  y = a_e32 (.) r - w    (y = r - w when no diagonal is stored)
+ * 4 launches per inner step, 4 max_iter + 2 per apply.  The operator owns t (n_o elements).  a_e32 and inv_o32 are rewritten by
+ * mgcr_gcr32_set_k in stream order (what is enqueued keeps the old values), c2_32 travels in the kernel arguments.
+ * Slot check, in addition to mgcr_gcr32_create's: when the operator of the solve is itself an even-odd operator of the scalar forms,
+ * its n and its parity vector must equal this operator's (MGCR_ERR_INVALID: another colouring would still converge, slowly and
+ * silently); when it carries site blocks: MGCR_ERR_UNSUPPORTED.  k is NOT compared — a preconditioner at another k is legitimate.
+ * The batched and queued solves refuse any preconditioner. */
+int mgcr_gcr32_create_eo(int64_t n, const int64_t *rowptr, const int64_t *col, const double *val_ri,
+                         const int8_t *parity /* NULL: two-colour */, const double *k_ri /* NULL: matrix form */,
+                         const mgcr_gcr_param *inner, mgcr_op_t *out);
+/* widths and tail rows of H_eo and H_oe; stored_bytes: both fp32 halves and, when stored, a_e and 1 / a_o */
+int mgcr_gcr32_eo_info(mgcr_op_t op, int64_t *n, int64_t *n_even, int64_t *n_odd, int32_t *width_eo, int32_t *width_oe,
+                       int64_t *tail_rows_eo, int64_t *tail_rows_oe, int32_t *real_slab, int32_t *has_diag, int64_t *stored_bytes);
+/* a_e32 and inv_o32 as the device holds them ((1, 0) when no diagonal is stored) */
+int mgcr_gcr32_eo_diag(mgcr_op_t op, float *a_even_ri /* [n_e][2] */, float *inv_a_odd_ri /* [n_o][2] */);
+
 /* ---- MG: src/MG.h, src/Mesh.h, src/SolverParam.h:38-59 ------------------------------------ */
 typedef struct mgcr_mg_param {
     /* MG_Param::mesh + spacetime mask (src/SolverParam.h:41,47): row-major mesh of the fine

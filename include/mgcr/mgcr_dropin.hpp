@@ -900,6 +900,8 @@ public:
 
 private:
     static std::complex<double> not_stored() { std::fprintf(stderr, "LowPrecisionGCR stores an fp32 copy on the device only\n"); std::abort(); }
+
+protected:
     static mgcr_gcr_param cparam(const GCR_Param<num_type> *inner) {
         mgcr_gcr_param p;
         std::memset(&p, 0, sizeof(p));
@@ -909,6 +911,8 @@ private:
         p.use_x0 = inner->use_x0; p.flexible = inner->flexible;
         return p;
     }
+
+private:
     void create(Sparse<num_type> *mat, bool dirac, const GCR_Param<num_type> *inner) {
         mgcr_detail::ensure_init();
         const num_type rows = mat->get_nrow(), nnz = mat->get_nnz();
@@ -922,8 +926,69 @@ private:
                         "LowPrecisionGCR");
         this->dim = rows;
     }
+
+protected:
+    LowPrecisionGCR() {}
+    // the Sparse's host arrays as the C interface takes them
+    static void host_csr(Sparse<num_type> *mat, std::vector<int64_t> &rp, std::vector<int64_t> &ci, std::vector<std::complex<double>> &va) {
+        const num_type rows = mat->get_nrow(), nnz = mat->get_nnz();
+        rp.resize((size_t)rows + 1); ci.resize((size_t)nnz); va.resize((size_t)nnz);
+        for (num_type i = 0; i <= rows; i++) rp[(size_t)i] = (int64_t)mat->get_ROW(i);
+        for (num_type i = 0; i < nnz; i++) { ci[(size_t)i] = (int64_t)mat->get_COL(i); va[(size_t)i] = mat->val_at(i); }
+    }
     std::complex<double> k{0., 0.};
     mgcr_op_t op = nullptr;
+};
+
+// LowPrecisionEvenOddGCR: mixed precision on the even-odd Schur system (extension, mgcr_gcr32_create_eo) — an fp32 copy of
+// S = diag(a_e) - c^2 H_eo diag(1/a_o) H_oe of a Sparse that may store a site diagonal, and LowPrecisionGCR's inner solve on its n_even
+// rows.  With k: Dirac form (the operator of EvenOddDiracOp / EvenOddDiagDiracOp); without: matrix form (EvenOddSparse).  Its place
+// is GCR_Param::right_precond, flexible = true, of EvenOddDiracOp::solve or of a GCR on such an operator made from the same matrix
+// and parity.  set_k, set_param, apply_matrix (Fields of n_even entries) and last are inherited; info() of the base class is
+// refused by the library: ask eo_info().
+template <typename num_type>
+class LowPrecisionEvenOddGCR : public LowPrecisionGCR<num_type> {
+public:
+    LowPrecisionEvenOddGCR(Sparse<num_type> *mat, std::complex<double> k_factor, const GCR_Param<num_type> *inner, const std::vector<int8_t> *parity = nullptr) {
+        this->k = k_factor;
+        create_eo(mat, true, inner, parity);
+    }
+    LowPrecisionEvenOddGCR(Sparse<num_type> *mat, const GCR_Param<num_type> *inner, const std::vector<int8_t> *parity = nullptr) { create_eo(mat, false, inner, parity); }
+    struct EoInfo { int64_t n, n_even, n_odd; int32_t width_eo, width_oe; int64_t tail_rows_eo, tail_rows_oe; bool real_slab, has_diag; int64_t stored_bytes; };
+    EoInfo eo_info() {
+        EoInfo i{};
+        int32_t real = 0, diag = 0;
+        mgcr_detail::ok(mgcr_gcr32_eo_info(this->op, &i.n, &i.n_even, &i.n_odd, &i.width_eo, &i.width_oe, &i.tail_rows_eo, &i.tail_rows_oe, &real, &diag,
+                                           &i.stored_bytes), "LowPrecisionEvenOddGCR::eo_info");
+        i.real_slab = real != 0; i.has_diag = diag != 0;
+        return i;
+    }
+    // (n, n_even, n_odd)
+    std::vector<num_type> sizes() { const EoInfo i = eo_info(); return {(num_type)i.n, (num_type)i.n_even, (num_type)i.n_odd}; }
+    // a_even and 1 / a_odd in single precision, as the device holds them
+    void diag(std::vector<std::complex<float>> &a_even, std::vector<std::complex<float>> &inv_a_odd) {
+        const EoInfo i = eo_info();
+        a_even.resize((size_t)i.n_even); inv_a_odd.resize((size_t)i.n_odd);
+        mgcr_detail::ok(mgcr_gcr32_eo_diag(this->op, reinterpret_cast<float *>(a_even.data()), reinterpret_cast<float *>(inv_a_odd.data())),
+                        "LowPrecisionEvenOddGCR::diag");
+    }
+
+private:
+    void create_eo(Sparse<num_type> *mat, bool dirac, const GCR_Param<num_type> *inner, const std::vector<int8_t> *parity) {
+        mgcr_detail::ensure_init();
+        const num_type rows = mat->get_nrow();
+        if (parity && (num_type)parity->size() != rows) { std::fprintf(stderr, "LowPrecisionEvenOddGCR: parity has %zu entries, the matrix has %lld rows\n", parity->size(), (long long)rows); std::abort(); }
+        std::vector<int64_t> rp, ci;
+        std::vector<std::complex<double>> va;
+        this->host_csr(mat, rp, ci, va);
+        double v[2] = {this->k.real(), this->k.imag()};
+        mgcr_gcr_param p = this->cparam(inner);
+        mgcr_detail::ok(mgcr_gcr32_create_eo((int64_t)rows, rp.data(), ci.data(), reinterpret_cast<const double *>(va.data()), parity ? parity->data() : nullptr,
+                                             dirac ? v : nullptr, &p, &this->op), "LowPrecisionEvenOddGCR");
+        int64_t ne = 0;
+        mgcr_detail::ok(mgcr_gcr32_eo_info(this->op, nullptr, &ne, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "LowPrecisionEvenOddGCR");
+        this->dim = (num_type)ne;
+    }
 };
 
 // EvenOddDiracOp: the even-odd (red-black) preconditioned Id - k*D (extension, mgcr_eo_create) — an Operator on the EVEN half of the

@@ -168,6 +168,10 @@ _SIGS = {
     "mgcr_gcr32_info": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "mgcr_gcr32_apply_matrix": (C.c_int, [_vp, _vp, _vp]),
     "mgcr_gcr32_last": (C.c_int, [_vp, C.POINTER(C.c_int32), _dp]),
+    "mgcr_gcr32_create_eo": (C.c_int, [C.c_int64, _vp, _vp, _vp, _vp, _dp, C.POINTER(GcrParamC), C.POINTER(_vp)]),
+    "mgcr_gcr32_eo_info": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "mgcr_gcr32_eo_diag": (C.c_int, [_vp, _vp, _vp]),
     "mgcr_timer_start": (C.c_int, []),
     "mgcr_timer_stop": (C.c_int, [_dp]),
 }

@@ -934,6 +934,52 @@ class LowPrecisionGCR(Operator):
         return dict(n=n.value, ell_width=w.value, tail_rows=t.value, real_slab=bool(real.value), stored_bytes=b.value)
 
 
+class LowPrecisionEvenOddGCR(LowPrecisionGCR):
+    """Mixed precision on the even-odd Schur system: an fp32 copy of S = diag(a_e) - c^2 H_eo diag(1/a_o) H_oe of `mat` (a Sparse that
+    may store a site diagonal) and LowPrecisionGCR's inner solve on its n_e rows (mgcr_gcr32_create_eo).  k given: Dirac form, the
+    operator of EvenOddDiracOp / EvenOddDiagDiracOp; k None: matrix form, EvenOddSparse.  parity as theirs.  Its place is
+    GCR_Param(solver_r=..., flexible=True) of EvenOddDiracOp.solve or of a GCR on such an operator made from the same matrix and
+    parity.  set_k, set_param, apply_matrix and last are inherited."""
+
+    def __init__(self, mat, k=None, gcr_param=None, parity=None):
+        Operator.__init__(self)
+        _lib.init()
+        if gcr_param is None:
+            gcr_param = GCR_Param(0, 8, 8, 0.1, False)
+        self.param = gcr_param
+        self.k = None if k is None else complex(k)
+        n = int(mat.ROW.size - 1)
+        par = None if parity is None else np.ascontiguousarray(parity, np.int8)
+        if par is not None and par.size != n:
+            raise MgcrError(1, "LowPrecisionEvenOddGCR: parity has %d entries, the matrix has %d rows" % (par.size, n))
+        h = C.c_void_p()
+        pc = gcr_param._c()
+        check(_lib.lib().mgcr_gcr32_create_eo(n, mat.ROW.ctypes.data, mat.COL.ctypes.data, mat.VAL.ctypes.data,
+                                              par.ctypes.data if par is not None else None, _ri(k) if k is not None else None,
+                                              C.byref(pc), C.byref(h)))
+        self.h = h
+
+    def info(self):
+        n, ne, no, b, t0, t1 = (C.c_int64() for _ in range(6))
+        w0, w1, real, diag = (C.c_int32() for _ in range(4))
+        check(_lib.lib().mgcr_gcr32_eo_info(self.h, C.byref(n), C.byref(ne), C.byref(no), C.byref(w0), C.byref(w1), C.byref(t0), C.byref(t1),
+                                            C.byref(real), C.byref(diag), C.byref(b)))
+        return dict(n=n.value, n_even=ne.value, n_odd=no.value, width_eo=w0.value, width_oe=w1.value, tail_rows_eo=t0.value,
+                    tail_rows_oe=t1.value, real_slab=bool(real.value), has_diag=bool(diag.value), stored_bytes=b.value)
+
+    def sizes(self):
+        """(n, n_even, n_odd)"""
+        i = self.info()
+        return i["n"], i["n_even"], i["n_odd"]
+
+    def diag(self):
+        """(a_even, 1 / a_odd) in complex64, as the device holds them"""
+        _, ne, no = self.sizes()
+        a, inv = np.empty(ne, np.complex64), np.empty(no, np.complex64)
+        check(_lib.lib().mgcr_gcr32_eo_diag(self.h, a.ctypes.data, inv.ctypes.data))
+        return a, inv
+
+
 def legacy_dense_gcr(matrix, rhs, x, tol, max_iter, truncation, verbose=True):
     """GCR(matrix, dimension).solve(rhs, x, tol, max_iter, truncation) — the reference's legacy raw-pointer dense solve
     (src/GCR.h:70-156): r0 = rhs - A x (x0 honoured), directions truncated to the last `truncation`, stops when

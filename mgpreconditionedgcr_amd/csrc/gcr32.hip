@@ -18,49 +18,10 @@
 // unchanged partials and ends in the same way.  Nothing is exchanged inside a launch; no atomics, no waits.
 #include <cmath>
 
-#include "gcr32_plan.h"
-#include "internal.h"
-#include "reduce.h"
+#include "gcr32_row_dev.h"
+#include "gcr32_state.h"
 
 namespace mgcr {
-
-typedef float2 c32;
-constexpr int G32_TILE = RED_THREADS;   // rows per workgroup of the apply (one thread per row)
-
-struct G32Dev {
-    int stop_a;    // steps the solve was cut to by the tolerance (INT_MAX: running); written by the apply kernels only
-    int stop_u;    // ... by a zero <Ap, Ap>; written by the update kernels only
-    int n_iter;    // steps performed
-    double rel;    // fp32 |r| / |f| behind the last step (exit kernel)
-    double den[GCR32_MAX_RESTART];   // <Ap_j, Ap_j> of the stored directions
-};
-
-struct G32Mat {
-    const float *val;       // [W][npad] or [W][npad][2]
-    const int32_t *col;     // [W][npad], -1: padding
-    int64_t npad;
-    int32_t W;
-    const int32_t *tile_tail, *tail_rows, *tail_ptr, *tail_col;
-    const float *tail_val;
-};
-
-struct Gcr32State {
-    int64_t n = 0, nv = 0, nnz = 0, n_tail_rows = 0, stored_bytes = 0;
-    int32_t W = 0;
-    bool real = false, dirac = false;
-    double k_ri[2] = {0., 0.};
-    c32 k32 = {0.f, 0.f};
-    int restart = 0, max_iter = 0;
-    double tol = 0.;
-    float *val = nullptr, *tail_val = nullptr;
-    int32_t *col = nullptr, *tile_tail = nullptr, *tail_rows = nullptr, *tail_ptr = nullptr, *tail_col = nullptr;
-    int64_t npad = 0;
-    float *r = nullptr, *ar = nullptr, *x = nullptr, *ps = nullptr, *aps = nullptr;   // c32 vectors of nv elements; ps, aps: restart slots
-    double *S2 = nullptr;       // [2][RED_MAX_BLOCKS]: |f|^2, |r|^2
-    double *partsA = nullptr;   // [3][RED_MAX_BLOCKS]: <Ap, Ap>, <Ap, r>
-    double *partsB = nullptr;   // [2 * GCR32_MAX_RESTART][RED_MAX_BLOCKS]: <Ap_j, Ar>
-    G32Dev *st = nullptr;
-};
 
 // Counters on the device: {applies that ran, inner steps those enqueued}, bumped by the entry kernel's first thread — launches of one
 // stream, one writer.  An apply that an outer solve silences (SkipRef) or gates (Gcr32Gate) does not count.
@@ -80,21 +41,6 @@ void gcr32_release() {
     g_dev_counts = nullptr;
 }
 
-#define SKIP_ARGS const int *__restrict__ skip, int skip_it
-#define SKIP_RETURN() \
-    if (skip && skip[0] < skip[1] + skip_it) return
-
-// NV block sums into a partial slab, at most 16 scalars at a time (each scalar's tree is wave_sum's whatever the chunking)
-template <int NV, int OFF = 0>
-__device__ __forceinline__ void block_sums_to_slab(const double (&acc)[NV], double *lds, double *__restrict__ parts, int blk) {
-    constexpr int C = NV - OFF < 16 ? NV - OFF : 16;
-    double v[C];
-#pragma unroll
-    for (int j = 0; j < C; j++) v[j] = acc[OFF + j];
-    const double mine = block_sum_owner<C>(v, lds + OFF * 17);
-    if ((int)threadIdx.x < C) parts[(size_t)(OFF + threadIdx.x) * RED_MAX_BLOCKS + blk] = mine;
-    if constexpr (OFF + C < NV) block_sums_to_slab<NV, OFF + C>(acc, lds, parts, blk);
-}
 __device__ __forceinline__ float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 __device__ __forceinline__ double norm2d(float re, float im) { return (double)re * (double)re + (double)im * (double)im; }
 
@@ -163,41 +109,8 @@ __global__ void __launch_bounds__(RED_THREADS, (ND <= 5 ? 8 : 4))
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t row = tile * G32_TILE + threadIdx.x;
         if (row < n) {
-            float sx = 0.f, sy = 0.f;
-            for (int w = 0; w < A.W; w++) {
-                const int64_t at = (int64_t)w * A.npad + row;
-                const int32_t c = A.col[at];
-                if (c < 0) continue;
-                const c32 xv = r[c];
-                if (REAL) {
-                    const float a = A.val[at];
-                    sx += a * xv.x;
-                    sy += a * xv.y;
-                } else {
-                    const c32 a = reinterpret_cast<const c32 *>(A.val)[at];
-                    sx += a.x * xv.x - a.y * xv.y;
-                    sy += a.x * xv.y + a.y * xv.x;
-                }
-            }
-            const int t0 = A.tile_tail[tile], t1 = A.tile_tail[tile + 1];
-            for (int t = t0; t < t1; t++) {
-                if (A.tail_rows[t] != (int32_t)row) continue;
-                float ux = 0.f, uy = 0.f;   // the tail has an accumulator of its own
-                for (int e = A.tail_ptr[t]; e < A.tail_ptr[t + 1]; e++) {
-                    const c32 xv = r[A.tail_col[e]];
-                    if (REAL) {
-                        const float a = A.tail_val[e];
-                        ux += a * xv.x;
-                        uy += a * xv.y;
-                    } else {
-                        const c32 a = reinterpret_cast<const c32 *>(A.tail_val)[e];
-                        ux += a.x * xv.x - a.y * xv.y;
-                        uy += a.x * xv.y + a.y * xv.x;
-                    }
-                }
-                sx += ux;
-                sy += uy;
-            }
+            float sx, sy;
+            g32_row_sum<REAL>(A, r, tile, row, sx, sy);
             c32 y = make_float2(sx, sy);
             if (dirac) {   // y = x - k32 s
                 const c32 own = r[row];
@@ -379,27 +292,12 @@ __global__ void __launch_bounds__(RED_THREADS) g32_exit_kernel(const float *__re
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-template <typename T>
-static int g32_alloc(T **p, size_t count) {
-    hipError_t e = hipMalloc((void **)p, sizeof(T) * (count ? count : 1));
-    if (e != hipSuccess) {
-        set_error("hipMalloc of %zu bytes failed: %s", sizeof(T) * count, hipGetErrorString(e));
-        return MGCR_ERR_ALLOC;
-    }
-    return MGCR_OK;
-}
-template <typename T>
-static int g32_upload(T **p, const std::vector<T> &h) {
-    MGCR_TRY(g32_alloc(p, h.size()));
-    if (!h.empty()) MGCR_HIP(hipMemcpy(*p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-    return MGCR_OK;
-}
-
 void gcr32_destroy(Gcr32State *g) {
     if (!g) return;
     hipFree(g->val); hipFree(g->tail_val); hipFree(g->col); hipFree(g->tile_tail); hipFree(g->tail_rows); hipFree(g->tail_ptr); hipFree(g->tail_col);
     hipFree(g->r); hipFree(g->ar); hipFree(g->x); hipFree(g->ps); hipFree(g->aps);
     hipFree(g->S2); hipFree(g->partsA); hipFree(g->partsB); hipFree(g->st);
+    gcr32_eo_destroy(g->eo);
     delete g;
 }
 int64_t gcr32_nnz(const Gcr32State *g) { return g->nnz; }
@@ -415,7 +313,7 @@ static int g32_alloc_slots(Gcr32State *g, int restart) {
 }
 
 // the inner parameters: what the operator refuses (nothing is changed then)
-static int g32_check_param(const mgcr_gcr_param *p, const char *who) {
+int g32_check_param(const mgcr_gcr_param *p, const char *who) {
     MGCR_CHECK(p->truncation >= 0 && p->restart >= 0, MGCR_ERR_INVALID, "%s: negative GCR parameter", who);
     std::string err;
     if (!gcr32_param_ok(p->truncation, p->restart, p->max_iter, p->left_precond || p->right_precond, p->use_x0 != 0, p->flexible != 0,
@@ -428,7 +326,7 @@ static int g32_check_param(const mgcr_gcr_param *p, const char *who) {
     return MGCR_OK;
 }
 
-static int g32_check_k(const double k_ri[2], c32 *k32, const char *who) {
+int g32_check_k(const double k_ri[2], c32 *k32, const char *who) {
     MGCR_CHECK(k_ri[0] != 0. || k_ri[1] != 0., MGCR_ERR_INVALID, "%s: No k value supplied for Dirac Operator!", who);
     float re, im;
     MGCR_CHECK(gcr32_to_float(k_ri[0], &re) && gcr32_to_float(k_ri[1], &im), MGCR_ERR_INVALID, "%s: k is not finite in single precision", who);
@@ -440,7 +338,9 @@ static G32Mat g32_mat(const Gcr32State *g) {
     return G32Mat{g->val, g->col, g->npad, g->W, g->tile_tail, g->tail_rows, g->tail_ptr, g->tail_col, g->tail_val};
 }
 
+// "the apply of this operator": Ar = A32 r and the partials of <Ap_j, Ar> — one launch for the square form, two for the even-odd one
 static int g32_launch_apply(Gcr32State *g, int nd, int it, SkipRef sk) {
+    if (g->eo) return gcr32_eo_launch_apply(g, nd, it, sk);
     const int ga = red_grid(g->n), gs = red_grid(g->n >> 1);
     const double tol2 = g->tol * g->tol;
     return dispatch_bool(g->real, [&](auto real) {
@@ -487,8 +387,29 @@ int gcr32_slot_check(const mgcr_gcr_param *p, const Op *A) {
                    "a low-precision GCR cannot precondition a distributed operator");
         MGCR_CHECK(A->dim == r->dim, MGCR_ERR_INVALID, "the low-precision GCR has %lld rows, the operator of the solve %lld", (long long)r->dim,
                    (long long)A->dim);
+        if (r->g32->eo) MGCR_TRY(gcr32_eo_slot_check(r->g32->eo, A));
     }
     return MGCR_OK;
+}
+
+// r, Ar, x, the restart slots, the partial slabs, the state words and — with the first operator — the library's two counters
+int g32_alloc_iteration(Gcr32State *g) {
+    int rc = MGCR_OK;
+    if (rc == MGCR_OK) rc = g32_alloc(&g->r, (size_t)2 * g->nv);
+    if (rc == MGCR_OK) rc = g32_alloc(&g->ar, (size_t)2 * g->nv);
+    if (rc == MGCR_OK) rc = g32_alloc(&g->x, (size_t)2 * g->nv);
+    if (rc == MGCR_OK) rc = g32_alloc_slots(g, g->restart);
+    if (rc == MGCR_OK) rc = g32_alloc(&g->S2, (size_t)2 * RED_MAX_BLOCKS);
+    if (rc == MGCR_OK) rc = g32_alloc(&g->partsA, (size_t)3 * RED_MAX_BLOCKS);
+    if (rc == MGCR_OK) rc = g32_alloc(&g->partsB, (size_t)2 * GCR32_MAX_RESTART * RED_MAX_BLOCKS);
+    if (rc == MGCR_OK) rc = g32_alloc(&g->st, 1);
+    if (rc == MGCR_OK && hipMemset(g->st, 0, sizeof(G32Dev)) != hipSuccess) rc = MGCR_ERR_HIP;
+    if (rc == MGCR_OK && !g_dev_counts) {   // the library's two device-side counters: made with the first operator, zeroed on the library's stream
+        rc = g32_alloc(&g_dev_counts, 2);
+        if (rc == MGCR_OK && hipMemsetAsync(g_dev_counts, 0, 2 * sizeof(long long), ctx().stream) != hipSuccess) rc = MGCR_ERR_HIP;
+    }
+    if (rc == MGCR_OK && hipDeviceSynchronize() != hipSuccess) rc = MGCR_ERR_HIP;   // (the memset above went to the null stream)
+    return rc;
 }
 
 }  // namespace mgcr
@@ -527,20 +448,7 @@ int mgcr_gcr32_create(int64_t n, const int64_t *rowptr, const int64_t *col, cons
     if (rc == MGCR_OK) rc = g32_upload(&g->tail_ptr, plan.tail_ptr);
     if (rc == MGCR_OK) rc = g32_upload(&g->tail_col, plan.tail_col);
     if (rc == MGCR_OK) rc = g32_upload(&g->tail_val, plan.tail_val);
-    if (rc == MGCR_OK) rc = g32_alloc(&g->r, (size_t)2 * g->nv);
-    if (rc == MGCR_OK) rc = g32_alloc(&g->ar, (size_t)2 * g->nv);
-    if (rc == MGCR_OK) rc = g32_alloc(&g->x, (size_t)2 * g->nv);
-    if (rc == MGCR_OK) rc = g32_alloc_slots(g, g->restart);
-    if (rc == MGCR_OK) rc = g32_alloc(&g->S2, (size_t)2 * RED_MAX_BLOCKS);
-    if (rc == MGCR_OK) rc = g32_alloc(&g->partsA, (size_t)3 * RED_MAX_BLOCKS);
-    if (rc == MGCR_OK) rc = g32_alloc(&g->partsB, (size_t)2 * GCR32_MAX_RESTART * RED_MAX_BLOCKS);
-    if (rc == MGCR_OK) rc = g32_alloc(&g->st, 1);
-    if (rc == MGCR_OK && hipMemset(g->st, 0, sizeof(G32Dev)) != hipSuccess) rc = MGCR_ERR_HIP;
-    if (rc == MGCR_OK && !g_dev_counts) {   // the library's two device-side counters: made with the first operator, zeroed on the library's stream
-        rc = g32_alloc(&g_dev_counts, 2);
-        if (rc == MGCR_OK && hipMemsetAsync(g_dev_counts, 0, 2 * sizeof(long long), ctx().stream) != hipSuccess) rc = MGCR_ERR_HIP;
-    }
-    if (rc == MGCR_OK && hipDeviceSynchronize() != hipSuccess) rc = MGCR_ERR_HIP;   // (the memset above went to the null stream)
+    if (rc == MGCR_OK) rc = g32_alloc_iteration(g);
     if (rc != MGCR_OK) { gcr32_destroy(g); return rc; }
     mgcr_op_s *op = new mgcr_op_s();
     op->kind = OP_GCR32;
@@ -559,6 +467,7 @@ int mgcr_gcr32_set_k(mgcr_op_t op, const double k_ri[2]) {
     c32 k32;
     MGCR_TRY(g32_check_k(k_ri, &k32, who));
     LOCK();
+    if (op->g32->eo) MGCR_TRY(gcr32_eo_set_k(op->g32, k_ri, who));   // a and 1 / a_o follow k; refused: nothing changes
     op->g32->k_ri[0] = k_ri[0]; op->g32->k_ri[1] = k_ri[1];
     op->g32->k32 = k32;
     return MGCR_OK;
@@ -582,6 +491,7 @@ int mgcr_gcr32_set_param(mgcr_op_t op, const mgcr_gcr_param *inner) {
 int mgcr_gcr32_info(mgcr_op_t op, int64_t *n, int32_t *ell_width, int64_t *tail_rows, int32_t *real_slab, int64_t *stored_bytes) {
     G32_CHECK(op, "mgcr_gcr32_info");
     const Gcr32State *g = op->g32;
+    MGCR_CHECK(!g->eo, MGCR_ERR_UNSUPPORTED, "mgcr_gcr32_info: the operator is in even-odd form and has two slabs: ask mgcr_gcr32_eo_info");
     if (n) *n = g->n;
     if (ell_width) *ell_width = g->W;
     if (tail_rows) *tail_rows = g->n_tail_rows;

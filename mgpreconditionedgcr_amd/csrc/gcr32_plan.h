@@ -41,12 +41,16 @@ inline bool gcr32_to_float(double v, float *out) {
     return std::isfinite(v) && std::isfinite(f);
 }
 
-// false: *err says why (inconsistent CSR, non-square, a value out of float's range)
+// false: *err says why (inconsistent CSR, non-square, a value out of float's range).  ncol: the column count of a rectangular
+// matrix — a half of the even-odd form (gcr32_eo_plan.h) —, default: square; force_complex: a complex slab whatever the values
+// (the two halves of one operator share one kernel form)
 inline bool gcr32_plan_build(int64_t n, const int64_t *rowptr, const int64_t *col, const double *val_ri, int32_t tile_rows, Gcr32Plan *out,
-                             std::string *err) {
+                             std::string *err, int64_t ncol = -1, bool force_complex = false) {
     Gcr32Plan &p = *out;
     p = Gcr32Plan();
-    if (n < 0 || n >= ((int64_t)1 << 31)) { *err = "the dimension must fit int32 (got " + std::to_string((long long)n) + ")"; return false; }
+    const bool square = ncol < 0;
+    if (square) ncol = n;
+    if (n < 0 || n >= ((int64_t)1 << 31) || ncol >= ((int64_t)1 << 31)) { *err = "the dimension must fit int32 (got " + std::to_string((long long)(n > ncol ? n : ncol)) + ")"; return false; }
     if (rowptr[0] != 0) { *err = "inconsistent CSR: rowptr[0] != 0"; return false; }
     int64_t maxlen = 0;
     for (int64_t i = 0; i < n; i++) {
@@ -56,12 +60,12 @@ inline bool gcr32_plan_build(int64_t n, const int64_t *rowptr, const int64_t *co
     }
     const int64_t nnz = rowptr[n];
     if (nnz >= ((int64_t)1 << 31) || maxlen >= ((int64_t)1 << 30)) { *err = "the entry count must fit int32"; return false; }
-    bool real = true;
+    bool real = !force_complex;
     for (int64_t i = 0; i < n; i++)
         for (int64_t e = rowptr[i]; e < rowptr[i + 1]; e++) {
-            if (col[e] < 0 || col[e] >= n) {
-                *err = "row " + std::to_string((long long)i) + " has column " + std::to_string((long long)col[e]) + ": the matrix must be square, " +
-                       std::to_string((long long)n) + " x " + std::to_string((long long)n);
+            if (col[e] < 0 || col[e] >= ncol) {
+                *err = "row " + std::to_string((long long)i) + " has column " + std::to_string((long long)col[e]) + ": the matrix must be " +
+                       (square ? "square, " : "") + std::to_string((long long)n) + " x " + std::to_string((long long)ncol);
                 return false;
             }
             float re, im;
