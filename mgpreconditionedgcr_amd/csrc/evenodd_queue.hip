@@ -21,10 +21,10 @@ namespace mgcr {
 //                            for a half with a CSR tail) — a column not admitted is computed on what its slot holds; nothing of it
 //                            is stored
 //     eoq_copy_kernel        the admitted columns of W_BHAT -> the b block and, without x0, r and P0
-//     then the queue's own admission: with x0 the Schur apply of the x block and q_r0_kernel; the Schur apply of r, q_admit_kernel,
-//     q_admit_state_kernel.  In all 4 (5 with x0) passes and 1 shifted D_eo + 1 (2) Schur applies.
+//     then the queue's own admission: with x0 the Schur apply of the x block and q_r0_kernel; the Schur apply of r,
+//     m_init_partials_kernel<KC, true>, q_admit_state_kernel.  In all 4 (5 with x0) passes and 1 shifted D_eo + 1 (2) Schur applies.
 //   retirement point (mask = the slots found stopped):
-//     hq_retire_kernel  the pending x updates of the retiring columns -> W_XE (gcr_multi.hip: the expression of q_retire_kernel)
+//     m_pending_x_kernel<KC, XBlock>  the pending x updates of the retiring columns -> W_XE (gcr_multi.hip: its work-block sink)
 //     eom_shift_apply(D_oe)  W_XO = W_BO - (-k_j) D_oe W_XE, all W columns (one launch, two with a tail)
 //     eoq_scatter_kernel     the retiring columns of W_XE and W_XO -> the systems' full Fields, through even[] / odd[]
 // W_BO is the block of the b_o in flight: column j is written when slot j is admitted and read when it retires.

@@ -38,16 +38,24 @@ __device__ __forceinline__ bool m_active(const DevState *st, int col, int k, int
     return col < k && !(st[col].stop_at < st[col].base + it);
 }
 
-// The queued solve (gcr_queue_run) admits columns at different steps, so a column's LAST step (own step number == max_iter) is not the
-// launch's: such a column takes the finishing bookkeeping (q_finish_kernel, which freezes it with stop_at == its step number) while
-// its neighbours run a full step, and the kernels behind that bookkeeping — coefficients, closing x update, build — must leave it
-// alone although stop_at == base + it reads as active.  Those three have q_ TWINS (q_coef_kernel, q_build_kernel, q_close_x_kernel):
-// the m_ kernel with this test in place of m_active.  A change to the arithmetic of either twin belongs in both — the bit-for-bit
-// rule ties solve_multi and solve_queue to the same single solve.  They are copies because a body shared through an inlined
-// __device__ function compiles to other code for the m_ entries (the work-group size is then looked up, not assumed).
-__device__ __forceinline__ bool q_active(const DevState *st, int col, int k, int it, int max_it) {
-    return m_active(st, col, k, it) && st[col].base + it < max_it;
+// QUEUED: the kernel serves the queued solve (gcr_queue_run), true, or the batched one (gcr_multi_run), false.  The queued solve
+// admits columns at different steps, so a column's LAST step (own step number == max_it) is not the launch's: such a column takes the
+// finishing bookkeeping (m_finish_kernel<true>, which freezes it with stop_at == its step number) while its neighbours run a full
+// step, and the kernels behind that bookkeeping — coefficients, closing x update, build — must leave it alone although
+// stop_at == base + it reads as active.  That test is all QUEUED changes in them, so both solves run ONE body and the bit-for-bit
+// rule needs no second copy.  The flag sits on the __global__ function itself (max_it is read by the QUEUED forms only): each
+// instantiation then compiles to the code of a kernel written out for it, whereas a body shared through an inlined __device__
+// function compiles to other code for the batched entries (the work-group size is then looked up, not assumed).
+template <bool QUEUED>
+__device__ __forceinline__ bool col_active(const DevState *st, int col, int k, int it, int max_it) {
+    if constexpr (QUEUED) return m_active(st, col, k, it) && st[col].base + it < max_it;
+    else return m_active(st, col, k, it);
 }
+
+struct QFields {   // queued solve, per column: the system's Fields (by value in the kernel arguments)
+    const cplx *b[MV_MAX_K];
+    cplx *x[MV_MAX_K];
+};
 
 __global__ void m_reset_kernel(DevState *st, double tol2, int k) {
     const int j = threadIdx.x;
@@ -62,13 +70,19 @@ __global__ void m_reset_kernel(DevState *st, double tol2, int k) {
     st[j].closed = 0;
 }
 
-// |b|^2, |r|^2, <r,Ap>, <Ap,Ap> per column in one pass (norm_partials_kernel, norm_partials_kernel, dot2_partials_kernel)
-template <int KC>
+// |b|^2, |r|^2, <r,Ap>, <Ap,Ap> per column in one pass (norm_partials_kernel, norm_partials_kernel, dot2_partials_kernel).
+// QUEUED: pass 2 of an admission point (`mask`: bit j = column j is admitted).  Only the admitted columns take part — a continuing
+// column's sums (the closing step's build wrote them) stay — and ap, which the k-wide apply left in the `ar` block, goes into
+// slot 0 (ap0) of the admitted columns on the way.
+template <int KC, bool QUEUED>
 __global__ void __launch_bounds__(RED_THREADS) m_init_partials_kernel(const cplx *__restrict__ b, const cplx *__restrict__ r,
                                                                       const cplx *__restrict__ ap, int64_t n, int k, double *__restrict__ partsN,
-                                                                      double *__restrict__ partsR, double *__restrict__ partsA) {
+                                                                      double *__restrict__ partsR, double *__restrict__ partsA, unsigned mask,
+                                                                      cplx *__restrict__ ap0) {
     __shared__ double lds[6 * KC * 17];
     const int c0 = (int)blockIdx.y * KC;
+    if constexpr (QUEUED)
+        if (((mask >> c0) & ((1u << KC) - 1u)) == 0) return;   // (uniform over the workgroup)
     double v[6 * KC];
 #pragma unroll
     for (int s = 0; s < 6 * KC; s++) v[s] = 0.;
@@ -79,6 +93,8 @@ __global__ void __launch_bounds__(RED_THREADS) m_init_partials_kernel(const cplx
         mv_load<KC>(ap, i, k, c0, av);
 #pragma unroll
         for (int c = 0; c < KC; c++) {
+            if constexpr (QUEUED)
+                if (c0 + c < k && ((mask >> (c0 + c)) & 1u)) ap0[i * k + c0 + c] = av[c];
             v[6 * c + 4] += bv[c].x * bv[c].x + bv[c].y * bv[c].y;
             v[6 * c + 5] += rv[c].x * rv[c].x + rv[c].y * rv[c].y;
             const cplx t = cconj_mul(rv[c], av[c]);
@@ -91,7 +107,7 @@ __global__ void __launch_bounds__(RED_THREADS) m_init_partials_kernel(const cplx
     const int t = (int)threadIdx.x;
     if (t < 6 * KC) {
         const int col = c0 + t / 6, s = t % 6;
-        if (col < k) {
+        if (col < k && (!QUEUED || ((mask >> col) & 1u))) {
             if (s < 4) partsA[(size_t)(col * 4 + s) * RED_MAX_BLOCKS + blockIdx.x] = tot;
             else if (s == 4) partsN[(size_t)col * RED_MAX_BLOCKS + blockIdx.x] = tot;
             else partsR[(size_t)col * RED_MAX_BLOCKS + blockIdx.x] = tot;
@@ -168,15 +184,22 @@ __global__ void __launch_bounds__(RED_THREADS) m_xr_kernel(const DevState *__res
     if (t < KC && m_active(st, c0 + t, k, it)) partsR[(size_t)(c0 + t) * RED_MAX_BLOCKS + blockIdx.x] = tot;
 }
 
-// the last step a solve can run: bookkeeping only (finish_step_kernel)
+// the last step a solve can run: bookkeeping only (finish_step_kernel).  QUEUED: for the columns at their OWN last step, which are
+// then frozen
+template <bool QUEUED>
 __global__ void __launch_bounds__(RED_THREADS) m_finish_kernel(DevState *st, int it, const double *__restrict__ partsR, int nblk,
-                                                               double *__restrict__ hist, int hist_cap) {
+                                                               double *__restrict__ hist, int hist_cap, int max_it) {
     __shared__ double lds[17];
     const int j = blockIdx.x;
     if (st[j].stop_at < st[j].base + it) return;
+    if constexpr (QUEUED)
+        if (st[j].base + it != max_it) return;
     double rr[1];
     fold_partials<1>(partsR + (size_t)j * RED_MAX_BLOCKS, nblk, RED_MAX_BLOCKS, rr, lds);
-    if (threadIdx.x == 0) close_step(st + j, it, rr[0], hist + (size_t)j * hist_cap, hist_cap, false);
+    if (threadIdx.x == 0) {
+        close_step(st + j, it, rr[0], hist + (size_t)j * hist_cap, hist_cap, false);
+        if constexpr (QUEUED) st[j].stop_at = st[j].base + it;
+    }
 }
 
 // <Ar, Ap_d> (conj on Ar) for the NDT directions of chunk blockIdx.z and the KC columns of group blockIdx.y; rows dealt by the
@@ -216,54 +239,20 @@ __global__ void __launch_bounds__(RED_THREADS) m_dot_kernel(const cplx *__restri
     }
 }
 
-// (twin: q_coef_kernel below)
 // the prologue of build_lean_kernel / build_close_kernel, one workgroup per column: betas, the step's bookkeeping, and either
 // row `lim` of the coefficient table (in-cycle step) or the closing coefficients cp
+template <bool QUEUED>
 __global__ void __launch_bounds__(RED_THREADS) m_coef_kernel(DevState *st, int it, const double *__restrict__ partsB, const double *__restrict__ partsR,
-                                                             int nblk, double *__restrict__ hist, int hist_cap, const cplx *__restrict__ den,
-                                                             LeanCoef *__restrict__ lcs, MCoef *__restrict__ coef, int lim, int closing) {
-    __shared__ double lds[2 * 17];
-    __shared__ cplx sbeta[LND];
-    const int j = blockIdx.x;
-    if (st[j].stop_at < st[j].base + it) return;
-    LeanCoef *lc = lcs + j;
-    for (int d = 0; d < lim; d++) {
-        double s[2];
-        fold_partials<2>(partsB + (size_t)((j * LND + d) * 2) * RED_MAX_BLOCKS, nblk, RED_MAX_BLOCKS, s, lds);
-        if (threadIdx.x == 0) sbeta[d] = cdiv(make_double2(s[0], s[1]), den[j * LND + d]);
-    }
-    double rr[1];
-    fold_partials<1>(partsR + (size_t)j * RED_MAX_BLOCKS, nblk, RED_MAX_BLOCKS, rr, lds);
-    if (threadIdx.x == 0) close_step(st + j, it, rr[0], hist + (size_t)j * hist_cap, hist_cap, closing != 0);
-    __syncthreads();
-    const int m = threadIdx.x;
-    if (m < lim) coef->beta[j][m] = sbeta[m];
-    if (!closing) {
-        if (lim < LND && m <= lim) {   // table row k = lim (build_lean_kernel)
-            const int kk = lim;
-            cplx a = make_double2(0., 0.);
-            if (m == 0) {
-                for (int q = 0; q < kk; q++) a = csub(a, cmul(sbeta[q], q == 0 ? make_double2(1., 0.) : lc->t[q]));
-                lc->t[kk] = a;
-            } else if (m < kk) {
-                for (int q = m; q < kk; q++) a = csub(a, cmul(sbeta[q], q == m ? make_double2(1., 0.) : lc->T[q * LND + m]));
-                lc->T[kk * LND + m] = a;
-            } else {
-                lc->T[kk * LND + kk] = make_double2(1., 0.);
-            }
-        }
-    } else if (m < lim) {              // cp (build_close_kernel / close_x_kernel)
-        coef->cp[j][m] = lean_close_coef(lc, sbeta, lim, m);
-    }
-}
-// ... in the queued solve (the same kernel but for the test of the column's own last step)
-__global__ void __launch_bounds__(RED_THREADS) q_coef_kernel(DevState *st, int it, const double *__restrict__ partsB, const double *__restrict__ partsR,
                                                              int nblk, double *__restrict__ hist, int hist_cap, const cplx *__restrict__ den,
                                                              LeanCoef *__restrict__ lcs, MCoef *__restrict__ coef, int lim, int closing, int max_it) {
     __shared__ double lds[2 * 17];
     __shared__ cplx sbeta[LND];
     const int j = blockIdx.x;
-    if (!q_active(st, j, (int)gridDim.x, it, max_it)) return;   // stopped, or at its own last step: q_finish_kernel has done the bookkeeping
+    if constexpr (QUEUED) {   // stopped, or at its own last step: m_finish_kernel<true> has done the bookkeeping
+        if (!col_active<true>(st, j, (int)gridDim.x, it, max_it)) return;
+    } else {   // one workgroup per column, so j < k: col_active<false> would add m_active's column test to this form's instructions
+        if (st[j].stop_at < st[j].base + it) return;
+    }
     LeanCoef *lc = lcs + j;
     for (int d = 0; d < lim; d++) {
         double s[2];
@@ -294,57 +283,10 @@ __global__ void __launch_bounds__(RED_THREADS) q_coef_kernel(DevState *st, int i
         coef->cp[j][m] = lean_close_coef(lc, sbeta, lim, m);
     }
 }
-
-// (twin: q_build_kernel below)
 // Ap' = Ar - sum_d beta_d Ap_d (d ascending) with the <r,Ap'>, <Ap',Ap'> partials: the loop of build_lean_kernel.  ap_out may be
 // slot 0 itself (closing step): a thread reads its rows of every slot before it writes.
-template <int KC>
+template <int KC, bool QUEUED>
 __global__ void __launch_bounds__(RED_THREADS) m_build_kernel(const DevState *__restrict__ st, int it, const MCoef *__restrict__ coef, MPtrs d, int lim,
-                                                              const cplx *r, const cplx *ar, cplx *ap_out, int64_t n, int k,
-                                                              double *__restrict__ partsA) {
-    __shared__ double lds[4 * KC * 17];
-    const int c0 = (int)blockIdx.y * KC;
-    bool act[KC];
-    bool any = false;
-#pragma unroll
-    for (int c = 0; c < KC; c++) {
-        act[c] = m_active(st, c0 + c, k, it);
-        any = any || act[c];
-    }
-    if (!any) return;
-    double v[4 * KC];
-#pragma unroll
-    for (int s = 0; s < 4 * KC; s++) v[s] = 0.;
-    MV_GRID_STRIDE(i, n) {
-        cplx av[KC], rv[KC], ac[KC];
-        mv_load<KC>(ar, i, k, c0, av);
-        mv_load<KC>(r, i, k, c0, rv);
-#pragma unroll
-        for (int c = 0; c < KC; c++) ac[c] = make_double2(0., 0.);
-        for (int q = 0; q < lim; q++) {
-            cplx aj[KC];
-            mv_load<KC>(d.aps[q], i, k, c0, aj);
-#pragma unroll
-            for (int c = 0; c < KC; c++)
-                if (c0 + c < k) ac[c] = csub(ac[c], cmul(coef->beta[c0 + c][q], aj[c]));
-        }
-#pragma unroll
-        for (int c = 0; c < KC; c++) {
-            const cplx an = cadd(av[c], ac[c]);
-            if (act[c]) ap_out[i * k + c0 + c] = an;
-            const cplx t = cconj_mul(rv[c], an);
-            v[4 * c] += t.x; v[4 * c + 1] += t.y;
-            const cplx u = cconj_mul(an, an);
-            v[4 * c + 2] += u.x; v[4 * c + 3] += u.y;
-        }
-    }
-    const double tot = block_sum_owner<4 * KC>(v, lds);
-    const int t = (int)threadIdx.x;
-    if (t < 4 * KC && m_active(st, c0 + t / 4, k, it)) partsA[(size_t)((c0 + t / 4) * 4 + (t & 3)) * RED_MAX_BLOCKS + blockIdx.x] = tot;
-}
-// ... in the queued solve
-template <int KC>
-__global__ void __launch_bounds__(RED_THREADS) q_build_kernel(const DevState *__restrict__ st, int it, const MCoef *__restrict__ coef, MPtrs d, int lim,
                                                               const cplx *r, const cplx *ar, cplx *ap_out, int64_t n, int k,
                                                               double *__restrict__ partsA, int max_it) {
     __shared__ double lds[4 * KC * 17];
@@ -353,7 +295,7 @@ __global__ void __launch_bounds__(RED_THREADS) q_build_kernel(const DevState *__
     bool any = false;
 #pragma unroll
     for (int c = 0; c < KC; c++) {
-        act[c] = q_active(st, c0 + c, k, it, max_it);
+        act[c] = col_active<QUEUED>(st, c0 + c, k, it, max_it);
         any = any || act[c];
     }
     if (!any) return;
@@ -385,52 +327,12 @@ __global__ void __launch_bounds__(RED_THREADS) q_build_kernel(const DevState *__
     }
     const double tot = block_sum_owner<4 * KC>(v, lds);
     const int t = (int)threadIdx.x;
-    if (t < 4 * KC && q_active(st, c0 + t / 4, k, it, max_it)) partsA[(size_t)((c0 + t / 4) * 4 + (t & 3)) * RED_MAX_BLOCKS + blockIdx.x] = tot;
+    if (t < 4 * KC && col_active<QUEUED>(st, c0 + t / 4, k, it, max_it)) partsA[(size_t)((c0 + t / 4) * 4 + (t & 3)) * RED_MAX_BLOCKS + blockIdx.x] = tot;
 }
-
-// (twin: q_close_x_kernel below)
 // the x / P0 half of the step that closes a cycle (close_x_kernel): x += sum_m cx_m (P0, D_1 ..), P0' = dir - sum_m cp_m (P0, D_1 ..),
 // written over slot 0.  No sums: 256-thread workgroups.
-template <int KC>
+template <int KC, bool QUEUED>
 __global__ void __launch_bounds__(256) m_close_x_kernel(const DevState *__restrict__ st, int it, const MCoef *__restrict__ coef,
-                                                        const LeanCoef *__restrict__ lc, MPtrs d, int lim, const cplx *dir, cplx *p_out, cplx *x,
-                                                        int64_t n, int k) {
-    const int c0 = (int)blockIdx.y * KC;
-    bool act[KC];
-    bool any = false;
-#pragma unroll
-    for (int c = 0; c < KC; c++) {
-        act[c] = m_active(st, c0 + c, k, it);
-        any = any || act[c];
-    }
-    if (!any) return;
-    MV_GRID_STRIDE(i, n) {
-        cplx xv[KC], dv[KC], pc[KC];
-        mv_load<KC>(x, i, k, c0, xv);
-        mv_load<KC>(dir, i, k, c0, dv);
-#pragma unroll
-        for (int c = 0; c < KC; c++) pc[c] = make_double2(0., 0.);
-        for (int q = 0; q < lim; q++) {
-            cplx pj[KC];
-            mv_load<KC>(d.ps[q], i, k, c0, pj);
-#pragma unroll
-            for (int c = 0; c < KC; c++)
-                if (c0 + c < k) {
-                    xv[c] = cadd(xv[c], cmul(lc[c0 + c].cx[q], pj[c]));
-                    pc[c] = csub(pc[c], cmul(coef->cp[c0 + c][q], pj[c]));
-                }
-        }
-#pragma unroll
-        for (int c = 0; c < KC; c++)
-            if (act[c]) {
-                x[i * k + c0 + c] = xv[c];
-                p_out[i * k + c0 + c] = cadd(dv[c], pc[c]);
-            }
-    }
-}
-// ... in the queued solve
-template <int KC>
-__global__ void __launch_bounds__(256) q_close_x_kernel(const DevState *__restrict__ st, int it, const MCoef *__restrict__ coef,
                                                         const LeanCoef *__restrict__ lc, MPtrs d, int lim, const cplx *dir, cplx *p_out, cplx *x,
                                                         int64_t n, int k, int max_it) {
     const int c0 = (int)blockIdx.y * KC;
@@ -438,7 +340,7 @@ __global__ void __launch_bounds__(256) q_close_x_kernel(const DevState *__restri
     bool any = false;
 #pragma unroll
     for (int c = 0; c < KC; c++) {
-        act[c] = q_active(st, c0 + c, k, it, max_it);
+        act[c] = col_active<QUEUED>(st, c0 + c, k, it, max_it);
         any = any || act[c];
     }
     if (!any) return;
@@ -466,20 +368,46 @@ __global__ void __launch_bounds__(256) q_close_x_kernel(const DevState *__restri
             }
     }
 }
+// Where m_pending_x_kernel puts a column's x.  XFlush: back into the x block, at the end of the batched solve — every column takes
+// part, and one without pending updates is not written.  The queued solve's retirement (`mask`: bit j = column j retires) writes
+// every retiring column, pending updates or not: XFields into the system's Field, XBlock into column j of a work block, for a
+// queue whose systems are not whole Fields (QueueHooks: the even-odd queue), from where the hooks take it.  The x block's column
+// is then left as it is: nothing reads it again, so the pending updates cannot be applied twice.
+struct XFlush {
+    static constexpr bool MASKED = false;
+    cplx *x;
+    __device__ void put(int64_t i, int k, int col, cplx v) const { x[i * k + col] = v; }
+};
+struct XFields {
+    static constexpr bool MASKED = true;
+    QFields f;
+    __device__ void put(int64_t i, int, int col, cplx v) const { f.x[col][i] = v; }
+};
+struct XBlock {
+    static constexpr bool MASKED = true;
+    cplx *__restrict__ out;
+    __device__ void put(int64_t i, int k, int col, cplx v) const { out[i * k + col] = v; }
+};
 
-// the x updates still pending when the solve ends (flush_x_kernel): per column its own count; never skipped
-template <int KC>
-__global__ void __launch_bounds__(256) m_flush_kernel(const DevState *__restrict__ st, const LeanCoef *__restrict__ lc, MPtrs d, cplx *x, int64_t n, int k) {
+// x_j + the x updates still pending for column j (flush_x_kernel): per column its own count; never skipped
+template <int KC, typename SINK>
+__global__ void __launch_bounds__(256) m_pending_x_kernel(unsigned mask, const DevState *__restrict__ st, const LeanCoef *__restrict__ lc, MPtrs d,
+                                                          const cplx *x, SINK to, int64_t n, int k) {
     const int c0 = (int)blockIdx.y * KC;
+    if constexpr (SINK::MASKED)
+        if (((mask >> c0) & ((1u << KC) - 1u)) == 0) return;
+    bool sel[KC];
     int np[KC];
     int npmax = 0;
 #pragma unroll
     for (int c = 0; c < KC; c++) {
-        np[c] = c0 + c < k ? st[c0 + c].npend : 0;
+        sel[c] = c0 + c < k && (!SINK::MASKED || ((mask >> (c0 + c)) & 1u));
+        np[c] = sel[c] ? st[c0 + c].npend : 0;
         if (np[c] > LND) np[c] = LND;
         npmax = np[c] > npmax ? np[c] : npmax;
     }
-    if (npmax <= 0) return;
+    if constexpr (!SINK::MASKED)
+        if (npmax <= 0) return;
     MV_GRID_STRIDE(i, n) {
         cplx xv[KC];
         mv_load<KC>(x, i, k, c0, xv);
@@ -492,7 +420,7 @@ __global__ void __launch_bounds__(256) m_flush_kernel(const DevState *__restrict
         }
 #pragma unroll
         for (int c = 0; c < KC; c++)
-            if (np[c] > 0) x[i * k + c0 + c] = xv[c];
+            if (SINK::MASKED ? sel[c] : np[c] > 0) to.put(i, k, c0 + c, xv[c]);
     }
 }
 
@@ -502,93 +430,9 @@ __global__ void __launch_bounds__(RED_THREADS) m_resid_sub_kernel(cplx *r, const
 }
 
 // ------------------------------------------------------------------------------------------------
-// queued solve: retire / admit single columns of the block (gcr_queue_run).  `mask`: bit j = column j takes part
+// queued solve: admit single columns of the block (gcr_queue_run; pass 2 is m_init_partials_kernel<KC, true>).  `mask`: bit j =
+// column j takes part
 // ------------------------------------------------------------------------------------------------
-struct QFields {   // per column: the system's Fields (by value in the kernel arguments)
-    const cplx *b[MV_MAX_K];
-    cplx *x[MV_MAX_K];
-};
-
-// a column's own last step: the bookkeeping of m_finish_kernel, then the column is frozen
-__global__ void __launch_bounds__(RED_THREADS) q_finish_kernel(DevState *st, int it, int max_it, const double *__restrict__ partsR, int nblk,
-                                                               double *__restrict__ hist, int hist_cap) {
-    __shared__ double lds[17];
-    const int j = blockIdx.x;
-    if (st[j].stop_at < st[j].base + it || st[j].base + it != max_it) return;
-    double rr[1];
-    fold_partials<1>(partsR + (size_t)j * RED_MAX_BLOCKS, nblk, RED_MAX_BLOCKS, rr, lds);
-    if (threadIdx.x == 0) {
-        close_step(st + j, it, rr[0], hist + (size_t)j * hist_cap, hist_cap, false);
-        st[j].stop_at = st[j].base + it;
-    }
-}
-
-// retire: x_s = column j of the x block + the column's pending updates (the expression of m_flush_kernel), written to the system's
-// Field.  The block's column is left as it is: nothing reads it again, so the pending updates cannot be applied twice.
-template <int KC>
-__global__ void __launch_bounds__(256) q_retire_kernel(unsigned mask, const DevState *__restrict__ st, const LeanCoef *__restrict__ lc, MPtrs d,
-                                                       const cplx *__restrict__ x, QFields f, int64_t n, int k) {
-    const int c0 = (int)blockIdx.y * KC;
-    if (((mask >> c0) & ((1u << KC) - 1u)) == 0) return;
-    bool ret[KC];
-    int np[KC];
-    int npmax = 0;
-#pragma unroll
-    for (int c = 0; c < KC; c++) {
-        ret[c] = c0 + c < k && ((mask >> (c0 + c)) & 1u);
-        np[c] = ret[c] ? st[c0 + c].npend : 0;
-        if (np[c] > LND) np[c] = LND;
-        npmax = np[c] > npmax ? np[c] : npmax;
-    }
-    MV_GRID_STRIDE(i, n) {
-        cplx xv[KC];
-        mv_load<KC>(x, i, k, c0, xv);
-        for (int q = 0; q < npmax; q++) {
-            cplx pj[KC];
-            mv_load<KC>(d.ps[q], i, k, c0, pj);
-#pragma unroll
-            for (int c = 0; c < KC; c++)
-                if (q < np[c]) xv[c] = cadd(xv[c], cmul(lc[c0 + c].cx[q], pj[c]));
-        }
-#pragma unroll
-        for (int c = 0; c < KC; c++)
-            if (ret[c]) f.x[c0 + c][i] = xv[c];
-    }
-}
-
-// ... for a queue whose systems are not whole Fields (QueueHooks: the even-odd queue): the same expression, written to column j of a
-// work block, from where the hooks take it
-template <int KC>
-__global__ void __launch_bounds__(256) hq_retire_kernel(unsigned mask, const DevState *__restrict__ st, const LeanCoef *__restrict__ lc, MPtrs d,
-                                                        const cplx *__restrict__ x, cplx *__restrict__ out, int64_t n, int k) {
-    const int c0 = (int)blockIdx.y * KC;
-    if (((mask >> c0) & ((1u << KC) - 1u)) == 0) return;
-    bool ret[KC];
-    int np[KC];
-    int npmax = 0;
-#pragma unroll
-    for (int c = 0; c < KC; c++) {
-        ret[c] = c0 + c < k && ((mask >> (c0 + c)) & 1u);
-        np[c] = ret[c] ? st[c0 + c].npend : 0;
-        if (np[c] > LND) np[c] = LND;
-        npmax = np[c] > npmax ? np[c] : npmax;
-    }
-    MV_GRID_STRIDE(i, n) {
-        cplx xv[KC];
-        mv_load<KC>(x, i, k, c0, xv);
-        for (int q = 0; q < npmax; q++) {
-            cplx pj[KC];
-            mv_load<KC>(d.ps[q], i, k, c0, pj);
-#pragma unroll
-            for (int c = 0; c < KC; c++)
-                if (q < np[c]) xv[c] = cadd(xv[c], cmul(lc[c0 + c].cx[q], pj[c]));
-        }
-#pragma unroll
-        for (int c = 0; c < KC; c++)
-            if (ret[c]) out[i * k + c0 + c] = xv[c];
-    }
-}
-
 // admit, pass 1: the system's x and b into column blockIdx.y of the x and b blocks; without x0 also r0 = P0 = b
 __global__ void __launch_bounds__(RED_THREADS) q_scatter_kernel(unsigned mask, QFields f, cplx *__restrict__ xb, cplx *__restrict__ bb, cplx *__restrict__ r,
                                                                 cplx *__restrict__ p0, int64_t n, int k, int use_x0) {
@@ -617,49 +461,6 @@ __global__ void __launch_bounds__(RED_THREADS) q_r0_kernel(unsigned mask, const 
         const cplx v = sub ? csub(bb[i * k + j], t[i * k + j]) : t[i * k + j];
         r[i * k + j] = v;
         p0[i * k + j] = v;
-    }
-}
-
-// admit, pass 2: A r0 (the k-wide apply left it in ar) into slot 0 of the admitted columns, and their four start sums — rows per
-// thread and summation tree of m_init_partials_kernel.  A continuing column's sums (the closing step's build wrote them) stay.
-template <int KC>
-__global__ void __launch_bounds__(RED_THREADS) q_admit_kernel(unsigned mask, const cplx *__restrict__ b, const cplx *__restrict__ r,
-                                                              const cplx *__restrict__ ar, cplx *__restrict__ ap0, int64_t n, int k,
-                                                              double *__restrict__ partsN, double *__restrict__ partsR, double *__restrict__ partsA) {
-    __shared__ double lds[6 * KC * 17];
-    const int c0 = (int)blockIdx.y * KC;
-    if (((mask >> c0) & ((1u << KC) - 1u)) == 0) return;   // (uniform over the workgroup)
-    bool adm[KC];
-#pragma unroll
-    for (int c = 0; c < KC; c++) adm[c] = c0 + c < k && ((mask >> (c0 + c)) & 1u);
-    double v[6 * KC];
-#pragma unroll
-    for (int s = 0; s < 6 * KC; s++) v[s] = 0.;
-    MV_GRID_STRIDE(i, n) {
-        cplx bv[KC], rv[KC], av[KC];
-        mv_load<KC>(b, i, k, c0, bv);
-        mv_load<KC>(r, i, k, c0, rv);
-        mv_load<KC>(ar, i, k, c0, av);
-#pragma unroll
-        for (int c = 0; c < KC; c++) {
-            if (adm[c]) ap0[i * k + c0 + c] = av[c];
-            v[6 * c + 4] += bv[c].x * bv[c].x + bv[c].y * bv[c].y;
-            v[6 * c + 5] += rv[c].x * rv[c].x + rv[c].y * rv[c].y;
-            const cplx t = cconj_mul(rv[c], av[c]);
-            v[6 * c] += t.x; v[6 * c + 1] += t.y;
-            const cplx u = cconj_mul(av[c], av[c]);
-            v[6 * c + 2] += u.x; v[6 * c + 3] += u.y;
-        }
-    }
-    const double tot = block_sum_owner<6 * KC>(v, lds);
-    const int t = (int)threadIdx.x;
-    if (t < 6 * KC) {
-        const int col = c0 + t / 6, s = t % 6;
-        if (col < k && ((mask >> col) & 1u)) {
-            if (s < 4) partsA[(size_t)(col * 4 + s) * RED_MAX_BLOCKS + blockIdx.x] = tot;
-            else if (s == 4) partsN[(size_t)col * RED_MAX_BLOCKS + blockIdx.x] = tot;
-            else partsR[(size_t)col * RED_MAX_BLOCKS + blockIdx.x] = tot;
-        }
     }
 }
 
@@ -701,18 +502,20 @@ __global__ void __launch_bounds__(RED_THREADS) q_admit_state_kernel(unsigned mas
 // ------------------------------------------------------------------------------------------------
 // host driver
 // ------------------------------------------------------------------------------------------------
-#define MK(kernel, grid, block, ...)                                                         \
+#define MK(kernel, blocks, block, ...)                                                        \
     do {                                                                                     \
-        hipLaunchKernelGGL(kernel, grid, dim3(block), 0, ctx().stream, __VA_ARGS__);         \
+        hipLaunchKernelGGL(kernel, blocks, dim3(block), 0, ctx().stream, __VA_ARGS__);       \
         MGCR_HIP(hipGetLastError());                                                         \
     } while (0)
-#define MK_KC(kernel, g, block, ...)                                                         \
-    do {                                                                                     \
-        const dim3 grid__((unsigned)(g), (unsigned)groups);                                  \
-        if (kc == 1) MK((kernel<1>), grid__, block, __VA_ARGS__);                            \
-        else if (kc == 2) MK((kernel<2>), grid__, block, __VA_ARGS__);                       \
-        else MK((kernel<4>), grid__, block, __VA_ARGS__);                                    \
-    } while (0)
+// ... of a kernel template over the columns per thread: pick(KC) names the instantiation for KC, a std::integral_constant of kc's
+// value (1, 2, or 4 for every other kc)
+template <typename PICK, typename... AA>
+static int launch_kc(int kc, PICK pick, dim3 blocks, int block, AA... args) {
+    return dispatch_value<1, 2, 4>(kc, [&](auto KC) -> int {
+        MK(pick(KC), blocks, block, args...);
+        return MGCR_OK;
+    });
+}
 
 namespace {
 // Device storage of the batched solve.  Kept from solve to solve (as a GcrState keeps its slots) and re-made when n, k, the number of
@@ -782,6 +585,80 @@ struct MWork {
     }
 };
 MWork g_work;
+
+// One lockstep solve in flight, what gcr_multi_run and gcr_queue_run share: the work storage as a solve finds it, the launch geometry,
+// and the step.
+struct MRun {
+    MWork &wk = g_work;
+    Op *A = nullptr;
+    int64_t n = 0;
+    int k = 0, max_it = 0, cap = 0;
+    int g = 0, gx = 0;        // blocks of the RED_THREADS kernels / of the 256-thread ones (m_close_x_kernel, m_pending_x_kernel)
+    int kc = 0, groups = 0;   // columns per thread, groups of kc columns (blockIdx.y)
+    MPtrs d;
+    RowMap rmap;
+
+    dim3 grid_of(int blocks, int z = 1) const { return dim3((unsigned)blocks, (unsigned)groups, (unsigned)z); }
+
+    int setup(Op *A_, int64_t n_, int k_, int storage, int max_it_) {
+        A = A_; n = n_; k = k_; max_it = max_it_; cap = max_it + 1;
+        g = red_grid(n);
+        gx = g * 4 > 2048 ? 2048 : g * 4;
+        kc = mv_group(k);
+        groups = (k + kc - 1) / kc;
+        MGCR_TRY(wk.prepare(n, k, storage, cap));
+        hipStream_t stream = ctx().stream;
+        MGCR_HIP(hipMemsetAsync(wk.dhist, 0, sizeof(double) * (size_t)k * cap, stream));
+        MGCR_HIP(hipMemsetAsync(wk.lc, 0, sizeof(LeanCoef) * MV_MAX_K, stream));
+        MGCR_HIP(hipMemsetAsync(wk.coef, 0, sizeof(MCoef), stream));
+        for (int j = 0; j < LND; j++) { d.ps[j] = wk.ps[(size_t)(j < storage ? j : 0)]; d.aps[j] = wk.aps[(size_t)(j < storage ? j : 0)]; }
+        int64_t reach = 0;
+        const Op *b0 = op_matrix(A);   // (a MultiDiracOp deals its rows as the DiracOps of its columns do)
+        if (b0 && b0->kind == OP_CSR) reach = b0->csr.reach;
+        rmap = make_row_map(n, g, reach);
+        return MGCR_OK;
+    }
+
+    // Enqueues one step (slot bookkeeping: QueueStep): alpha, the residual update, the bookkeeping of the columns at their last step
+    // — after which a step that is the last for all of them ends — the k-wide apply, the beta dots, the coefficients, on a closing
+    // step the x / P0 update of the block x, and the build.
+    template <bool QUEUED>
+    int step(const QueueStep &s, cplx *x) {
+        const int it = s.it, lim = s.lim;
+        const DevState *st = wk.st;
+        const MCoef *coef = wk.coef;
+        const cplx *rin = s.cur >= 1 ? wk.ps[(size_t)s.cur] : wk.r;
+        cplx *dslot = s.nxt >= 1 ? wk.ps[(size_t)s.nxt] : wk.r;
+        MK(m_alpha_kernel, dim3((unsigned)k), RED_THREADS, wk.st, it, (const double *)wk.partsA, g, wk.den, s.cur, wk.lc, wk.coef);
+        MGCR_TRY(launch_kc(kc, [](auto KC) { return m_xr_kernel<KC>; }, grid_of(g), RED_THREADS, st, it, coef, (const cplx *)wk.aps[(size_t)s.cur],
+                           rin, dslot, n, k, wk.partsR));
+        if (s.any_last) MK((m_finish_kernel<QUEUED>), dim3((unsigned)k), RED_THREADS, wk.st, it, (const double *)wk.partsR, g, wk.dhist, cap, max_it);
+        if (s.all_last) return MGCR_OK;
+        MGCR_TRY(op_apply_multi_raw(A, dslot, wk.ar, n, k));
+        constexpr int NDT = 2;
+        MGCR_TRY(launch_kc(kc, [](auto KC) { return m_dot_kernel<KC, NDT>; }, grid_of(g, (lim + NDT - 1) / NDT), RED_THREADS, (const cplx *)wk.ar, d,
+                           lim, n, k, rmap, wk.partsB));
+        MK((m_coef_kernel<QUEUED>), dim3((unsigned)k), RED_THREADS, wk.st, it, (const double *)wk.partsB, (const double *)wk.partsR, g, wk.dhist, cap,
+           (const cplx *)wk.den, wk.lc, wk.coef, lim, s.closing ? 1 : 0, max_it);
+        if (s.closing)
+            MGCR_TRY(launch_kc(kc, [](auto KC) { return m_close_x_kernel<KC, QUEUED>; }, grid_of(gx), 256, st, it, coef, (const LeanCoef *)wk.lc, d,
+                               lim, (const cplx *)dslot, wk.ps[0], x, n, k, max_it));
+        MGCR_TRY(launch_kc(kc, [](auto KC) { return m_build_kernel<KC, QUEUED>; }, grid_of(g), RED_THREADS, st, it, coef, d, lim, (const cplx *)dslot,
+                           (const cplx *)wk.ar, wk.aps[(size_t)s.nxt], n, k, wk.partsA, max_it));
+        return MGCR_OK;
+    }
+};
+
+// A finished column's iteration count, flag and history row `row` (nullptr: not fetched, the caller wants neither history nor lines)
+// as system s of the caller's arrays, and its verbose lines
+void report_column(const mgcr_gcr_param &p, int s, int it, const double *row, double *hist, int hist_cap, int *n_iter, int *converged) {
+    if (n_iter) n_iter[s] = it;
+    if (converged) converged[s] = it == p.max_iter ? 0 : 1;
+    if (hist && row)
+        for (int i = 0; i <= it && i < hist_cap; i++) hist[(size_t)s * hist_cap + i] = row[i];
+    if (p.verbose && row)
+        for (int i = 0; i <= it; i++) printf("[%d] Step %d residual norm = %.10e\n", s, i, row[i]);
+}
 }  // namespace
 
 void mvec_release();   // mvec.hip
@@ -803,32 +680,14 @@ int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int6
     if (p.max_iter >= 1 && p.max_iter + 1 < storage) storage = p.max_iter + 1;
     MGCR_CHECK(storage <= LND, MGCR_ERR_UNSUPPORTED, "batched GCR: restart cycles of at most %d steps (the lean cycle) are supported", LND);
     const int max_it = p.max_iter > 0 ? p.max_iter : 1;
-    const int cap = max_it + 1;
-    const int g = red_grid(n);
-    const int kc = mv_group(k), groups = (k + kc - 1) / kc;
+    MRun run;
+    MGCR_TRY(run.setup(A, n, k, storage, max_it));
+    MWork &wk = run.wk;
+    const int g = run.g, kc = run.kc, cap = run.cap;
     const size_t ne = (size_t)n * (size_t)k;
-    MWork &wk = g_work;
-    MGCR_TRY(wk.prepare(n, k, storage, cap));
-    cplx *r = wk.r, *ar = wk.ar, *den = wk.den;
-    std::vector<cplx *> &ps = wk.ps, &aps = wk.aps;
-    DevState *st = wk.st;
-    LeanCoef *lc = wk.lc;
-    MCoef *coef = wk.coef;
-    double *partsA = wk.partsA, *partsR = wk.partsR, *partsN = wk.partsN, *partsB = wk.partsB, *dhist = wk.dhist;
-    MGCR_HIP(hipMemsetAsync(dhist, 0, sizeof(double) * (size_t)k * cap, c.stream));
-    MGCR_HIP(hipMemsetAsync(lc, 0, sizeof(LeanCoef) * MV_MAX_K, c.stream));
-    MGCR_HIP(hipMemsetAsync(coef, 0, sizeof(MCoef), c.stream));
+    cplx *r = wk.r;
 
-    MPtrs d;
-    for (int j = 0; j < LND; j++) { d.ps[j] = ps[(size_t)(j < storage ? j : 0)]; d.aps[j] = aps[(size_t)(j < storage ? j : 0)]; }
-    int64_t reach = 0;
-    {
-        const Op *b0 = op_matrix(A);   // (a MultiDiracOp deals its rows as the DiracOps of its columns do)
-        if (b0 && b0->kind == OP_CSR) reach = b0->csr.reach;
-    }
-    const RowMap rmap = make_row_map(n, g, reach);
-
-    MK(m_reset_kernel, dim3(1), MV_MAX_K, st, p.tol * p.tol, k);
+    MK(m_reset_kernel, dim3(1), MV_MAX_K, wk.st, p.tol * p.tol, k);
     // r0 = b, or b - A x0 formed as the single solve forms it (op_residual_raw: one pass for a plain Sparse, apply then b - r for
     // a DiracOp and for a MultiDiracOp)
     if (p.use_x0) {
@@ -841,55 +700,31 @@ int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int6
     } else {
         MGCR_TRY(mv_copy(r, rhs, n, k));
     }
-    MGCR_TRY(mv_copy(ps[0], r, n, k));                       // P0 = r0
-    MGCR_TRY(op_apply_multi_raw(A, r, aps[0], n, k));        // Ap0
-    MK_KC(m_init_partials_kernel, g, RED_THREADS, rhs, (const cplx *)r, (const cplx *)aps[0], n, k, partsN, partsR, partsA);
-    MK(m_init_kernel, dim3((unsigned)k), RED_THREADS, st, (const double *)partsN, (const double *)partsR, g, dhist, cap);
+    MGCR_TRY(mv_copy(wk.ps[0], r, n, k));                       // P0 = r0
+    MGCR_TRY(op_apply_multi_raw(A, r, wk.aps[0], n, k));        // Ap0
+    MGCR_TRY(launch_kc(kc, [](auto KC) { return m_init_partials_kernel<KC, false>; }, run.grid_of(g), RED_THREADS, rhs, (const cplx *)r,
+                       (const cplx *)wk.aps[0], n, k, wk.partsN, wk.partsR, wk.partsA, 0u, (cplx *)nullptr));
+    MK(m_init_kernel, dim3((unsigned)k), RED_THREADS, wk.st, (const double *)wk.partsN, (const double *)wk.partsR, g, wk.dhist, cap);
 
     const int check_every = p.check_every > 0 ? p.check_every : 10;
     std::vector<DevState> hs((size_t)MV_MAX_K);
     auto poll = [&]() -> int {
-        MGCR_HIP(hipMemcpyAsync(hs.data(), st, sizeof(DevState) * MV_MAX_K, hipMemcpyDeviceToHost, c.stream));
+        MGCR_HIP(hipMemcpyAsync(hs.data(), wk.st, sizeof(DevState) * MV_MAX_K, hipMemcpyDeviceToHost, c.stream));
         MGCR_HIP(hipStreamSynchronize(c.stream));
         return MGCR_OK;
     };
-    const cplx *rcur = r;
     int iter_count = 0, cur = 0, global = 0, last_check = 0;
     bool done = false;
     while (global < max_it && !done) {
         global++;
-        const int it = global;
-        const bool last = global == max_it;
+        const bool last = global == max_it;   // every column's last step: the step ends with the bookkeeping
         // slot bookkeeping of gcr.hip's gcr_step
         iter_count++;
         const int lim = storage < iter_count ? storage : iter_count;
         int ic_next = iter_count;
         if (iter_count % restart == 0) ic_next = 0;
         const int nxt = ic_next % storage;
-        cplx *dslot = nxt >= 1 ? ps[(size_t)nxt] : r;
-        MK(m_alpha_kernel, dim3((unsigned)k), RED_THREADS, st, it, (const double *)partsA, g, den, cur, lc, coef);
-        MK_KC(m_xr_kernel, g, RED_THREADS, (const DevState *)st, it, (const MCoef *)coef, (const cplx *)aps[(size_t)cur], rcur, dslot, n, k, partsR);
-        rcur = dslot;
-        if (last) {
-            MK(m_finish_kernel, dim3((unsigned)k), RED_THREADS, st, it, (const double *)partsR, g, dhist, cap);
-        } else {
-            const int closing = ic_next == 0 ? 1 : 0;
-            MGCR_TRY(op_apply_multi_raw(A, dslot, ar, n, k));
-            {
-                constexpr int NDT = 2;
-                const dim3 grid((unsigned)g, (unsigned)groups, (unsigned)((lim + NDT - 1) / NDT));
-                if (kc == 1) MK((m_dot_kernel<1, NDT>), grid, RED_THREADS, (const cplx *)ar, d, lim, n, k, rmap, partsB);
-                else if (kc == 2) MK((m_dot_kernel<2, NDT>), grid, RED_THREADS, (const cplx *)ar, d, lim, n, k, rmap, partsB);
-                else MK((m_dot_kernel<4, NDT>), grid, RED_THREADS, (const cplx *)ar, d, lim, n, k, rmap, partsB);
-            }
-            MK(m_coef_kernel, dim3((unsigned)k), RED_THREADS, st, it, (const double *)partsB, (const double *)partsR, g, dhist, cap,
-               (const cplx *)den, lc, coef, lim, closing);
-            if (closing)
-                MK_KC(m_close_x_kernel, red_grid(n) * 4 > 2048 ? 2048 : red_grid(n) * 4, 256, (const DevState *)st, it, (const MCoef *)coef,
-                      (const LeanCoef *)lc, d, lim, (const cplx *)dslot, ps[0], x, n, k);
-            MK_KC(m_build_kernel, g, RED_THREADS, (const DevState *)st, it, (const MCoef *)coef, d, lim, rcur, (const cplx *)ar, aps[(size_t)nxt], n, k,
-                  partsA);
-        }
+        MGCR_TRY(run.step<false>(QueueStep{global, lim, cur, nxt, ic_next == 0, last, last}, x));
         iter_count = ic_next;
         cur = nxt;
         if (global / check_every != last_check || global == max_it) {
@@ -899,20 +734,12 @@ int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int6
             for (int j = 0; j < k; j++) done = done && hs[(size_t)j].stop_at != INT_MAX;
         }
     }
-    MK_KC(m_flush_kernel, red_grid(n) * 4 > 2048 ? 2048 : red_grid(n) * 4, 256, (const DevState *)st, (const LeanCoef *)lc, d, x, n, k);
+    MGCR_TRY(launch_kc(kc, [](auto KC) { return m_pending_x_kernel<KC, XFlush>; }, run.grid_of(run.gx), 256, 0u, (const DevState *)wk.st,
+                       (const LeanCoef *)wk.lc, run.d, (const cplx *)x, XFlush{x}, n, k));
     MGCR_TRY(poll());
     std::vector<double> hh((size_t)k * cap);
-    MGCR_HIP(hipMemcpy(hh.data(), dhist, sizeof(double) * hh.size(), hipMemcpyDeviceToHost));
-    for (int j = 0; j < k; j++) {
-        const int it = hs[(size_t)j].iter;
-        if (n_iter) n_iter[j] = it;
-        if (converged) converged[j] = it == p.max_iter ? 0 : 1;
-        if (hist)
-            for (int i = 0; i <= it && i < hist_cap; i++) hist[(size_t)j * hist_cap + i] = hh[(size_t)j * cap + i];
-        if (p.verbose) {
-            for (int i = 0; i <= it; i++) printf("[%d] Step %d residual norm = %.10e\n", j, i, hh[(size_t)j * cap + i]);
-        }
-    }
+    MGCR_HIP(hipMemcpy(hh.data(), wk.dhist, sizeof(double) * hh.size(), hipMemcpyDeviceToHost));
+    for (int j = 0; j < k; j++) report_column(p, j, hs[(size_t)j].iter, hh.data() + (size_t)j * cap, hist, hist_cap, n_iter, converged);
     g_multi_solves++;
     return resident_check();
 }
@@ -921,18 +748,20 @@ int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int6
 // Queued batched solve: nsys systems stream through k = min(width, nsys) columns of ONE batched solve.  The schedule — when the
 // host polls, which slots it retires and refills — is queue_plan.h's; this driver carries it out.  Every launch is enqueued by
 // the host in stream order: no kernel waits on another workgroup, on a flag or on the host.
-//   retire (slots found stopped by a poll): q_retire_kernel (pending x updates + unpack into the system's Field), the history
-//     row and the iteration count go to the system's entries;
+//   retire (slots found stopped by a poll): m_pending_x_kernel<KC, XFields> (pending x updates + unpack into the system's Field),
+//     the history row and the iteration count go to the system's entries;
 //   admit (phase 0 of the cycle, `global` steps launched): q_scatter_kernel; with x0 the k-wide apply into the free `ar` block and
-//     q_r0_kernel; the k-wide apply of r into `ar` (column j has the bits of the single apply: Rule 1) and q_admit_kernel, which
-//     copies the admitted columns into slot 0 while it takes their four start sums; q_admit_state_kernel (base = -global).
+//     q_r0_kernel; the k-wide apply of r into `ar` (column j has the bits of the single apply: Rule 1) and
+//     m_init_partials_kernel<KC, true>, which copies the admitted columns into slot 0 while it takes their four start sums;
+//     q_admit_state_kernel (base = -global).
 //     Per admission point: 2 (3 with x0) passes over the block + 1 (2) k-wide applies, whatever the number of columns admitted.
-//   step: gcr_multi_run's, except that a column at its OWN last step takes q_finish_kernel and is left out of what follows.
+//   step: gcr_multi_run's (MRun::step), in its QUEUED form: a column at its OWN last step takes the finishing bookkeeping and is
+//     left out of what follows.
 // ks != nullptr: system s is (1 - ks[s] D) x = b, D = A a plain Sparse; the slots' shifts live in a MultiDiracOp made here, whose
 // values travel in the kernel arguments of every apply (KCols): admitting system s into slot j sets entry j.
 // hk != nullptr (the even-odd queue, evenodd_queue.hip): the systems are not Fields of n entries.  The hooks fill the admitted
-// columns in place of q_scatter_kernel and take the retiring columns from a work block that hq_retire_kernel writes in place of
-// q_retire_kernel; rhs, x and ks are not read, and the counters that move are the hooks' own.  Without hooks every launch is what it was.
+// columns in place of q_scatter_kernel and take the retiring columns from a work block that the XBlock form of m_pending_x_kernel writes in place of
+// the XFields one; rhs, x and ks are not read, and the counters that move are the hooks' own.  Without hooks every launch is what it was.
 // ------------------------------------------------------------------------------------------------
 static int64_t g_queue_solves = 0, g_queue_admissions = 0, g_queue_steps = 0;
 static int64_t g_hooked_solves = 0, g_hooked_admissions = 0, g_hooked_steps = 0;
@@ -948,23 +777,6 @@ int gcr_queue_run(Op *A0, const mgcr_gcr_param &p, int width, int nsys, const cp
     QueuePlan qp(width < nsys ? width : nsys, nsys, restart, p.max_iter, p.check_every);
     const int storage = qp.storage, max_it = qp.max_it, k = qp.width;
     MGCR_CHECK(storage <= LND, MGCR_ERR_UNSUPPORTED, "batched GCR: restart cycles of at most %d steps (the lean cycle) are supported", LND);
-    const int cap = max_it + 1;
-    const int g = red_grid(n);
-    const int kc = mv_group(k), groups = (k + kc - 1) / kc;
-    const int gx = red_grid(n) * 4 > 2048 ? 2048 : red_grid(n) * 4;   // the 256-thread kernels (m_close_x_kernel, m_flush_kernel)
-    MWork &wk = g_work;
-    MGCR_TRY(wk.prepare(n, k, storage, cap));
-    MGCR_TRY(wk.prepare_queue());
-    cplx *r = wk.r, *ar = wk.ar, *den = wk.den, *xb = wk.xq, *bb = wk.bq;
-    std::vector<cplx *> &ps = wk.ps, &aps = wk.aps;
-    DevState *st = wk.st;
-    LeanCoef *lc = wk.lc;
-    MCoef *coef = wk.coef;
-    double *partsA = wk.partsA, *partsR = wk.partsR, *partsN = wk.partsN, *partsB = wk.partsB, *dhist = wk.dhist;
-    MGCR_HIP(hipMemsetAsync(dhist, 0, sizeof(double) * (size_t)k * cap, c.stream));
-    MGCR_HIP(hipMemsetAsync(lc, 0, sizeof(LeanCoef) * MV_MAX_K, c.stream));
-    MGCR_HIP(hipMemsetAsync(coef, 0, sizeof(MCoef), c.stream));
-
     Op shifted;   // ks: the slots' MultiDiracOp (borrows A0; lives for this call)
     Op *A = A0;
     if (ks) {
@@ -976,14 +788,13 @@ int gcr_queue_run(Op *A0, const mgcr_gcr_param &p, int width, int nsys, const cp
         for (int j = 0; j < MV_MAX_K; j++) shifted.ks[j] = make_double2(j < k ? 1. : 0., 0.);
         A = &shifted;
     }
-    MPtrs d;
-    for (int j = 0; j < LND; j++) { d.ps[j] = ps[(size_t)(j < storage ? j : 0)]; d.aps[j] = aps[(size_t)(j < storage ? j : 0)]; }
-    int64_t reach = 0;
-    {
-        const Op *b0 = op_matrix(A);
-        if (b0 && b0->kind == OP_CSR) reach = b0->csr.reach;
-    }
-    const RowMap rmap = make_row_map(n, g, reach);
+    MRun run;
+    MGCR_TRY(run.setup(A, n, k, storage, max_it));
+    MWork &wk = run.wk;
+    MGCR_TRY(wk.prepare_queue());
+    const int g = run.g, kc = run.kc, cap = run.cap;
+    cplx *r = wk.r, *ar = wk.ar, *xb = wk.xq, *bb = wk.bq;
+    DevState *st = wk.st;
     const bool residual_form = A->kind == OP_CSR && A->csr.nrow == n && A->csr.ncol == n;   // b - A x0 in one pass (op_residual_raw)
 
     MK(m_reset_kernel, dim3(1), MV_MAX_K, st, p.tol * p.tol, 0);   // every slot empty
@@ -1001,21 +812,21 @@ int gcr_queue_run(Op *A0, const mgcr_gcr_param &p, int width, int nsys, const cp
             for (int j = 0; j < k; j++)
                 if (qp.occupied(j) && hs[(size_t)j].stop_at != INT_MAX) mask |= 1u << j;
             if (mask) {
-                if (hk) MK_KC(hq_retire_kernel, gx, 256, mask, (const DevState *)st, (const LeanCoef *)lc, d, (const cplx *)xb, hk->retire_block(), n, k);
-                else MK_KC(q_retire_kernel, gx, 256, mask, (const DevState *)st, (const LeanCoef *)lc, d, (const cplx *)xb, f, n, k);
+                if (hk)
+                    MGCR_TRY(launch_kc(kc, [](auto KC) { return m_pending_x_kernel<KC, XBlock>; }, run.grid_of(run.gx), 256, mask,
+                                       (const DevState *)st, (const LeanCoef *)wk.lc, run.d, (const cplx *)xb, XBlock{hk->retire_block()}, n, k));
+                else
+                    MGCR_TRY(launch_kc(kc, [](auto KC) { return m_pending_x_kernel<KC, XFields>; }, run.grid_of(run.gx), 256, mask,
+                                       (const DevState *)st, (const LeanCoef *)wk.lc, run.d, (const cplx *)xb, XFields{f}, n, k));
                 for (int j = 0; j < k; j++) {
                     if (!((mask >> j) & 1u)) continue;
-                    const int s = qp.sys[j], it = hs[(size_t)j].iter;
-                    if (n_iter) n_iter[s] = it;
-                    if (converged) converged[s] = it == p.max_iter ? 0 : 1;
-                    if ((hist && hist_cap > 0) || p.verbose) {   // (the row is final: the column stopped before the poll's synchronise)
+                    const int it = hs[(size_t)j].iter;
+                    const bool fetch = (hist && hist_cap > 0) || p.verbose;   // (the row is final: the column stopped before the poll's synchronise)
+                    if (fetch) {
                         row.resize((size_t)cap);
-                        MGCR_HIP(hipMemcpy(row.data(), dhist + (size_t)j * cap, sizeof(double) * (size_t)(it + 1), hipMemcpyDeviceToHost));
-                        if (hist)
-                            for (int i = 0; i <= it && i < hist_cap; i++) hist[(size_t)s * hist_cap + i] = row[(size_t)i];
-                        if (p.verbose)
-                            for (int i = 0; i <= it; i++) printf("[%d] Step %d residual norm = %.10e\n", s, i, row[(size_t)i]);
+                        MGCR_HIP(hipMemcpy(row.data(), wk.dhist + (size_t)j * cap, sizeof(double) * (size_t)(it + 1), hipMemcpyDeviceToHost));
                     }
+                    report_column(p, qp.sys[j], it, fetch ? row.data() : nullptr, hist, hist_cap, n_iter, converged);
                     qp.retire(j);
                 }
                 if (hk) MGCR_TRY(hk->retire(mask));
@@ -1034,44 +845,23 @@ int gcr_queue_run(Op *A0, const mgcr_gcr_param &p, int width, int nsys, const cp
                 if (ks) shifted.ks[j] = ks[s];
             }
             const dim3 cols((unsigned)g, (unsigned)k);
-            if (hk) MGCR_TRY(hk->admit(mask, m, slots, systems, xb, bb, r, ps[0], p.use_x0 != 0));
-            else MK(q_scatter_kernel, cols, RED_THREADS, mask, f, xb, bb, r, ps[0], n, k, p.use_x0 ? 1 : 0);
+            if (hk) MGCR_TRY(hk->admit(mask, m, slots, systems, xb, bb, r, wk.ps[0], p.use_x0 != 0));
+            else MK(q_scatter_kernel, cols, RED_THREADS, mask, f, xb, bb, r, wk.ps[0], n, k, p.use_x0 ? 1 : 0);
             if (p.use_x0) {
                 if (residual_form) MGCR_TRY(op_apply_multi_raw(A, xb, ar, n, k, bb));
                 else MGCR_TRY(op_apply_multi_raw(A, xb, ar, n, k));
-                MK(q_r0_kernel, cols, RED_THREADS, mask, (const cplx *)ar, (const cplx *)bb, r, ps[0], n, k, residual_form ? 0 : 1);
+                MK(q_r0_kernel, cols, RED_THREADS, mask, (const cplx *)ar, (const cplx *)bb, r, wk.ps[0], n, k, residual_form ? 0 : 1);
             }
             MGCR_TRY(op_apply_multi_raw(A, r, ar, n, k));
-            MK_KC(q_admit_kernel, g, RED_THREADS, mask, (const cplx *)bb, (const cplx *)r, (const cplx *)ar, aps[0], n, k, partsN, partsR, partsA);
-            MK(q_admit_state_kernel, dim3((unsigned)k), RED_THREADS, mask, st, qp.global, p.tol * p.tol, (const double *)partsN, (const double *)partsR, g,
-               dhist, cap, lc, coef);
+            MGCR_TRY(launch_kc(kc, [](auto KC) { return m_init_partials_kernel<KC, true>; }, run.grid_of(g), RED_THREADS, (const cplx *)bb,
+                               (const cplx *)r, (const cplx *)ar, n, k, wk.partsN, wk.partsR, wk.partsA, mask, wk.aps[0]));
+            MK(q_admit_state_kernel, dim3((unsigned)k), RED_THREADS, mask, st, qp.global, p.tol * p.tol, (const double *)wk.partsN,
+               (const double *)wk.partsR, g, wk.dhist, cap, wk.lc, wk.coef);
         }
         if (qp.finished()) break;
         MGCR_CHECK(qp.any_running(), MGCR_ERR_HIP, "queued GCR: a column is still marked as running after its last step");
-        const QueueStep s = qp.step();
         steps++;
-        const int it = s.it, lim = s.lim;
-        const cplx *rin = s.cur >= 1 ? ps[(size_t)s.cur] : r;
-        cplx *dslot = s.nxt >= 1 ? ps[(size_t)s.nxt] : r;
-        MK(m_alpha_kernel, dim3((unsigned)k), RED_THREADS, st, it, (const double *)partsA, g, den, s.cur, lc, coef);
-        MK_KC(m_xr_kernel, g, RED_THREADS, (const DevState *)st, it, (const MCoef *)coef, (const cplx *)aps[(size_t)s.cur], rin, dslot, n, k, partsR);
-        if (s.any_last) MK(q_finish_kernel, dim3((unsigned)k), RED_THREADS, st, it, max_it, (const double *)partsR, g, dhist, cap);
-        if (s.all_last) continue;
-        MGCR_TRY(op_apply_multi_raw(A, dslot, ar, n, k));
-        {
-            constexpr int NDT = 2;
-            const dim3 grid((unsigned)g, (unsigned)groups, (unsigned)((lim + NDT - 1) / NDT));
-            if (kc == 1) MK((m_dot_kernel<1, NDT>), grid, RED_THREADS, (const cplx *)ar, d, lim, n, k, rmap, partsB);
-            else if (kc == 2) MK((m_dot_kernel<2, NDT>), grid, RED_THREADS, (const cplx *)ar, d, lim, n, k, rmap, partsB);
-            else MK((m_dot_kernel<4, NDT>), grid, RED_THREADS, (const cplx *)ar, d, lim, n, k, rmap, partsB);
-        }
-        MK(q_coef_kernel, dim3((unsigned)k), RED_THREADS, st, it, (const double *)partsB, (const double *)partsR, g, dhist, cap, (const cplx *)den, lc,
-           coef, lim, s.closing ? 1 : 0, max_it);
-        if (s.closing)
-            MK_KC(q_close_x_kernel, gx, 256, (const DevState *)st, it, (const MCoef *)coef, (const LeanCoef *)lc, d, lim, (const cplx *)dslot, ps[0], xb, n,
-                  k, max_it);
-        MK_KC(q_build_kernel, g, RED_THREADS, (const DevState *)st, it, (const MCoef *)coef, d, lim, (const cplx *)dslot, (const cplx *)ar,
-              aps[(size_t)s.nxt], n, k, partsA, max_it);
+        MGCR_TRY(run.step<true>(qp.step(), xb));
     }
     MGCR_HIP(hipStreamSynchronize(c.stream));   // the last retirement's writes to the systems' Fields
     (hk ? g_hooked_admissions : g_queue_admissions) += qp.admissions - admissions0;

@@ -1,11 +1,15 @@
-"""Register budget of the queued even-odd scan's kernels (csrc/evenodd_queue.hip, and hq_retire_kernel of csrc/gcr_multi.hip) on the
+"""Register budget of the queued even-odd scan's kernels (csrc/evenodd_queue.hip, and the work-block sink of m_pending_x_kernel in
+csrc/gcr_multi.hip) on the
 code object hipcc builds for gfx950 (-Rpass-analysis=kernel-resource-usage); no GPU needed.  The masked gather / scatter / copy
 <KP lanes per row> and the block form of the retiring x update <KC columns per thread> are streaming kernels: none touches scratch
 or LDS, and each keeps 8 waves per SIMD, so that two 1024-thread workgroups share a CU.
 
 The feature reaches everything else through entries that existed before it.  Those compile to what they were: spmm.hip against
 tests/golden/spmm_kernel_usage.json, and the q_ / m_ kernels of gcr_multi.hip and the eom_ kernels of evenodd_multi.hip against
-tests/golden/queue_kernel_usage.json, recorded from the commit before the queued even-odd scan."""
+tests/golden/queue_kernel_usage.json, recorded from the commit before the queued even-odd scan.  (The rows stand under the names of
+the instantiations that have since replaced the queued solve's copies — m_build_kernel<KC, true> for q_build_kernel<KC>, and so on,
+profiles/multi_fold_resource_usage.md — with the figures recorded then; the one figure that moved with the fold is the VGPR count of
+the flush form of the pending-x kernel at KC = 2, 4: 24 and 42, which were 26 and 44.)"""
 import json
 import os
 import re
@@ -19,7 +23,7 @@ CS = os.path.join(HERE, "..", "mgpreconditionedgcr_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 KEYS = ("VGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]")
 NEW = ["%s<%d>" % (k, kp) for k in ("eoq_gather_kernel", "eoq_scatter_kernel", "eoq_copy_kernel") for kp in (1, 2, 4, 8, 16)]
-NEW_IN_GCR_MULTI = ["hq_retire_kernel<%d>" % kc for kc in (1, 2, 4)]
+NEW_IN_GCR_MULTI = ["m_pending_x_kernel<%d, XBlock>" % kc for kc in (1, 2, 4)]
 
 
 def resource_usage(hipcc, src, out):

@@ -148,6 +148,25 @@ def test_mixed_stops():
     check_queue(A, args, bs, refs, 3)
 
 
+def test_own_last_step_beside_a_closing_step_four_columns_per_thread():
+    """Width 3 (four columns per thread, a ragged group), restart 5, max_iter 20.  System 0 is solved in one step, so its slot is refilled
+    at step 5: at step 20, which closes a cycle, two columns are at their own last step while the refilled one, at its step 15, runs
+    the closing step; at step 25 that one is at its last step beside system 4, admitted at 20.  (In test_every_system_runs_to_max_iter
+    the columns of a launch end together; in test_mixed_stops max_iter is no multiple of the cycle.)  Two columns per thread meet
+    the same case in test_scan_longest_first and test_check_every_does_not_change_the_results at width 2: system 0 of the scan runs
+    to max_iter 400, a closing step, while the other slot runs another system.  One column per thread has no neighbour."""
+    n = 12
+    A, N = poisson(n)
+    assert A.xr_fuse_kind() in (0, 1)
+    args = (0, 5, 20, 1e-8)
+    bs = [eigenvector(n, 1, 1, 1)] + [problems.rhs_grid(N, s) for s in range(1, 5)]
+    refs = [single(("last-closing", s), A, args, bs[s]) for s in range(5)]
+    its = [r[0] for r in refs]
+    assert its[0] < 5 and its[1:] == [20] * 4, its
+    steps, admissions = check_queue(A, args, bs, refs, 3)
+    assert steps == 40 and admissions == 2      # systems 1, 2: 0 .. 20; 3: 5 .. 25; 4: 20 .. 40
+
+
 # ---- 6: x0 -----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("use_x0", [True, False])
 def test_nonzero_x_on_entry(sample, use_x0):

@@ -37,12 +37,12 @@ OCC = {
     "bcsr_multi_kernel<0>": 8, "bcsr_multi_kernel<1>": 8, "bcsr_multi_kernel<2>": 8, "bcsr_multi_kernel<4>": 8,
     "bcsr_multi_kernel<8>": 6, "bcsr_multi_kernel<16>": 3,
     # batched GCR <KC columns per thread> (1024-thread workgroups: 4 .. 7 = one workgroup per CU, 8 = two)
-    "m_init_partials_kernel<1>": 8, "m_init_partials_kernel<2>": 8, "m_init_partials_kernel<4>": 4,
+    "m_init_partials_kernel<1, false>": 8, "m_init_partials_kernel<2, false>": 8, "m_init_partials_kernel<4, false>": 4,
     "m_xr_kernel<1>": 8, "m_xr_kernel<2>": 8, "m_xr_kernel<4>": 8,
     "m_dot_kernel<1, 2>": 8, "m_dot_kernel<2, 2>": 8, "m_dot_kernel<4, 2>": 5,
-    "m_build_kernel<1>": 8, "m_build_kernel<2>": 8, "m_build_kernel<4>": 4,
-    "m_close_x_kernel<1>": 8, "m_close_x_kernel<2>": 8, "m_close_x_kernel<4>": 6,
-    "m_flush_kernel<1>": 8, "m_flush_kernel<2>": 8, "m_flush_kernel<4>": 8,
+    "m_build_kernel<1, false>": 8, "m_build_kernel<2, false>": 8, "m_build_kernel<4, false>": 4,
+    "m_close_x_kernel<1, false>": 8, "m_close_x_kernel<2, false>": 8, "m_close_x_kernel<4, false>": 6,
+    "m_pending_x_kernel<1, XFlush>": 8, "m_pending_x_kernel<2, XFlush>": 8, "m_pending_x_kernel<4, XFlush>": 8,
 }
 
 

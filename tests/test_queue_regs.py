@@ -1,9 +1,10 @@
-"""Register budget of the queued batched GCR's kernels (csrc/gcr_multi.hip: the q_* entries) on the code object hipcc builds for
-gfx950 (-Rpass-analysis=kernel-resource-usage); no GPU needed.  None spills to scratch.  The step kernels that share a body with a
-batched-solve entry (q_build_kernel / m_build_kernel, q_close_x_kernel / m_close_x_kernel) keep that entry's occupancy and LDS;
-the KC-templated streaming kernels of retirement and admission reach the waves per SIMD of m_xr_kernel<KC> — except
-q_admit_kernel<4>, which carries the 24 running sums of m_init_partials_kernel<4> and has its occupancy (DESIGN.md section 9,
-"Queued solve": it runs once per admission point, not per step)."""
+"""Register budget of the queued batched GCR's kernels (csrc/gcr_multi.hip: the q_* entries, the QUEUED = true instantiations of the
+kernels it shares with the batched solve, and the Field sink of the pending-x kernel) on the code object hipcc builds for gfx950
+(-Rpass-analysis=kernel-resource-usage); no GPU needed.  None spills to scratch.  The step kernels' queued instantiations
+(m_build_kernel<KC, true>, m_close_x_kernel<KC, true>) keep the occupancy and LDS of the batched ones (<KC, false>); the
+KC-templated streaming kernels of retirement and admission reach the waves per SIMD of m_xr_kernel<KC> — except
+m_init_partials_kernel<4, true>, which carries the 24 running sums of m_init_partials_kernel<4, false> and has its occupancy
+("Queued solve": it runs once per admission point, not per step)."""
 import os
 import re
 import shutil
@@ -13,10 +14,15 @@ import pytest
 
 CS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mgpreconditionedgcr_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SCALAR = ["q_finish_kernel", "q_coef_kernel", "q_scatter_kernel", "q_r0_kernel", "q_admit_state_kernel"]
-SHARED_BODY = {"q_build_kernel": "m_build_kernel", "q_close_x_kernel": "m_close_x_kernel"}
-STREAMING = ["q_retire_kernel", "q_admit_kernel"]
-EXCEPTIONS = {"q_admit_kernel<4>": "m_init_partials_kernel<4>"}   # kernel -> the entry whose occupancy it has instead of m_xr_kernel's
+SCALAR = ["m_finish_kernel<true>", "m_coef_kernel<true>", "q_scatter_kernel", "q_r0_kernel", "q_admit_state_kernel"]
+SHARED_BODY = {"m_build_kernel<%d, true>": "m_build_kernel<%d, false>", "m_close_x_kernel<%d, true>": "m_close_x_kernel<%d, false>"}
+STREAMING = {"retire": "m_pending_x_kernel<%d, XFields>", "admit": "m_init_partials_kernel<%d, true>"}
+# kernel -> the entry whose occupancy it has instead of m_xr_kernel's
+EXCEPTIONS = {"m_init_partials_kernel<4, true>": "m_init_partials_kernel<4, false>"}
+
+
+def is_queue_entry(name):
+    return name.startswith("q_") or name.endswith("true>") or name.endswith("XFields>")
 
 
 @pytest.fixture(scope="module")
@@ -44,8 +50,8 @@ def usage(tmp_path_factory):
 
 
 def test_every_queue_kernel_is_there_and_none_spills(usage):
-    names = [n for n in usage if n.startswith("q_")]
-    want = SCALAR + [k + "<%d>" % kc for k in list(SHARED_BODY) + STREAMING for kc in (1, 2, 4)]
+    names = [n for n in usage if is_queue_entry(n)]
+    want = SCALAR + [k % kc for k in list(SHARED_BODY) + list(STREAMING.values()) for kc in (1, 2, 4)]
     assert sorted(names) == sorted(want)
     for n in names:
         assert usage[n]["ScratchSize [bytes/lane]"] == 0, (n, usage[n])
@@ -54,14 +60,14 @@ def test_every_queue_kernel_is_there_and_none_spills(usage):
 @pytest.mark.parametrize("kc", [1, 2, 4])
 def test_step_kernels_keep_the_batched_entries_budget(usage, kc):
     for q, m in SHARED_BODY.items():
-        a, b = usage["%s<%d>" % (q, kc)], usage["%s<%d>" % (m, kc)]
+        a, b = usage[q % kc], usage[m % kc]
         assert a["Occupancy [waves/SIMD]"] >= b["Occupancy [waves/SIMD]"], (q, kc, a, b)
         assert a["LDS Size [bytes/block]"] == b["LDS Size [bytes/block]"], (q, kc, a, b)
 
 
 @pytest.mark.parametrize("kc", [1, 2, 4])
-@pytest.mark.parametrize("kernel", STREAMING)
-def test_streaming_kernels_reach_the_residual_updates_occupancy(usage, kernel, kc):
-    name = "%s<%d>" % (kernel, kc)
+@pytest.mark.parametrize("point", sorted(STREAMING))
+def test_streaming_kernels_reach_the_residual_updates_occupancy(usage, point, kc):
+    name = STREAMING[point] % kc
     ref = EXCEPTIONS.get(name, "m_xr_kernel<%d>" % kc)
     assert usage[name]["Occupancy [waves/SIMD]"] >= usage[ref]["Occupancy [waves/SIMD]"], (name, usage[name], ref, usage[ref])

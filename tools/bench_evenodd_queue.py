@@ -141,10 +141,13 @@ def main():
     ap.add_argument("--k-synth", type=float, default=0.116)
     ap.add_argument("--parts", nargs="+", default=["sample", "synthetic"], choices=["sample", "synthetic"])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "evenodd_queue.json"))
+    ap.add_argument("--lib", default=None, help="load this libmgcr_hip.so instead of the in-tree one (one side of a parent / this comparison)")
     a = ap.parse_args()
     if a.runs < 6:
         ap.error("--runs must be at least 6")
     import bench
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     _lib.init()
     out = {"src_sha16": bench.source_sha16(), "restart": RESTART, "tol": TOL, "check_every": CHECK_EVERY, "runs": a.runs, "problems": {}}
     if "sample" in a.parts and a.sample:
