@@ -385,7 +385,8 @@ int mgcr_set_option(const char *name, int value, int *previous);
  * "evenodd_block_applies" = Schur applies of an operator with a dense block per site (mgcr_eo_create_block), inside GCR steps or
  * not, "evenodd_block_fused_steps" = its GCR steps whose last apply launch took the step's beta dot products (Rule 3b),
  * "gcr32_applies" = applies of a low-precision GCR (mgcr_gcr32_create) that ran on the device, "gcr32_steps" = the inner steps those
- * enqueued (both kept on the device: one synchronisation per query). */
+ * enqueued (both kept on the device: one synchronisation per query), "gcr32_multi_applies" = batched applies of a low-precision
+ * GCR (mgcr_gcr32_apply_multi, mgcr_gcr32_solve_multi) enqueued, "gcr32_multi_steps" = the lockstep steps those enqueued. */
 int mgcr_stat(const char *name, int64_t *value);
 
 /* Self-test of the hardware behaviour the one-launch solver paths (csrc/gcr_resident.hip, gcr_stepbuild.hip) build on: inside
@@ -602,6 +603,55 @@ int mgcr_gcr32_eo_info(mgcr_op_t op, int64_t *n, int64_t *n_even, int64_t *n_odd
                        int64_t *tail_rows_eo, int64_t *tail_rows_oe, int32_t *real_slab, int32_t *has_diag, int64_t *stored_bytes);
 /* a_e32 and inv_o32 as the device holds them ((1, 0) when no diagonal is stored) */
 int mgcr_gcr32_eo_diag(mgcr_op_t op, float *a_even_ri /* [n_e][2] */, float *inv_a_odd_ri /* [n_o][2] */);
+
+/* Batched mixed precision: the low-precision GCR on a BLOCK of k Fields (csrc/gcr32_multi.hip), 1 <= k <= 16, columns interleaved
+ * as in every multi-vector.  `low` is a LowPrecisionGCR of the square form (mgcr_gcr32_create), Dirac or matrix form; its current
+ * inner parameters and k32 apply.
+ * mgcr_gcr32_apply_multi: column j of Y is y_j ~ A^-1 f_j from the fp32 restarted GCR.  The k inner solves advance in LOCKSTEP and
+ * share every launch: the fp32 slab is streamed once per step for all k columns.
+ * Rule M1: column j of Y, its step count and its rel_res (mgcr_gcr32_last_multi) are BIT-IDENTICAL to mgcr_op_apply(low, f_j) and
+ * mgcr_gcr32_last — for every k, every column position and whatever the other columns do.  Per column the kernels keep the single
+ * kernels' row-to-thread maps, grids, reduction trees and element-wise expressions (one copy of each, shared by both files).
+ * Freezing: every column has its own state (stop words, step count, <Ap_i, Ap_i>) and its own partial slabs.  A column stops on its
+ * tolerance, on an exactly zero <Ap, Ap> or on f_j = 0; a column that has stopped is frozen — every later store to it is masked.
+ * `active`: bit j set — column j takes part; bit j clear — column j performs 0 steps and y_j = 0 (the batched form of the gate the
+ * single apply gets from its outer solve; its rel_res is that of 0 steps).  Bits at or above k: MGCR_ERR_INVALID.
+ * Launch count: fixed, whatever the data — per step an apply, a dots (not in the step that opens a restart cycle), a build and an
+ * update launch, plus an entry and an exit launch: 4 max_iter + 2 - ceil(max_iter / restart) per batched apply.  No host round
+ * trip, no atomics, no graph capture.
+ * Storage: r, Ar, x and 2 * restart slot blocks of nv * k float2 (nv = n rounded up to 4), held planar (column c of a vector at
+ * [c nv, c nv + n), the single solve's layout per column), a second copy of r of nv * k float2 with the columns interleaved (what the
+ * k-wide matrix apply gathers from), the partial slabs and the states belong to the operator: allocated by the first batched apply
+ * of width k, reallocated — behind a stream synchronisation — when k or restart has changed, freed by mgcr_op_destroy.
+ * Counters (mgcr_stat): "gcr32_multi_applies" = batched applies enqueued, "gcr32_multi_steps" = the lockstep steps those enqueued
+ * (max_iter each); "gcr32_applies" and "gcr32_steps" do not move.
+ * MGCR_ERR_UNSUPPORTED: the even-odd form (mgcr_gcr32_create_eo).  MGCR_ERR_INVALID: not a low-precision GCR, a null handle, F and
+ * Y of different shape or the same block, rows != n, `active` bits at or above k.  mgcr_op_apply_multi, mgcr_gcr_solve_multi and
+ * the queues go on refusing the operator (above).
+ * mgcr_gcr32_last_multi: ONE synchronisation; steps performed and last fp32 |r| / |f| of each column of the last batched apply
+ * that was enqueued, by this call or by mgcr_gcr32_solve_multi (a solve in which no column was ever active enqueues none);
+ * MGCR_ERR_INVALID before the operator's first batched apply.
+ *
+ * mgcr_gcr32_solve_multi: the batched mixed solve, fp64 DEFECT CORRECTION around the k-wide inner solve.  Per column, driven by the
+ * host between launches: r = b - A x (without use_x0: x = 0, r = b); hist[j][0] = |r_j| / |b_j|; at outer step t = 1, 2, ... the
+ * active columns are those with |r_j|^2 > tol^2 |b_j|^2 (a column with b_j = 0 is never active and counts as converged at 0
+ * steps); when none is active or t > max_outer the solve ends; else E = mgcr_gcr32_apply_multi(low, R, active), x_j = x_j + e_j on
+ * the active columns, r_j = b_j - (A x)_j from the k-wide fp64 apply (mgcr_op_apply_multi), hist[j][t] = |r_j| / |b_j| and
+ * n_outer[j] = t for the active columns.  A column that has converged keeps its x, its history and its count.  One
+ * synchronisation per outer step (the k norms).  hist: [k][hist_cap] or NULL; converged[j] = 1 when column j's last residual meets
+ * the tolerance.
+ * Rule M2: x, history, n_outer and converged of column j are BIT-IDENTICAL to the same loop written with the single-Field entry
+ * points on column j alone — mgcr_op_apply(A), mgcr_add_scaled(r, b, -1, t), mgcr_norm2, mgcr_op_apply(low), mgcr_axpy(1, e, x) —
+ * wherever mgcr_op_apply_multi is bit-identical to the single apply: every storage form.
+ * A: whatever mgcr_op_apply_multi takes on one GPU, with dim == n.  MGCR_ERR_UNSUPPORTED: a MultiDiracOp or MultiEvenOddDiracOp (a
+ * shift per column against the one k32 would not contract), distributed operators, GCR or MG objects, a low-precision GCR as A, an
+ * even-odd `low`.  MGCR_ERR_INVALID: max_outer < 0, tol < 0, null handles, B and X of different shape or the same block, rows != n.
+ * The work blocks (R, E, A X) belong to `low` and are kept between calls while k stays. */
+int mgcr_gcr32_apply_multi(mgcr_op_t low, mgcr_mvec_t F, mgcr_mvec_t Y, uint32_t active /* bit j: column j takes part */);
+int mgcr_gcr32_last_multi(mgcr_op_t low, int32_t *n_iter /* [k] */, double *rel_res /* [k] */);   /* one synchronisation */
+int mgcr_gcr32_solve_multi(mgcr_op_t A, mgcr_op_t low, double tol, int32_t max_outer, int32_t use_x0,
+                           mgcr_mvec_t B, mgcr_mvec_t X, double *hist /* [k][hist_cap] or NULL */, int32_t hist_cap,
+                           int32_t *n_outer /* [k] */, int32_t *converged /* [k] */);
 
 /* ---- MG: src/MG.h, src/Mesh.h, src/SolverParam.h:38-59 ------------------------------------ */
 typedef struct mgcr_mg_param {

@@ -897,8 +897,47 @@ public:
         i.real_slab = real != 0;
         return i;
     }
+    // Blocks of k Fields (extension, mgcr_gcr32_apply_multi): Y_j ~ A^-1 F_j, the k fp32 inner solves advancing in lockstep — column
+    // j has the bits of operator()(F.column(j)).  active: bit j set, column j takes part; clear, it performs 0 steps and y_j = 0.
+    void inner_multi(const MultiField<num_type> &F, MultiField<num_type> &Y, uint32_t active) {
+        mgcr_detail::ok(mgcr_gcr32_apply_multi(op, F.device(), Y.device(), active), "LowPrecisionGCR::inner_multi");
+        last_k = F.ncols();
+    }
+    void inner_multi(const MultiField<num_type> &F, MultiField<num_type> &Y) { inner_multi(F, Y, (uint32_t)((1u << F.ncols()) - 1u)); }
+    // steps and last fp32 |r| / |f| per column of the last batched inner solve (one synchronisation)
+    std::vector<int> last_multi(std::vector<double> *rel_res = nullptr) {
+        int32_t it[16] = {};
+        double rel[16] = {};
+        mgcr_detail::ok(mgcr_gcr32_last_multi(op, it, rel), "LowPrecisionGCR::last_multi");
+        if (rel_res) rel_res->assign(rel, rel + last_k);
+        return std::vector<int>(it, it + last_k);
+    }
+    // The batched mixed solve A X = B (extension, mgcr_gcr32_solve_multi): fp64 defect correction, R = B - A X, X += inner_multi(R) on
+    // the columns that have not converged; column j has the bits of the same loop on column j alone.  Per column: last_history[j]
+    // (|r| / |b| per outer step), last_iterations[j], last_converged[j].
+    void solve_multi(Operator<num_type> &A, const MultiField<num_type> &B, MultiField<num_type> &X, double tol = 1e-10, int max_outer = 50,
+                     bool use_x0 = false) {
+        const int k = B.ncols(), cap = (max_outer >= 0 ? max_outer : 0) + 1;
+        std::vector<double> hist((size_t)k * cap, 0.);
+        std::vector<int32_t> it((size_t)k, 0), conv((size_t)k, 0);
+        mgcr_detail::ok(mgcr_gcr32_solve_multi(A.handle(), op, tol, max_outer, use_x0 ? 1 : 0, B.device(), X.device(), hist.data(), cap, it.data(), conv.data()),
+                        "LowPrecisionGCR::solve_multi");
+        for (int32_t v : it)
+            if (v > 0) last_k = k;   // (a solve in which no column was ever active enqueues no batched apply)
+        last_history.assign((size_t)k, std::vector<double>());
+        last_iterations.assign(it.begin(), it.end());
+        last_converged.assign((size_t)k, false);
+        for (int j = 0; j < k; j++) {
+            last_history[(size_t)j].assign(hist.begin() + (size_t)j * cap, hist.begin() + (size_t)j * cap + it[(size_t)j] + 1);
+            last_converged[(size_t)j] = conv[(size_t)j] != 0;
+        }
+    }
+    std::vector<std::vector<double>> last_history;   // of solve_multi, column j relative to |b_j|
+    std::vector<int> last_iterations;
+    std::vector<bool> last_converged;
 
 private:
+    int last_k = 0;
     static std::complex<double> not_stored() { std::fprintf(stderr, "LowPrecisionGCR stores an fp32 copy on the device only\n"); std::abort(); }
 
 protected:

@@ -172,6 +172,10 @@ _SIGS = {
     "mgcr_gcr32_eo_info": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "mgcr_gcr32_eo_diag": (C.c_int, [_vp, _vp, _vp]),
+    "mgcr_gcr32_apply_multi": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
+    "mgcr_gcr32_last_multi": (C.c_int, [_vp, C.POINTER(C.c_int32), _dp]),
+    "mgcr_gcr32_solve_multi": (C.c_int, [_vp, _vp, C.c_double, C.c_int32, C.c_int32, _vp, _vp, _dp, C.c_int32, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32)]),
     "mgcr_timer_start": (C.c_int, []),
     "mgcr_timer_stop": (C.c_int, [_dp]),
 }

@@ -933,6 +933,49 @@ class LowPrecisionGCR(Operator):
         check(_lib.lib().mgcr_gcr32_info(self.h, C.byref(n), C.byref(w), C.byref(t), C.byref(real), C.byref(b)))
         return dict(n=n.value, ell_width=w.value, tail_rows=t.value, real_slab=bool(real.value), stored_bytes=b.value)
 
+    # ---- blocks of k Fields: the k inner solves in lockstep, and fp64 defect correction around them (mgcr_gcr32_apply_multi) ----
+    def inner_multi(self, F, Y=None, active=None):
+        """Y_j ~ A^-1 F_j for the k columns of the MultiField F, the k fp32 inner solves advancing in lockstep; column j has the bits
+        of self(F.column(j)) (Rule M1).  active: an iterable of k truth values, or a bit mask — a column that is not active performs 0
+        steps and gets y = 0; None: every column."""
+        if Y is None:
+            Y = MultiField.like(F)
+        if active is None:
+            mask = (1 << F.k) - 1
+        elif isinstance(active, (int, np.integer)):
+            mask = int(active)
+        else:
+            mask = sum(1 << j for j, a in enumerate(active) if a)
+        if mask < 0 or mask >> 32:
+            raise MgcrError(1, "LowPrecisionGCR.inner_multi: active = %r is not a mask of at most 16 columns" % (active,))
+        check(_lib.lib().mgcr_gcr32_apply_multi(self.h, F.h, Y.h, mask))
+        self._last_k = F.k
+        return Y
+
+    def last_multi(self):
+        """[(steps, last fp32 |r| / |f|)] per column of the last batched inner solve that was enqueued, by inner_multi or by
+        solve_multi (a solve in which no column was ever active enqueues none): one synchronisation."""
+        it, rel = (C.c_int32 * 16)(), (C.c_double * 16)()
+        check(_lib.lib().mgcr_gcr32_last_multi(self.h, it, rel))
+        return [(int(it[j]), float(rel[j])) for j in range(getattr(self, "_last_k", 0))]
+
+    def solve_multi(self, A, B, X, tol=1e-10, max_outer=50, use_x0=False):
+        """The batched mixed solve A X = B: fp64 defect correction, R = B - A X, X += inner_multi(R), on the columns that have not
+        converged (mgcr_gcr32_solve_multi; column j has the bits of the same loop on column j alone, Rule M2).  Sets last_history
+        (one array of |r| / |b| per column), last_iterations and last_converged (lists)."""
+        k = B.k
+        cap = int(max_outer) + 1 if max_outer >= 0 else 1
+        hist = np.zeros((k, cap), np.float64)
+        it, conv = (C.c_int32 * k)(), (C.c_int32 * k)()
+        check(_lib.lib().mgcr_gcr32_solve_multi(A.h, self.h, float(tol), int(max_outer), 1 if use_x0 else 0, B.h, X.h,
+                                                hist.ctypes.data_as(C.POINTER(C.c_double)), cap, it, conv))
+        self.last_iterations = [int(v) for v in it]
+        if max(self.last_iterations) > 0:
+            self._last_k = k
+        self.last_converged = [bool(v) for v in conv]
+        self.last_history = [hist[j, : it[j] + 1].copy() for j in range(k)]
+        return X
+
 
 class LowPrecisionEvenOddGCR(LowPrecisionGCR):
     """Mixed precision on the even-odd Schur system: an fp32 copy of S = diag(a_e) - c^2 H_eo diag(1/a_o) H_oe of `mat` (a Sparse that

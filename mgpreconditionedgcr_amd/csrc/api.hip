@@ -290,6 +290,8 @@ int mgcr_stat(const char *name, int64_t *value) {
     else if (!strcmp(name, "evenodd_block_fused_steps")) *value = eo_block_fused_step_count();
     else if (!strcmp(name, "gcr32_applies")) *value = gcr32_apply_count();
     else if (!strcmp(name, "gcr32_steps")) *value = gcr32_step_count();
+    else if (!strcmp(name, "gcr32_multi_applies")) *value = gcr32_multi_stat(0);
+    else if (!strcmp(name, "gcr32_multi_steps")) *value = gcr32_multi_stat(1);
     else { set_error("mgcr_stat: unknown counter '%s'", name); return MGCR_ERR_INVALID; }
     return MGCR_OK;
 }
@@ -457,7 +459,7 @@ int mgcr_bench_op_apply(mgcr_op_t op, mgcr_vec_t x, mgcr_vec_t y, int32_t reps, 
 }
 
 // ---- blocks of k Fields: k-wide apply (spmm.hip), batched GCR (gcr_multi.hip) ------------------------------------------
-static int apply_multi_checks(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y, const char *who) {
+extern "C++" int mgcr::op_apply_multi_checks(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y, const char *who) {   // (C++ linkage: internal, not part of the ABI)
     MGCR_CHECK(op && x && y, MGCR_ERR_INVALID, "%s: null argument", who);
     MGCR_REFUSE_EVENODD(op, who);
     MGCR_REFUSE_GCR32(op, who);
@@ -478,7 +480,7 @@ static int apply_multi_checks(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y, const 
 
 int mgcr_op_apply_multi(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y) {
     MGCR_TRY(require_ctx());
-    MGCR_TRY(apply_multi_checks(op, x, y, "mgcr_op_apply_multi"));
+    MGCR_TRY(op_apply_multi_checks(op, x, y, "mgcr_op_apply_multi"));
     LOCK();
     return op_apply_multi_raw(op, x->d, y->d, x->n, x->k);
 }
@@ -486,7 +488,7 @@ int mgcr_op_apply_multi(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y) {
 int mgcr_bench_op_apply_multi(mgcr_op_t op, mgcr_mvec_t x, mgcr_mvec_t y, int32_t reps, double *ms_avg) {
     MGCR_TRY(require_ctx());
     MGCR_CHECK(reps > 0 && ms_avg, MGCR_ERR_INVALID, "mgcr_bench_op_apply_multi: bad argument");
-    MGCR_TRY(apply_multi_checks(op, x, y, "mgcr_bench_op_apply_multi"));
+    MGCR_TRY(op_apply_multi_checks(op, x, y, "mgcr_bench_op_apply_multi"));
     LOCK();
     Context &c = ctx();
     MGCR_TRY(op_apply_multi_raw(op, x->d, y->d, x->n, x->k));  // warm-up

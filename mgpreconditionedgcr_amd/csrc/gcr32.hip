@@ -18,6 +18,7 @@
 // unchanged partials and ends in the same way.  Nothing is exchanged inside a launch; no atomics, no waits.
 #include <cmath>
 
+#include "gcr32_elem_dev.h"
 #include "gcr32_row_dev.h"
 #include "gcr32_state.h"
 
@@ -40,9 +41,6 @@ void gcr32_release() {
     if (g_dev_counts) hipFree(g_dev_counts);
     g_dev_counts = nullptr;
 }
-
-__device__ __forceinline__ float uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-__device__ __forceinline__ double norm2d(float re, float im) { return (double)re * (double)re + (double)im * (double)im; }
 
 // ---- entry: r = fp32(f), x = 0, |f|^2 (of the rounded values: what the iteration sees) -------------------------------------------
 __global__ void __launch_bounds__(RED_THREADS) g32_entry_kernel(const cplx *__restrict__ f, float *__restrict__ r, float *__restrict__ x, int64_t n,
@@ -113,9 +111,7 @@ __global__ void __launch_bounds__(RED_THREADS, (ND <= 5 ? 8 : 4))
             g32_row_sum<REAL>(A, r, tile, row, sx, sy);
             c32 y = make_float2(sx, sy);
             if (dirac) {   // y = x - k32 s
-                const c32 own = r[row];
-                const float kx = k32.x * sx - k32.y * sy, ky = k32.x * sy + k32.y * sx;
-                y = make_float2(own.x - kx, own.y - ky);
+                y = g32_dirac_shift(k32, r[row], sx, sy);
             }
             ar[row] = y;
             if constexpr (ND > 0) {
@@ -123,9 +119,7 @@ __global__ void __launch_bounds__(RED_THREADS, (ND <= 5 ? 8 : 4))
 #pragma unroll
                 for (int j = 0; j < ND; j++) {   // <Ap_j, Ar> = sum conj(Ap_j) Ar
                     const c32 a = aps[(int64_t)j * nv + row];
-                    const double ax = (double)a.x, ay = (double)a.y;
-                    acc[2 * j] += ax * yx + ay * yy;
-                    acc[2 * j + 1] += ax * yy - ay * yx;
+                    g32_beta_dot(a.x, a.y, yx, yy, acc[2 * j], acc[2 * j + 1]);
                 }
             }
         }
@@ -133,38 +127,8 @@ __global__ void __launch_bounds__(RED_THREADS, (ND <= 5 ? 8 : 4))
     if constexpr (ND > 0) block_sums_to_slab<2 * ND>(acc, lds, partsB, blockIdx.x);
 }
 
-// beta_j = <Ap_j, Ar> / <Ap_j, Ap_j>, j < ND, from the apply's partial slab: folded 8 directions at a time, formed in fp64, rounded once
-// and left in LDS (beta[2 j], beta[2 j + 1]; the caller's barrier publishes them): held in registers, 2 ND of them and the 2 ND + 2 lane
-// addresses of an unrolled direction loop do not fit 64 VGPRs from 2 directions on
-template <int ND, int J0 = 0>
-__device__ __forceinline__ void fold_betas(const double *__restrict__ partsB, int nblk, const double *__restrict__ den, float *beta, double *lds) {
-    constexpr int C = ND - J0 < 8 ? ND - J0 : 8;
-    double v[2 * C];
-    fold_partials<2 * C>(partsB + (size_t)2 * J0 * RED_MAX_BLOCKS, nblk, RED_MAX_BLOCKS, v, lds);
-#pragma unroll
-    for (int j = 0; j < C; j++) {
-        const double d = den[J0 + j];
-        if (threadIdx.x == 0) {
-            beta[2 * (J0 + j)] = (float)(v[2 * j] / d);
-            beta[2 * (J0 + j) + 1] = (float)(v[2 * j + 1] / d);
-        }
-    }
-    if constexpr (J0 + C < ND) fold_betas<ND, J0 + C>(partsB, nblk, den, beta, lds);
-}
-
 // ---- build: beta_j, p = r - sum beta_j p_j and Ap = Ar - sum beta_j Ap_j into slot ND, <Ap, Ap> and <Ap, r> ------------------------
-// o -= beta v, un-fused
-__device__ __forceinline__ void g32_sub_scaled(float bx, float by, float vx, float vy, float &ox, float &oy) {
-    ox -= bx * vx - by * vy;
-    oy -= bx * vy + by * vx;
-}
-__device__ __forceinline__ void g32_build_dots(float qx, float qy, float rx, float ry, double (&acc)[3]) {
-    const double dqx = (double)qx, dqy = (double)qy, drx = (double)rx, dry = (double)ry;
-    acc[0] += dqx * dqx + dqy * dqy;
-    acc[1] += dqx * drx + dqy * dry;
-    acc[2] += dqx * dry - dqy * drx;
-}
-
+// (the element-wise expressions — g32_sub_scaled, g32_build_dots, g32_update_one, fold_betas — are gcr32_elem_dev.h's)
 template <int ND>
 __global__ void __launch_bounds__(RED_THREADS, (ND <= 5 ? 8 : 4))
     g32_build_kernel(const float *__restrict__ r, const float *__restrict__ ar, float *__restrict__ ps, float *__restrict__ aps, int64_t nv, int64_t n,
@@ -222,15 +186,6 @@ __global__ void __launch_bounds__(RED_THREADS, (ND <= 5 ? 8 : 4))
 }
 
 // ---- update: alpha, x += alpha p, r -= alpha Ap, |r|^2, the step counter -------------------------------------------------------------
-__device__ __forceinline__ void g32_update_one(float ax, float ay, float px, float py, float qx, float qy, float &xx, float &xy, float &rx, float &ry,
-                                               double &acc) {
-    xx += ax * px - ay * py;
-    xy += ax * py + ay * px;
-    rx -= ax * qx - ay * qy;
-    ry -= ax * qy + ay * qx;
-    acc += norm2d(rx, ry);
-}
-
 __global__ void __launch_bounds__(RED_THREADS, 8)
     g32_update_kernel(float *__restrict__ x, float *__restrict__ r, const float *__restrict__ p, const float *__restrict__ ap, int64_t n,
                       const double *__restrict__ partsA, int nblkA, G32Dev *__restrict__ st, int it, int slot, double *__restrict__ S2, SKIP_ARGS) {
@@ -298,6 +253,7 @@ void gcr32_destroy(Gcr32State *g) {
     hipFree(g->r); hipFree(g->ar); hipFree(g->x); hipFree(g->ps); hipFree(g->aps);
     hipFree(g->S2); hipFree(g->partsA); hipFree(g->partsB); hipFree(g->st);
     gcr32_eo_destroy(g->eo);
+    gcr32_multi_destroy(g->mw);
     delete g;
 }
 int64_t gcr32_nnz(const Gcr32State *g) { return g->nnz; }

@@ -31,6 +31,7 @@ struct G32Mat {
 };
 
 struct Gcr32EoState;   // gcr32_eo.hip
+struct Gcr32MultiState;   // gcr32_multi.hip
 
 struct Gcr32State {
     int64_t n = 0, nv = 0, nnz = 0, n_tail_rows = 0, stored_bytes = 0;
@@ -49,6 +50,7 @@ struct Gcr32State {
     double *partsB = nullptr;   // [2 * GCR32_MAX_RESTART][RED_MAX_BLOCKS]: <Ap_j, Ar>
     G32Dev *st = nullptr;
     Gcr32EoState *eo = nullptr;   // the even-odd form (mgcr_gcr32_create_eo): n = n_e, the matrix fields above are unused (owned)
+    Gcr32MultiState *mw = nullptr;   // the k-wide storage of mgcr_gcr32_apply_multi, made by its first call (owned)
 };
 
 #define SKIP_ARGS const int *__restrict__ skip, int skip_it
@@ -95,5 +97,8 @@ int gcr32_eo_launch_apply(Gcr32State *g, int nd, int it, SkipRef sk);   // stage
 int gcr32_eo_set_k(Gcr32State *g, const double k_ri[2], const char *who);   // refused: nothing changes
 // the slot check's questions about a preconditioner in even-odd form and about the operator of the solve
 int gcr32_eo_slot_check(const Gcr32EoState *e, const Op *A);
+
+// ---- gcr32_multi.hip: the k-wide lockstep inner solve ------------------------------------------------------------------------------
+void gcr32_multi_destroy(Gcr32MultiState *m);
 
 }  // namespace mgcr

@@ -464,6 +464,7 @@ void gcr32_release();   // the device-side counters (mgcr_finalize)
 int gcr32_slot_check(const mgcr_gcr_param *p, const Op *A);   // the preconditioner slots of an fp64 solve on A (A may be null)
 int64_t gcr32_apply_count();  // applies that ran on the device (not silenced by an outer solve that was over): one synchronisation
 int64_t gcr32_step_count();   // the inner steps those enqueued
+int64_t gcr32_multi_stat(int which);   // gcr32_multi.hip — 0: batched applies enqueued, 1: the lockstep steps those enqueued
 
 // ---- mvec.hip / spmm.hip / gcr_multi.hip: blocks of k Fields ------------------------------------
 int mv_copy(cplx *dst, const cplx *src, int64_t n, int k);
@@ -507,3 +508,8 @@ int gcr_small_run(Op *A, const mgcr_gcr_param &p, int storage, int restart, cons
 struct mgcr_vec_s : mgcr::Vec {};
 struct mgcr_op_s : mgcr::Op {};
 struct mgcr_mvec_s : mgcr::MVec {};
+
+// api.hip: what mgcr_op_apply_multi asks of (op, x, y) before it launches anything (mgcr_gcr32_solve_multi asks the same of its A)
+namespace mgcr {
+int op_apply_multi_checks(mgcr_op_s *op, mgcr_mvec_s *x, mgcr_mvec_s *y, const char *who);
+}
