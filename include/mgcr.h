@@ -386,7 +386,9 @@ int mgcr_set_option(const char *name, int value, int *previous);
  * not, "evenodd_block_fused_steps" = its GCR steps whose last apply launch took the step's beta dot products (Rule 3b),
  * "gcr32_applies" = applies of a low-precision GCR (mgcr_gcr32_create) that ran on the device, "gcr32_steps" = the inner steps those
  * enqueued (both kept on the device: one synchronisation per query), "gcr32_multi_applies" = batched applies of a low-precision
- * GCR (mgcr_gcr32_apply_multi, mgcr_gcr32_solve_multi) enqueued, "gcr32_multi_steps" = the lockstep steps those enqueued. */
+ * GCR (mgcr_gcr32_apply_multi, mgcr_gcr32_solve_multi) enqueued, "gcr32_multi_steps" = the lockstep steps those enqueued,
+ * "multi_flex_solves" = flexible batched solves (mgcr_gcr_solve_multi with a right preconditioner) completed — "multi_solves" counts
+ * them as well, and the batched applies they enqueue move "gcr32_multi_applies" and "gcr32_multi_steps". */
 int mgcr_stat(const char *name, int64_t *value);
 
 /* Self-test of the hardware behaviour the one-launch solver paths (csrc/gcr_resident.hip, gcr_stepbuild.hip) build on: inside
@@ -434,9 +436,11 @@ int mgcr_eo_multi_solve(mgcr_op_t op, const mgcr_gcr_param *param, mgcr_mvec_t B
  * whatever stops the single solve) is FROZEN — its x, residual, history and iteration count no longer change — while the
  * others go on; the solve ends when every column has stopped or at max_iter.  x is updated in place; use_x0 as in
  * mgcr_gcr_solve.
- * Supported: restart mode (restart != 0, cycles of at most 16 steps), unpreconditioned, on the operators of
+ * Supported: restart mode (restart != 0, cycles of at most 16 steps), unpreconditioned — or with a flexible right preconditioner,
+ * see "Flexible batched GCR" below —, on the operators of
  * mgcr_op_apply_multi.  MGCR_ERR_UNSUPPORTED: truncation != 0, restart == 0, restart > 16 (with max_iter >= 16), a left or
- * right preconditioner, flexible, profile_spmv, distributed operators, GCR / MG objects as the operator.
+ * right preconditioner, flexible (other than the flexible right preconditioners of the block below), profile_spmv, distributed
+ * operators, GCR / MG objects as the operator.
  * Arithmetic: the lean restart cycle of mgcr_gcr_solve per column, with the same rows per thread, grid size, summation trees
  * and folds: history, iteration count, convergence flag and x of column j are BIT-IDENTICAL to mgcr_gcr_solve(A, param, rhs_j)
  * with default options, for operators whose mgcr_op_xr_fuse_kind is 0 or 1 and more rows than the small-solve limit
@@ -444,7 +448,46 @@ int mgcr_eo_multi_solve(mgcr_op_t op, const mgcr_gcr_param *param, mgcr_mvec_t B
  * and mgcr_op_xr_fuse_kind == 2 (grids from 182^3: |r'|^2 and the start-up sums run over a banded row map) — the batched solve
  * sums in the plain row order and the results agree to rounding only.  There is no one-workgroup batched form.
  * The work vectors (2 + 2 * min(restart, max_iter + 1) blocks of n x k) are kept by the library from one batched solve to the
- * next while n, k and the cycle length stay the same, and are freed by mgcr_finalize. */
+ * next while n, k and the cycle length stay the same, and are freed by mgcr_finalize.
+ *
+ * Flexible batched GCR: mgcr_gcr_solve_multi with param->flexible == 1 and param->right_precond = M (csrc/gcr_multi.hip, the device
+ * side csrc/gcr_multi_flex.hip).  Slot kinds:
+ *   (a) a LowPrecisionGCR of the square form (mgcr_gcr32_create, Dirac or matrix form) with n equal to the block's rows: it runs as
+ *       the k-wide LOCKSTEP inner solve of mgcr_gcr32_apply_multi, the fp32 slab streamed once per inner step for all k columns.  The
+ *       preconditioner keeps its own k32 — a preconditioner at another k is legitimate, so a MultiDiracOp as A is accepted;
+ *   (b) any operator that mgcr_op_apply_multi takes on one GPU with dim n and n rows (Sparse, DiracOp, HierarchicalSparse), applied
+ *       k-wide to the residual block.
+ * A: whatever mgcr_gcr_solve_multi takes unpreconditioned on n rows, a MultiDiracOp included.
+ * Per column the recurrences are the single solve's lean flexible cycle: r0 = b (use_x0: b - A x0), Z = M r0 with every column
+ * taking part, P0 = Z, Ap0 = A P0; per step alpha, r -= alpha Ap IN PLACE (the residual ring is not written), D = M r into the slot
+ * of the next direction — into a block of its own on the step that closes a cycle —, A D, the beta dots, the build; there is no
+ * preconditioner behind a solve's last update.
+ * Rule F: history, iteration count, convergence flag and x of column j are BIT-IDENTICAL to mgcr_gcr_solve(A_j, param, rhs_j) with
+ * the same preconditioner in the slot, on column j alone (A_j = DiracOp(D, ks[j]) for a MultiDiracOp) — for every k, every column
+ * position and whatever the other columns do; default options, mgcr_op_xr_fuse_kind 0 or 1.  The small-solve limit does not enter:
+ * a single solve with any preconditioner never takes the one-workgroup path (gcr_small_eligible returns false for a left or right
+ * preconditioner and for profile_spmv) nor the resident one-launch path, so Rule F holds at every n.
+ * The mask: a column that has stopped is FROZEN with x updates still pending in the slots; the preconditioner stores D to the
+ * columns that are still active at the step only — a frozen column's slots keep their bits until the pending updates are applied.
+ * The gate: behind the inner solve's entry, one launch per outer step evaluates per column the outer solve's own stopping test
+ * (the fold of the step's |r|^2 partials, |b|^2, tol^2: the solver's fold and expression, the bits of the single solve's gate) and
+ * cuts the inner solve of a column that is frozen, or about to end on this residual, to 0 steps; a gated column that is still
+ * active gets D = 0, as in the single solve.  mgcr_gcr32_last_multi then reports 0 steps for it.  Kind (b) is not gated.
+ * Launches per outer step, whatever the data: the unpreconditioned step's, plus for (a) the batched apply's
+ * 4 m + 2 - ceil(m / restart_inner) (m = the inner max_iter) plus 1, the gate; for (b) the k-wide apply of M plus, off the closing
+ * step, 1 masked copy.  No host round trip is added: the host polls every check_every steps as before.  The unpreconditioned
+ * solve enqueues exactly the launches it enqueued before.
+ * Storage: one more n x k block (3 + 2 * min(restart, max_iter + 1) in all), allocated only by a flexible solve; storage made by a
+ * flexible solve serves an unpreconditioned one at the same n, k and cycle length, not the reverse.  (a) also uses the operator's own
+ * k-wide storage (mgcr_gcr32_apply_multi).
+ * Counters (mgcr_stat): "multi_flex_solves" = flexible batched solves completed ("multi_solves" counts them too);
+ * "gcr32_multi_applies" and "gcr32_multi_steps" count the applies and lockstep steps these solves enqueue.
+ * MGCR_ERR_UNSUPPORTED: a left preconditioner; a right preconditioner with flexible == 0; flexible == 1 without one; a GCR or MG object
+ * in either slot; an even-odd `low` (mgcr_gcr32_create_eo); a MultiDiracOp or MultiEvenOddDiracOp in the slot; an even-odd
+ * preconditioned DiracOp in the slot; a low-precision GCR as A; profile_spmv, distributed operators (A or M), truncation or full
+ * mode, cycles longer than 16.  MGCR_ERR_INVALID: a preconditioner whose dimension is not n or that is not square.  Nothing is
+ * written to x in any refused call.  mgcr_eo_multi_solve, mgcr_gcr_solve_queue and mgcr_eo_solve_queue go on refusing every
+ * preconditioner. */
 int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t rhs, mgcr_mvec_t x, double *hist, int32_t hist_cap,
                          int32_t *n_iter, int32_t *converged);
 /* Queued batched GCR: nsys independent systems (any nsys) stream through `width` <= 16 slots (columns) of ONE batched restarted solve
@@ -549,7 +592,8 @@ int mgcr_gcr_set_x0(mgcr_op_t gcr, mgcr_vec_t x0);
  * differs from the outer operator's: MGCR_ERR_INVALID; a distributed outer operator: MGCR_ERR_UNSUPPORTED.
  * Refused with MGCR_ERR_UNSUPPORTED: as the system operator of any solve (mgcr_gcr_solve, mgcr_gcr_create, mgcr_gcr_set_operator),
  * mgcr_mg_create, mgcr_op_apply_multi, mgcr_gcr_solve_multi, mgcr_gcr_solve_queue, mgcr_eo_solve_queue and the storage queries
- * (mgcr_op_stored_bytes / storage_format / ell_layout / xr_fuse_kind / halo_kind; ask mgcr_gcr32_info).
+ * (mgcr_op_stored_bytes / storage_format / ell_layout / xr_fuse_kind / halo_kind; ask mgcr_gcr32_info).  mgcr_gcr_solve_multi refuses
+ * it as its operator A; the right_precond slot of that solve, flexible = 1, takes it (the "Flexible batched GCR" block there).
  * All storage (r, Ar, x, 2 * restart slots, slabs, state) belongs to the operator: allocated here or by mgcr_gcr32_set_param, freed by
  * mgcr_op_destroy.  k travels in the kernel arguments of every launch: what is already enqueued keeps the old value.
  * In the right_precond slot the apply that follows an outer step's residual update is handed that solve's own stopping test (the
@@ -594,7 +638,8 @@ int mgcr_gcr32_last(mgcr_op_t op, int32_t *n_iter, double *rel_res);
  * Slot check, in addition to mgcr_gcr32_create's: when the operator of the solve is itself an even-odd operator of the scalar forms,
  * its n and its parity vector must equal this operator's (MGCR_ERR_INVALID: another colouring would still converge, slowly and
  * silently); when it carries site blocks: MGCR_ERR_UNSUPPORTED.  k is NOT compared — a preconditioner at another k is legitimate.
- * The batched and queued solves refuse any preconditioner. */
+ * The batched and queued solves refuse any preconditioner of this even-odd form: mgcr_eo_multi_solve and the queues take none at
+ * all, mgcr_gcr_solve_multi the square form of mgcr_gcr32_create only (its "Flexible batched GCR" block). */
 int mgcr_gcr32_create_eo(int64_t n, const int64_t *rowptr, const int64_t *col, const double *val_ri,
                          const int8_t *parity /* NULL: two-colour */, const double *k_ri /* NULL: matrix form */,
                          const mgcr_gcr_param *inner, mgcr_op_t *out);
@@ -627,7 +672,8 @@ int mgcr_gcr32_eo_diag(mgcr_op_t op, float *a_even_ri /* [n_e][2] */, float *inv
  * (max_iter each); "gcr32_applies" and "gcr32_steps" do not move.
  * MGCR_ERR_UNSUPPORTED: the even-odd form (mgcr_gcr32_create_eo).  MGCR_ERR_INVALID: not a low-precision GCR, a null handle, F and
  * Y of different shape or the same block, rows != n, `active` bits at or above k.  mgcr_op_apply_multi, mgcr_gcr_solve_multi and
- * the queues go on refusing the operator (above).
+ * the queues go on refusing the operator (above) as the operator they apply or solve on; mgcr_gcr_solve_multi takes it in its
+ * right_precond slot with flexible = 1, where this batched apply is the inner solve.
  * mgcr_gcr32_last_multi: ONE synchronisation; steps performed and last fp32 |r| / |f| of each column of the last batched apply
  * that was enqueued, by this call or by mgcr_gcr32_solve_multi (a solve in which no column was ever active enqueues none);
  * MGCR_ERR_INVALID before the operator's first batched apply.

@@ -760,8 +760,11 @@ public:
         std::ofstream file("../../data/out_data/convergence.txt");  // :168 (silently a no-op when the directory is absent)
         for (int i = 0; i <= it; i++) file << i << "\t" << history[(size_t)i] << "\n";
     }
-    // k independent solves A x_j = rhs_j in lockstep (extension, mgcr_gcr_solve_multi: restart mode, unpreconditioned; the
-    // operator a matrix, a DiracOp or a MultiDiracOp).  X is updated in place; per column: last_history[j][i] = the value
+    // k independent solves A x_j = rhs_j in lockstep (extension, mgcr_gcr_solve_multi: restart mode; the operator a matrix, a
+    // DiracOp or a MultiDiracOp).  Unpreconditioned, or — the flexible batched GCR — with GCR_Param::right_precond = M and
+    // flexible = true: M a LowPrecisionGCR of the square form, which runs as the k-wide lockstep inner solve, or a Sparse, DiracOp
+    // or HierarchicalSparse, applied k-wide to the residual block (Rule F of mgcr.h; M must outlive the solve, as in solve()).
+    // X is updated in place; per column: last_history[j][i] = the value
     // solve() would print at step i, last_iterations[j], last_converged[j] — the bits of solve() on that column alone.
     void solve_multi(const MultiField<num_type> &rhs, MultiField<num_type> &x) {
         if (!A_operator) { std::fprintf(stderr, "GCR has no operator (call initialise first)\n"); std::abort(); }

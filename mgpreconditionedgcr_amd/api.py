@@ -840,16 +840,23 @@ class GCR(Operator):
         return x
 
     def solve_multi(self, RHS, X):
-        """k independent solves A x_j = rhs_j in lockstep (mgcr_gcr_solve_multi; restart mode, unpreconditioned).  X is updated
-        in place; last_history (k arrays), last_iterations and last_converged (lists) are kept per column."""
+        """k independent solves A x_j = rhs_j in lockstep (mgcr_gcr_solve_multi; restart mode).  Unpreconditioned, or — the flexible
+        batched GCR — with GCR_Param(..., solver_r=M, flexible=True): M a LowPrecisionGCR of the square form, which runs as the k-wide
+        lockstep inner solve, or an operator that apply_multi takes (Sparse, DiracOp, HierarchicalSparse), applied k-wide to the
+        residual block.  Column j has the bits of solve() on column j alone with the same M in the slot (Rule F of include/mgcr.h).
+        X is updated in place; last_history (k arrays), last_iterations and last_converged (lists) are kept per column."""
         if self.A is None:
             raise MgcrError(1, "GCR has no operator (call initialise first)")
         k = RHS.k
+        if self.param.right_precond is not None and not any(o is self.param.right_precond for o in self._keep):
+            self._keep.append(self.param.right_precond)   # (a preconditioner set on the param after construction lives as long as the solver)
         cap = max(self.param.max_iter, 1) + 1
         hist = np.zeros((k, cap), np.float64)
         it, conv = (C.c_int32 * k)(), (C.c_int32 * k)()
         pc = self.param._c()
         check(_lib.lib().mgcr_gcr_solve_multi(self.A.h, C.byref(pc), RHS.h, X.h, hist.ctypes.data, cap, it, conv))
+        if isinstance(self.param.right_precond, LowPrecisionGCR):
+            self.param.right_precond._last_k = k   # last_multi() of the preconditioner: the k-wide inner solve this solve enqueued last
         self.last_iterations = [int(v) for v in it]
         self.last_converged = [bool(v) for v in conv]
         self.last_history = [hist[j, : it[j] + 1].copy() for j in range(k)]

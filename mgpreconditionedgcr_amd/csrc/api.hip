@@ -278,6 +278,7 @@ int mgcr_stat(const char *name, int64_t *value) {
     else if (!strcmp(name, "halo_split_exchanges")) *value = dist_halo_split_count();
     else if (!strcmp(name, "pw_tail_folds")) *value = comm_pw_tail_count();
     else if (!strcmp(name, "multi_solves")) *value = gcr_multi_solve_count();
+    else if (!strcmp(name, "multi_flex_solves")) *value = gcr_multi_flex_solve_count();
     else if (!strcmp(name, "queue_solves")) *value = gcr_queue_stat(0);
     else if (!strcmp(name, "queue_admissions")) *value = gcr_queue_stat(1);
     else if (!strcmp(name, "queue_steps")) *value = gcr_queue_stat(2);
@@ -511,8 +512,11 @@ int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t r
     MGCR_CHECK(param->truncation >= 0 && param->restart >= 0 && param->max_iter >= 0, MGCR_ERR_INVALID, "negative GCR parameter");
     MGCR_CHECK(param->truncation == 0, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: truncation mode is not supported (restart mode only)");
     MGCR_CHECK(param->restart != 0, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: restart mode only (restart != 0)");
-    MGCR_CHECK(!param->left_precond && !param->right_precond, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: preconditioners are not supported");
-    MGCR_CHECK(!param->flexible && !param->profile_spmv, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: flexible / profile_spmv are not supported");
+    MGCR_CHECK(!param->left_precond, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: a left preconditioner is not supported");
+    MGCR_CHECK(!param->right_precond || param->flexible, MGCR_ERR_UNSUPPORTED,
+               "mgcr_gcr_solve_multi: a right preconditioner is supported in flexible mode only (set flexible = 1)");
+    MGCR_CHECK(!param->flexible || param->right_precond, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: flexible without a right preconditioner is not supported");
+    MGCR_CHECK(!param->profile_spmv, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: profile_spmv is not supported");
     MGCR_CHECK(A->kind != OP_GCR && A->kind != OP_MG, MGCR_ERR_UNSUPPORTED, "mgcr_gcr_solve_multi: the operator must be a matrix");
     {
         const Op *b0 = op_matrix(A);
@@ -527,6 +531,20 @@ int mgcr_gcr_solve_multi(mgcr_op_t A, const mgcr_gcr_param *param, mgcr_mvec_t r
                "mgcr_gcr_solve_multi: the MultiDiracOp carries %d hopping parameters, the blocks have %d columns", A->nk, (int)x->k);
     MGCR_CHECK(A->kind != OP_DIRAC_EO_MULTI || x->k == A->nk, MGCR_ERR_INVALID,
                "mgcr_gcr_solve_multi: the MultiEvenOddDiracOp carries %d hopping parameters, the blocks have %d columns", A->nk, (int)x->k);
+    if (mgcr_op_t M = param->right_precond) {   // flexible: a square low-precision GCR, or whatever mgcr_op_apply_multi takes, on dim rows
+        const char *who = "mgcr_gcr_solve_multi: right_precond";
+        if (M->kind == OP_GCR32) {
+            MGCR_TRY(gcr32_multi_slot_check(M, A->dim, who));
+        } else {
+            MGCR_CHECK(M->kind != OP_DIRAC_MULTI && M->kind != OP_DIRAC_EO_MULTI, MGCR_ERR_UNSUPPORTED,
+                       "%s: an operator with one hopping parameter per column has no single-Field counterpart in the slot", who);
+            mgcr_mvec_s out;   // the shape M would write: the checks of mgcr_op_apply_multi, nothing is applied
+            out.n = M->nrow ? M->nrow : M->dim;
+            out.k = rhs->k;
+            MGCR_TRY(op_apply_multi_checks(M, rhs, &out, who));
+            MGCR_CHECK(out.n == A->dim, MGCR_ERR_INVALID, "%s: the preconditioner must be square, it has %lld rows", who, (long long)out.n);
+        }
+    }
     LOCK();
     return gcr_multi_run(A, *param, rhs->d, x->d, x->n, x->k, hist, hist_cap, n_iter, converged);
 }

@@ -428,7 +428,10 @@ static int g32m_launch(void (*kernel)(KA...), int gx, int gy, int gz, AA... args
     return MGCR_OK;
 }
 
-static int gcr32_apply_multi(Gcr32State *g, const cplx *f, cplx *y, int k, unsigned active) {
+// gate != nullptr (the flexible batched solve, gcr_multi.hip): behind the entry kernel one launch cuts the columns that the outer solve
+// has frozen or is about to end on, and the exit stores to the outer solve's active columns only (gcr_multi_flex.hip).  Without it
+// every launch is what it was.
+static int gcr32_apply_multi(Gcr32State *g, const cplx *f, cplx *y, int k, unsigned active, const MFlexGate *gate = nullptr) {
     MGCR_TRY(g32m_storage(g, k));
     Gcr32MultiState *m = g->mw;
     const int64_t n = g->n, nv = g->nv, slot = g->nv * k;
@@ -442,6 +445,7 @@ static int gcr32_apply_multi(Gcr32State *g, const cplx *f, cplx *y, int k, unsig
         return g32m_launch(g32m_entry_kernel<KC>, gs, (k + KC - 1) / KC, 1, f, m->r, m->rg, m->x, nv, n, k, active, m->st, m->S2);
     });
     MGCR_TRY(erc);
+    if (gate) MGCR_TRY(mflex_gate(*gate, k, m->st));
     const int K = k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : k <= 8 ? 8 : 16;
     for (int it = 1; it <= g->max_iter; it++) {
         const int nd = (it - 1) % g->restart;   // directions stored when the step starts; the new one goes into slot nd
@@ -468,10 +472,26 @@ static int gcr32_apply_multi(Gcr32State *g, const cplx *f, cplx *y, int k, unsig
         MGCR_TRY(g32m_launch(g32m_update_kernel, gs, k, 1, (float *)m->x, (float *)m->r, m->rg, (const float *)(m->ps + (size_t)slot * nd),
                              (const float *)(m->aps + (size_t)slot * nd), nv, n, k, (const double *)m->partsA, gs, m->st, it, nd, m->S2));
     }
+    if (gate) return mflex_exit(*gate, (const c32 *)m->x, y, nv, n, k, (const double *)m->S2, gs, m->st);
     return g32m_dispatch_kc(k, 4, [&](auto kcc) {
         constexpr int KC = decltype(kcc)::value;
         return g32m_launch(g32m_exit_kernel<KC>, gs, (k + KC - 1) / KC, 1, (const c32 *)m->x, y, nv, n, k, (const double *)m->S2, gs, m->st);
     });
+}
+
+// what the right_precond slot of the flexible batched solve (mgcr_gcr_solve_multi on n rows) asks of a low-precision GCR; k is not
+// compared (gcr32_slot_check: a preconditioner at another k is legitimate)
+int gcr32_multi_slot_check(const Op *low, int64_t n, const char *who) {
+    MGCR_CHECK(low->g32 && !low->g32->eo, MGCR_ERR_UNSUPPORTED, "%s: the even-odd form of the low-precision GCR has no batched inner solve", who);
+    MGCR_CHECK(low->g32->n == n, MGCR_ERR_INVALID, "%s: the low-precision GCR has %lld rows, the operator of the solve %lld", who, (long long)low->g32->n,
+               (long long)n);
+    return MGCR_OK;
+}
+
+int gcr32_apply_multi_raw(Op *low, const cplx *f, cplx *y, int64_t n, int k, const MFlexGate *gate) {
+    Gcr32State *g = low->g32;
+    MGCR_CHECK(g->n == n, MGCR_ERR_INVALID, "low-precision GCR of %lld rows applied to a block of %lld rows", (long long)g->n, (long long)n);
+    return gcr32_apply_multi(g, f, y, k, (1u << k) - 1u, gate);   // (k <= MV_MAX_K = 16)
 }
 
 static int g32m_work(Gcr32State *g, int k) {

@@ -101,4 +101,8 @@ int gcr32_eo_slot_check(const Gcr32EoState *e, const Op *A);
 // ---- gcr32_multi.hip: the k-wide lockstep inner solve ------------------------------------------------------------------------------
 void gcr32_multi_destroy(Gcr32MultiState *m);
 
+// ---- gcr_multi_flex.hip: the two launches a k-wide apply takes on when an outer batched solve hands it its state (MFlexGate) ----------
+int mflex_gate(const MFlexGate &g, int k, G32Dev *st32);
+int mflex_exit(const MFlexGate &g, const c32 *x, cplx *y, int64_t nv, int64_t n, int k, const double *S2, int nblkS, G32Dev *st32);
+
 }  // namespace mgcr

@@ -13,6 +13,11 @@
 // Rule for the arithmetic: rows per thread, grid size, summation trees and folds are those of the single kernels (multi_dev.h),
 // the element-wise expressions are copied from them: history, iteration count, convergence flag and x of column j are
 // bit-identical to mgcr_gcr_solve on (A, param, rhs_j) wherever that solve sums in the plain row order (see include/mgcr.h).
+//
+// With a flexible right preconditioner M (gcr_multi_run only; host code — MRun::precondition — on the kernels above): the single lean
+// cycle's flexible form per column, r in place in MWork::r, D = M r in the slot of the next direction or in MWork::z on a closing
+// step.  M is a low-precision GCR, run as the k-wide lockstep inner solve of gcr32_multi.hip, or any operator of the k-wide apply; the
+// kernels that keep it off the frozen columns' slots are gcr_multi_flex.hip's (Rule F of include/mgcr.h).
 #include <climits>
 #include <cmath>
 
@@ -524,7 +529,9 @@ struct MWork {
     std::vector<void *> ptrs;
     int64_t n = -1;
     int k = 0, storage = 0, cap = 0;
+    bool flex = false;
     cplx *r = nullptr, *ar = nullptr, *den = nullptr;
+    cplx *z = nullptr;   // a flexible solve's M r on the step that closes a cycle (and the block another operator than a low-precision GCR writes)
     cplx *xq = nullptr, *bq = nullptr;   // the queued solve's x and b blocks (made by its first call at this n and k)
     std::vector<cplx *> ps, aps;
     DevState *st = nullptr;
@@ -537,7 +544,7 @@ struct MWork {
         for (void *p : ptrs) hipFree(p);
         ptrs.clear();
         ps.clear(); aps.clear();
-        xq = bq = nullptr;
+        xq = bq = z = nullptr;
         n = -1;
     }
     template <typename T>
@@ -550,14 +557,16 @@ struct MWork {
         ptrs.push_back((void *)*p);
         return MGCR_OK;
     }
-    int prepare(int64_t n_, int k_, int storage_, int cap_) {
-        if (n == n_ && k == k_ && storage == storage_ && cap >= cap_) return MGCR_OK;
+    // flex_: the solve is flexible and wants the block z as well (storage made by a flexible solve serves a plain one, not the reverse)
+    int prepare(int64_t n_, int k_, int storage_, int cap_, bool flex_ = false) {
+        if (n == n_ && k == k_ && storage == storage_ && cap >= cap_ && (flex || !flex_)) return MGCR_OK;
         release();
         const size_t ne = (size_t)n_ * (size_t)k_;
         ps.assign((size_t)storage_, nullptr);
         aps.assign((size_t)storage_, nullptr);
         int rc = alloc(&r, ne);
         if (rc == MGCR_OK) rc = alloc(&ar, ne);
+        if (rc == MGCR_OK && flex_) rc = alloc(&z, ne);
         for (int s = 0; s < storage_ && rc == MGCR_OK; s++) {
             rc = alloc(&ps[(size_t)s], ne);
             if (rc == MGCR_OK) rc = alloc(&aps[(size_t)s], ne);
@@ -572,7 +581,7 @@ struct MWork {
         if (rc == MGCR_OK) rc = alloc(&partsB, (size_t)MV_MAX_K * LND * 2 * RED_MAX_BLOCKS);
         if (rc == MGCR_OK) rc = alloc(&dhist, (size_t)k_ * cap_);
         if (rc != MGCR_OK) { release(); return rc; }
-        n = n_; k = k_; storage = storage_; cap = cap_;
+        n = n_; k = k_; storage = storage_; cap = cap_; flex = flex_;
         return MGCR_OK;
     }
     int prepare_queue() {
@@ -591,6 +600,7 @@ MWork g_work;
 struct MRun {
     MWork &wk = g_work;
     Op *A = nullptr;
+    Op *M = nullptr;          // the flexible right preconditioner (gcr_multi_run only), or nullptr
     int64_t n = 0;
     int k = 0, max_it = 0, cap = 0;
     int g = 0, gx = 0;        // blocks of the RED_THREADS kernels / of the 256-thread ones (m_close_x_kernel, m_pending_x_kernel)
@@ -600,13 +610,13 @@ struct MRun {
 
     dim3 grid_of(int blocks, int z = 1) const { return dim3((unsigned)blocks, (unsigned)groups, (unsigned)z); }
 
-    int setup(Op *A_, int64_t n_, int k_, int storage, int max_it_) {
-        A = A_; n = n_; k = k_; max_it = max_it_; cap = max_it + 1;
+    int setup(Op *A_, int64_t n_, int k_, int storage, int max_it_, Op *M_ = nullptr) {
+        A = A_; M = M_; n = n_; k = k_; max_it = max_it_; cap = max_it + 1;
         g = red_grid(n);
         gx = g * 4 > 2048 ? 2048 : g * 4;
         kc = mv_group(k);
         groups = (k + kc - 1) / kc;
-        MGCR_TRY(wk.prepare(n, k, storage, cap));
+        MGCR_TRY(wk.prepare(n, k, storage, cap, M != nullptr));
         hipStream_t stream = ctx().stream;
         MGCR_HIP(hipMemsetAsync(wk.dhist, 0, sizeof(double) * (size_t)k * cap, stream));
         MGCR_HIP(hipMemsetAsync(wk.lc, 0, sizeof(LeanCoef) * MV_MAX_K, stream));
@@ -622,18 +632,23 @@ struct MRun {
     // Enqueues one step (slot bookkeeping: QueueStep): alpha, the residual update, the bookkeeping of the columns at their last step
     // — after which a step that is the last for all of them ends — the k-wide apply, the beta dots, the coefficients, on a closing
     // step the x / P0 update of the block x, and the build.
+    // With a flexible right preconditioner M (step_residual_lean's flexible form, per column): r stays in wk.r — the residual ring is
+    // not written —, the direction start D = M r goes where the plain step leaves r', into the slot of the next direction, or into
+    // wk.z on the step that closes a cycle; there is no preconditioner behind the last update.
     template <bool QUEUED>
     int step(const QueueStep &s, cplx *x) {
         const int it = s.it, lim = s.lim;
         const DevState *st = wk.st;
         const MCoef *coef = wk.coef;
-        const cplx *rin = s.cur >= 1 ? wk.ps[(size_t)s.cur] : wk.r;
-        cplx *dslot = s.nxt >= 1 ? wk.ps[(size_t)s.nxt] : wk.r;
+        const cplx *rin = M || s.cur < 1 ? wk.r : wk.ps[(size_t)s.cur];
+        cplx *dslot = s.nxt >= 1 ? wk.ps[(size_t)s.nxt] : (M ? wk.z : wk.r);   // what the new direction is started from
+        cplx *rnew = M ? wk.r : dslot;
         MK(m_alpha_kernel, dim3((unsigned)k), RED_THREADS, wk.st, it, (const double *)wk.partsA, g, wk.den, s.cur, wk.lc, wk.coef);
         MGCR_TRY(launch_kc(kc, [](auto KC) { return m_xr_kernel<KC>; }, grid_of(g), RED_THREADS, st, it, coef, (const cplx *)wk.aps[(size_t)s.cur],
-                           rin, dslot, n, k, wk.partsR));
+                           rin, rnew, n, k, wk.partsR));
         if (s.any_last) MK((m_finish_kernel<QUEUED>), dim3((unsigned)k), RED_THREADS, wk.st, it, (const double *)wk.partsR, g, wk.dhist, cap, max_it);
         if (s.all_last) return MGCR_OK;
+        if (M) MGCR_TRY(precondition(it, dslot));
         MGCR_TRY(op_apply_multi_raw(A, dslot, wk.ar, n, k));
         constexpr int NDT = 2;
         MGCR_TRY(launch_kc(kc, [](auto KC) { return m_dot_kernel<KC, NDT>; }, grid_of(g, (lim + NDT - 1) / NDT), RED_THREADS, (const cplx *)wk.ar, d,
@@ -643,8 +658,23 @@ struct MRun {
         if (s.closing)
             MGCR_TRY(launch_kc(kc, [](auto KC) { return m_close_x_kernel<KC, QUEUED>; }, grid_of(gx), 256, st, it, coef, (const LeanCoef *)wk.lc, d,
                                lim, (const cplx *)dslot, wk.ps[0], x, n, k, max_it));
-        MGCR_TRY(launch_kc(kc, [](auto KC) { return m_build_kernel<KC, QUEUED>; }, grid_of(g), RED_THREADS, st, it, coef, d, lim, (const cplx *)dslot,
+        MGCR_TRY(launch_kc(kc, [](auto KC) { return m_build_kernel<KC, QUEUED>; }, grid_of(g), RED_THREADS, st, it, coef, d, lim, (const cplx *)rnew,
                            (const cplx *)wk.ar, wk.aps[(size_t)s.nxt], n, k, wk.partsA, max_it));
+        return MGCR_OK;
+    }
+
+    // D = M r behind outer step `it`'s residual update (flex_precond_apply of gcr.hip, per column), into the columns of `out` that are
+    // active at that step: a frozen column's slot holds x updates that are still pending.  A low-precision GCR runs as the k-wide
+    // lockstep inner solve, handed the columns' states (MFlexGate: the inner solves of frozen columns, and of columns about to end on
+    // this residual, are cut to 0 steps); every other operator is applied k-wide into wk.z, whose active columns are then copied.
+    // it == 0: the start, out == wk.z — every column takes part, nothing is gated (gcr_start applies M the same way).
+    int precondition(int it, cplx *out) {
+        if (M->kind == OP_GCR32) {
+            const MFlexGate gate{wk.st, it, wk.partsR, g};
+            return gcr32_apply_multi_raw(M, wk.r, out, n, k, it > 0 ? &gate : nullptr);
+        }
+        MGCR_TRY(op_apply_multi_raw(M, wk.r, wk.z, n, k));
+        if (out != wk.z) MGCR_TRY(mflex_take(wk.st, it, wk.z, out, n, k, gx));
         return MGCR_OK;
     }
 };
@@ -668,8 +698,9 @@ void multi_release() {
     mvec_release();
 }
 
-static int64_t g_multi_solves = 0;
+static int64_t g_multi_solves = 0, g_multi_flex_solves = 0;
 int64_t gcr_multi_solve_count() { return g_multi_solves; }
+int64_t gcr_multi_flex_solve_count() { return g_multi_flex_solves; }
 
 int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int64_t n, int k, double *hist, int hist_cap, int *n_iter,
                   int *converged) {
@@ -680,8 +711,9 @@ int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int6
     if (p.max_iter >= 1 && p.max_iter + 1 < storage) storage = p.max_iter + 1;
     MGCR_CHECK(storage <= LND, MGCR_ERR_UNSUPPORTED, "batched GCR: restart cycles of at most %d steps (the lean cycle) are supported", LND);
     const int max_it = p.max_iter > 0 ? p.max_iter : 1;
+    Op *M = p.flexible ? (Op *)p.right_precond : nullptr;   // (the entry point lets no other preconditioner through)
     MRun run;
-    MGCR_TRY(run.setup(A, n, k, storage, max_it));
+    MGCR_TRY(run.setup(A, n, k, storage, max_it, M));
     MWork &wk = run.wk;
     const int g = run.g, kc = run.kc, cap = run.cap;
     const size_t ne = (size_t)n * (size_t)k;
@@ -700,8 +732,14 @@ int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int6
     } else {
         MGCR_TRY(mv_copy(r, rhs, n, k));
     }
-    MGCR_TRY(mv_copy(wk.ps[0], r, n, k));                       // P0 = r0
-    MGCR_TRY(op_apply_multi_raw(A, r, wk.aps[0], n, k));        // Ap0
+    if (M) {                                                    // flexible: Z = M r0, P0 = Z, Ap0 = A P0 (gcr.hip start_vectors)
+        MGCR_TRY(run.precondition(0, wk.z));
+        MGCR_TRY(mv_copy(wk.ps[0], wk.z, n, k));
+        MGCR_TRY(op_apply_multi_raw(A, wk.ps[0], wk.aps[0], n, k));
+    } else {
+        MGCR_TRY(mv_copy(wk.ps[0], r, n, k));                   // P0 = r0
+        MGCR_TRY(op_apply_multi_raw(A, r, wk.aps[0], n, k));    // Ap0
+    }
     MGCR_TRY(launch_kc(kc, [](auto KC) { return m_init_partials_kernel<KC, false>; }, run.grid_of(g), RED_THREADS, rhs, (const cplx *)r,
                        (const cplx *)wk.aps[0], n, k, wk.partsN, wk.partsR, wk.partsA, 0u, (cplx *)nullptr));
     MK(m_init_kernel, dim3((unsigned)k), RED_THREADS, wk.st, (const double *)wk.partsN, (const double *)wk.partsR, g, wk.dhist, cap);
@@ -741,6 +779,7 @@ int gcr_multi_run(Op *A, const mgcr_gcr_param &p, const cplx *rhs, cplx *x, int6
     MGCR_HIP(hipMemcpy(hh.data(), wk.dhist, sizeof(double) * hh.size(), hipMemcpyDeviceToHost));
     for (int j = 0; j < k; j++) report_column(p, j, hs[(size_t)j].iter, hh.data() + (size_t)j * cap, hist, hist_cap, n_iter, converged);
     g_multi_solves++;
+    if (M) g_multi_flex_solves++;
     return resident_check();
 }
 

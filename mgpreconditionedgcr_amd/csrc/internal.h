@@ -465,6 +465,23 @@ int gcr32_slot_check(const mgcr_gcr_param *p, const Op *A);   // the preconditio
 int64_t gcr32_apply_count();  // applies that ran on the device (not silenced by an outer solve that was over): one synchronisation
 int64_t gcr32_step_count();   // the inner steps those enqueued
 int64_t gcr32_multi_stat(int which);   // gcr32_multi.hip — 0: batched applies enqueued, 1: the lockstep steps those enqueued
+// The batched form of Gcr32Gate: the flexible batched solve's per-column device state (gcr_multi.hip), handed to the k-wide apply that
+// follows outer step `it`'s residual update.  Column j's inner solve is cut to 0 steps when the outer column is frozen or about to end
+// on partsR[j] (nblk partials per column, stride RED_MAX_BLOCKS), and the result is stored to the columns still active at `it` only
+// (gcr_multi_flex.hip)
+struct MFlexGate {
+    const DevState *st = nullptr;
+    int it = 0;
+    const double *partsR = nullptr;
+    int nblk = 0;
+};
+// Y ~ A^-1 F per column, the lockstep inner solve of mgcr_gcr32_apply_multi with every column taking part.  gate == nullptr: its
+// launches, every column of y written; else the gate behind the entry kernel and the masked exit in place of the plain one
+int gcr32_apply_multi_raw(Op *low, const cplx *f, cplx *y, int64_t n, int k, const MFlexGate *gate);
+int gcr32_multi_slot_check(const Op *low, int64_t n, const char *who);   // the flexible batched solve's right_precond slot
+// the columns of z that are active at step `it` into the same columns of `slot` (gcr_multi_flex.hip; blocks: 256-thread workgroups per column group)
+int mflex_take(const DevState *st, int it, const cplx *z, cplx *slot, int64_t n, int k, int blocks);
+int64_t gcr_multi_flex_solve_count();  // gcr_multi.hip: flexible batched solves completed
 
 // ---- mvec.hip / spmm.hip / gcr_multi.hip: blocks of k Fields ------------------------------------
 int mv_copy(cplx *dst, const cplx *src, int64_t n, int k);
