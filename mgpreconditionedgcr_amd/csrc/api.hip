@@ -239,6 +239,11 @@ int mgcr_set_option(const char *name, int value, int *previous) {
         if (previous) *previous = p;
         return MGCR_OK;
     }
+    if (!strcmp(name, "step_build_pair_late")) {   // 0 off, 1 the late-r pair forms that cleared their gate, 2 every built one (gcr_steppair_late.hip)
+        const int p = set_stepbuild_pair_late(value);
+        if (previous) *previous = p;
+        return MGCR_OK;
+    }
     bool prev;
     if (!strcmp(name, "pattern_storage")) prev = set_patterns_enabled(value != 0);
     else if (!strcmp(name, "stencil_storage")) prev = set_stencil_enabled(value != 0);
@@ -267,11 +272,13 @@ int mgcr_stat(const char *name, int64_t *value) {
     if (!strcmp(name, "resident_solves")) *value = resident_solve_count();
     // The three step counters count steps by FORM, not by kernel symbol: every one-launch step | those at >= 4 directions that read
     // r once | those whose apply takes its own r from the diagonal gather.  A step that runs as step_pair_kernel (gcr_steppair.hip)
-    // is counted by each of them it belongs to, and by step_pair_launches, which alone says which kernel ran.
+    // or step_pair_late_kernel (gcr_steppair_late.hip) is counted by each of them it belongs to; step_pair_launches (a pair kernel
+    // at 1..4 directions) and step_pair_late_launches (the late-r kernel, the close at 5 included) say which kernel ran.
     else if (!strcmp(name, "step_build_launches")) *value = stepbuild_launch_count();
     else if (!strcmp(name, "step_keep_wide_launches")) *value = stepbuild_keep_wide_launch_count();
     else if (!strcmp(name, "step_apply_own_launches")) *value = stepbuild_apply_own_launch_count();
     else if (!strcmp(name, "step_pair_launches")) *value = stepbuild_pair_launch_count();
+    else if (!strcmp(name, "step_pair_late_launches")) *value = stepbuild_pair_late_launch_count();
     else if (!strcmp(name, "start_build_launches")) *value = start_build_launch_count();
     else if (!strcmp(name, "small_solves")) *value = gcr_small_solve_count();
     else if (!strcmp(name, "one_launch_fallbacks")) *value = gcr_fallback_count();

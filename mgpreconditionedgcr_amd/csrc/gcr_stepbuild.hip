@@ -465,8 +465,10 @@ static int64_t g_keep_wide_launches = 0;   // ... of them, step_keep_wide_kernel
 int64_t stepbuild_keep_wide_launch_count() { return g_keep_wide_launches; }
 static int64_t g_apply_own_launches = 0;   // ... of them, keep forms whose apply takes the own r from the diagonal gather (sb_apply_form 1, 2)
 int64_t stepbuild_apply_own_launch_count() { return g_apply_own_launches; }
-static int64_t g_pair_launches = 0;        // ... of them, launched as step_pair_kernel (gcr_steppair.hip)
+static int64_t g_pair_launches = 0;        // ... of them, launched as step_pair_kernel (gcr_steppair.hip) or, at 3 and 4 directions, its late-r form
 int64_t stepbuild_pair_launch_count() { return g_pair_launches; }
+static int64_t g_pair_late_launches = 0;   // ... of them, launched as step_pair_late_kernel (gcr_steppair_late.hip), the close at 5 included
+int64_t stepbuild_pair_late_launch_count() { return g_pair_late_launches; }
 
 // The instantiation a step with `nd` stored directions launches (sb_kernel).
 // KEEP-ALL (step_keep_kernel) where an instantiation keeps 0 scratch and 8 waves per SIMD: up to 2 stored directions in every
@@ -623,9 +625,17 @@ int csr_step_build(const CsrDev &A, const cplx *x, bool shift, cplx k, const cpl
     // The pair form (gcr_steppair.hip) of a keep step whose apply takes the own r from the diagonal gather: one workgroup per CU
     // carries two of the 512 logical ones.  Built for the operator itself, not for 1 - k A (a DiracOp keeps the keep forms).  Asked per
     // launch like everything above; where it does not fit, the keep form runs.
-    const void *pair = own && !shift && g_sb_keep_all.on() && a.nlogical == SB_PAIR_LOGICAL && exchange_shared().cus >= SB_PAIR_GRID
-                           ? sb_pair_kernel(nd, xr, close, realc) : nullptr;
-    if (pair && launch_is_coresident(pair, RED_THREADS, SB_PAIR_LDS, SB_PAIR_GRID)) {
+    const bool pair_ok = own && !shift && g_sb_keep_all.on() && a.nlogical == SB_PAIR_LOGICAL && exchange_shared().cus >= SB_PAIR_GRID;
+    const void *pair = pair_ok ? sb_pair_kernel(nd, xr, close, realc) : nullptr;
+    // Its late-r form (gcr_steppair_late.hip) loads r again from a.x in the build: a.x must be a vector the launch does not write.
+    // The drivers hand in a residual of the ring that is neither the next one nor a direction; where that does not hold, the forms
+    // above run.
+    const void *late = pair_ok && a.x != a.xr_out && a.x != a.p_out ? sb_pair_late_kernel(nd, xr, close, realc) : nullptr;
+    if (late && launch_is_coresident(late, RED_THREADS, SB_PAIR_LDS, SB_PAIR_GRID)) {
+        MGCR_TRY(sb_launch(late, &a, SB_PAIR_GRID, SB_PAIR_LDS, "csr_step_build (late-r pair form)"));
+        g_pair_late_launches++;
+        if (!close) g_pair_launches++;   // (a pair step at 1..4 directions, whichever of the two kernels ran it)
+    } else if (pair && launch_is_coresident(pair, RED_THREADS, SB_PAIR_LDS, SB_PAIR_GRID)) {
         MGCR_TRY(sb_launch(pair, &a, SB_PAIR_GRID, SB_PAIR_LDS, "csr_step_build (pair form)"));
         g_pair_launches++;
     } else {

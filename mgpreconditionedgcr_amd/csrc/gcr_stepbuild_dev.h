@@ -127,6 +127,8 @@ __device__ __forceinline__ double sb_stage_rr(int nblk, const double *lds_rr) {
 
 // gcr_steppair.hip: the pair form of a keep step (nullptr: that step has none in this build / by the gate), its dynamic LDS, its grid
 const void *sb_pair_kernel(int nd, bool xr, bool close, bool realc);
+// gcr_steppair_late.hip: its late-r form (nullptr: none built / not by the gate and option step_build_pair_late / pair forms off)
+const void *sb_pair_late_kernel(int nd, bool xr, bool close, bool realc);
 constexpr size_t SB_PAIR_LDS = sizeof(cplx) * RED_THREADS * 2 * SB_MAX_TRIPS;   // A r of eight rows per thread
 constexpr int SB_PAIR_LOGICAL = 512, SB_PAIR_GRID = SB_PAIR_LOGICAL / 2;
 

@@ -314,7 +314,10 @@ bool set_start_build_enabled(bool on);         // ... and the start of a solve a
 int64_t start_build_launch_count();
 bool set_stepbuild_keep_all_enabled(bool on);  // ... every one-launch step reads r once (step_keep_kernel)
 bool set_stepbuild_pair_enabled(bool on);      // gcr_steppair.hip: one workgroup per CU carries two logical ones (step_pair_kernel)
-int64_t stepbuild_pair_launch_count();         // one-launch steps that ran as step_pair_kernel
+bool stepbuild_pair_is_enabled();
+int64_t stepbuild_pair_launch_count();         // one-launch steps at 1..4 directions that ran as a pair kernel (step_pair_kernel or step_pair_late_kernel)
+int set_stepbuild_pair_late(int mode);         // gcr_steppair_late.hip: 0 off, 1 the forms that cleared the gate, 2 every built form; returns the previous mode
+int64_t stepbuild_pair_late_launch_count();    // launches of step_pair_late_kernel, the close at 5 included
 int coherence_selftest(int steps, int coherent, int64_t *rows_wrong);   // gcr_resident.hip
 bool stepbuild_is_enabled();
 bool launch_is_coresident(const void *kernel, int threads, size_t dyn_lds, int grid);   // gcr_stepbuild.hip: asks the runtime
