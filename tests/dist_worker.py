@@ -6,6 +6,8 @@ modes
   plan   (CPU, gloo)  partition plan + numpy SpMV through the plan's halo lists vs the global SpMV
   gcr    (GPU, gloo-staged transport; all ranks may share GPU 0) distributed SpMV and GCR on the
          HIP path vs what the caller computes in one process
+  gcr-coeffs  the gcr body over the kinds "coeffs48" / "coeffs48c" only: 48^3 boxes with seven distinct stencil coefficients
+         (tests/stencil_coeff_cases.py), real and complex — the rare-tail layout of a row block on values that tell the slots apart
 """
 import os
 import sys
@@ -30,6 +32,11 @@ def problem(kind):
         n = 6 if kind == "poisson" else 48
         N, ncol, rowptr, col, val = problems.poisson3d_csr(n)
         return N, rowptr, col, val, (n * n)  # rows per plane: slabs must hold whole planes
+    if kind in ("coeffs48", "coeffs48c"):
+        from tests.stencil_coeff_cases import DIST_KINDS, box_csr
+        dims, which = DIST_KINDS[kind]
+        N, ncol, rowptr, col, val = box_csr(*dims, which)
+        return N, rowptr, col, val, dims[1] * dims[2]
     rng = np.random.default_rng(7)
     N = 1000
     rowptr, col, val = problems.random_csr(N, N, rng, min_len=1, max_len=9)
@@ -294,7 +301,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
         return
-    for kind in ("poisson", "random") + (("poisson48",) if mode == "gcr" else ()):
+    for kind in ("coeffs48", "coeffs48c") if mode == "gcr-coeffs" else ("poisson", "random") + (("poisson48",) if mode == "gcr" else ()):
         N, rowptr, col, val, gran = problem(kind)
         offs = split_rows(N // gran, world)
         r0, r1 = offs[rank] * gran, offs[rank + 1] * gran

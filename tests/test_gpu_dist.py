@@ -155,6 +155,54 @@ def test_distributed_gcr_matches_single_process(tmp_path, world):
             assert np.abs(xd - xs.to_numpy()).max() <= max(1e-7 * np.abs(xs.to_numpy()).max(), 20 * xsens)
 
 
+@pytest.mark.parametrize("world", [2, 3])
+def test_distributed_stencil_coefficients(tmp_path, world):
+    """The rare-tail layout of a distributed row block (stencil view: 7 common slots, the halo columns as a leading slot and a rare one
+    behind the common sum) on 48^3 boxes with seven DISTINCT coefficients, real and complex (tests/stencil_coeff_cases.py): on the
+    Poisson kinds above a kernel that pairs a slot with another slot's coefficient gives the same bits.  Apply, restart-4 and
+    truncation-11 histories and x against the oracle in the distributed device's order."""
+    from tests.dist_worker import split_rows
+    mg.init()
+    res = run_workers("gcr-coeffs", world, tmp_path, timeout=240)
+    for kind in ("coeffs48", "coeffs48c"):
+        N, rowptr, col, val, gran = problem(kind)
+        assert all(res[r][kind]["format"] == 3 for r in range(world)), [res[r][kind]["format"] for r in range(world)]
+        allreduce = res[0][kind]["allreduce"]
+        assert allreduce in ("peer-write", "host") and all(res[r][kind]["allreduce"] == allreduce for r in range(world))
+        for r in range(world):
+            assert np.array_equal(res[r][kind]["hist"], res[r][kind]["hist_notail"]), (kind, r)
+            assert np.array_equal(res[r][kind]["x"], res[r][kind]["x_notail"]) and np.array_equal(res[r][kind]["y"], res[r][kind]["y_unsplit"]), (kind, r)
+        Ao = orc.csr(N, N, rowptr, col, val)
+        x, b = problems.rhs_grid(N, 5), problems.rhs_grid(N, 1)
+        offs = np.array(split_rows(N // gran, world), np.int64) * gran
+        # the rank totals are added in rank order — which the peer-write all-reduce guarantees; with two ranks any order gives the same bits
+        exact = allreduce == "peer-write" or world == 2
+        print(kind, "world", world, "all-reduce", allreduce, "halo", res[0][kind]["halo"], "bit for bit" if exact else "sensitivity envelope")
+        modes = (("", dict(restart=4, max_iter=25, tol=1e-30)), ("_trunc", dict(truncation=11, max_iter=25, tol=1e-30)))
+        with orc.device_order(rank_offsets=offs, lean=True):
+            assert np.array_equal(np.concatenate([res[r][kind]["y"] for r in range(world)]), Ao(x)), kind
+            refs = {tag: orc.gcr_solve(Ao, orc.gcr_param(**okw), b) for tag, okw in modes}
+        for tag, okw in modes:
+            xo, ho, ito, _ = refs[tag]
+            xd = np.concatenate([res[r][kind]["x" + tag] for r in range(world)])
+            for r in range(world):
+                h = res[r][kind]["hist" + tag]
+                assert np.array_equal(h, res[0][kind]["hist" + tag]), (kind, tag, r)     # every rank sees identical scalars
+                assert h.size == ho.size == 26 and np.isfinite(h).all() and h[-1] < h[0], (kind, tag, r)
+            h = res[0][kind]["hist" + tag]
+            if exact:
+                assert np.array_equal(h, ho), (kind, tag, int(np.argmax(h != ho)))
+                assert np.array_equal(xd, xo), (kind, tag, int((xd != xo).sum()))
+            else:
+                # three ranks on the host all-reduce: the envelope of test_distributed_gcr_matches_single_process — how far the
+                # reference algorithm itself moves when its dot products are summed in another order
+                _, sens, _ = orc.gcr_reorder_sensitivity(Ao, orc.gcr_param(**okw), b)
+                _, xsens = orc.gcr_x_sensitivity(Ao, orc.gcr_param(**okw), b)
+                tol = np.maximum(1e-8 * ho, 8 * sens) + 1e-17
+                assert (np.abs(h - ho)[1:] <= tol[1:]).all(), (kind, tag)
+                assert np.abs(xd - xo).max() <= max(1e-7 * np.abs(xo).max(), 20 * xsens), (kind, tag)
+
+
 def test_rccl_single_rank_collectives(tmp_path):
     """RCCL binding on the one GPU we have: a 1-rank communicator with the fold + ncclAllReduce path
     forced on (MGCR_TEST_FORCE_COLLECTIVES) must reproduce the plain single-GPU solve bit for bit."""
